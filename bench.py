@@ -19,6 +19,18 @@ in HBM before the timed region.
   More ranks than GPUs (tests on a one-GPU box): torch.distributed falls back to gloo for the bookkeeping and
   `--rccl-library` must name a stand-in for librccl (tests/mock_rccl/mock_rccl_shm.cpp); never a measurement.
 
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, `--dump-outputs` if asked
+for, the JSON line.  `--full` adds everything else the line can carry -- the three extra timing windows, the STREAM
+triad, the 256^3 and 64^3 / 128^3 side measurements, the reference's kernel on this GPU, the CPU baseline and, at N > 1,
+the chain's parity check -- each of which takes runs of its own; the `--no-...` switches leave single ones out of a
+`--full` run.
+
+`--dump-outputs DIR` writes, after the timed steps, what they computed as a caller of the stepping path receives it:
+DIR/receiver.npy (the receiver's pressure at each of the K timed steps, float64), DIR/current.npy and
+DIR/previous.npy (both fields after the last timed step, in the run's precision: the planes through and next to the
+source, or a fixed seeded sample of them where three planes exceed 24 MB).  At N > 1 each rank writes what it holds,
+as <name>.rank<r>.npy.  The inputs are fixed by the arguments, so two builds can be compared array for array.
+
 Prints ONE JSON line on rank 0 (see the README of the driver contract); `roofline` is for the
 dominant kernel, timed with HIP events on the engine's stream: the two-step pass (pair_march_kernel:
 one launch advances every node by TWO time steps and moves 4 x 8 B per node, 16 B per node-update) --
@@ -30,11 +42,11 @@ quoted only for the very device code, kernel and workload it was measured on) wh
 algorithmic bytes; `frac_definition` says which, `frac_algorithmic` / `frac_measured_traffic` give both, and every fraction
 in the line can be recomputed from fields of the same line.  `roofline.boundary` = the two boundary launches of a pass (HIP
 events like the march): what stands between the dominant kernel's rate and the whole step's.  `windows`: three more windows of
-steps after the timed region (the driver's K may be a few dozen steps: 61 ms at K = 20), min / median / max.
+steps after the timed region (the driver's K may be a few dozen steps: 61 ms at K = 20), min / median / max (`--full`).
 A run that cannot finish -- a peer rank died, a collective hangs -- ends with the JSON line carrying "error" and a non-zero exit
 status (the engine's watchdog, wv_options::comm_timeout_s; `--deadline` for everything else) instead of hanging.
-`cpu_baseline` is the reference's own kernel compiled for the host (oracle/_ref, kind "reference";
-the C restatement, kind "port", when that is absent) on the host's cores, N = 1 only, on the SAME
+`cpu_baseline` (`--full`; null otherwise) is the reference's own kernel compiled for the host (oracle/_ref, kind
+"reference"; the C restatement, kind "port", when that is absent) on the host's cores, N = 1 only, on the SAME
 mesh for a few steps.
 """
 import hashlib
@@ -82,7 +94,42 @@ def parse_args():
                         "hanging (a stuck collective, a dead peer); 0 = none")
     p.add_argument("--no-windows", action="store_true", help="skip the three extra timing windows after the timed region")
     p.add_argument("--no-parity-check", action="store_true", help="N > 1: skip the small chain-against-single-domain check before the timed run")
+    p.add_argument("--full", action="store_true",
+                   help="also the measurements and checks beyond the headline figure (extra windows, triad, side meshes, the reference "
+                        "on the GPU, the CPU baseline, the chain's parity check); a plain run times the K steps only")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the timed steps computed (receiver trace, sampled final fields) to DIR/<name>.npy")
     return p.parse_args()
+
+
+DUMP_FIELD_BYTES = 24 << 20  # per field: three 1024 x 1024 planes of doubles
+
+
+def dump_outputs(args, eng, E, layout, src_global, world, rank):
+    """--dump-outputs DIR: the receiver's rows of the K timed steps and both fields after the last of them (module docstring)."""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    suffix = ".rank%d" % rank if world > 1 else ""
+
+    def save(name, a):
+        np.save(os.path.join(args.dump_outputs, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+    nz_global = layout.global_dims[2]
+    z_src = src_global // layout.plane
+    elem = np.dtype(eng.dtype).itemsize
+    n_planes = int(max(1, min(3, DUMP_FIELD_BYTES // (layout.plane * elem))))
+    z_a = max(0, min(z_src - n_planes // 2, nz_global - n_planes))
+    lo, hi = max(z_a, layout.z0), min(z_a + n_planes, layout.z1)          # the chosen planes this rank owns
+    if layout.owns_z(z_src):
+        save("receiver", eng.fetch_receivers(args.warmup, args.steps))
+    if lo >= hi:
+        return
+    keep = None
+    if (hi - lo) * layout.plane * elem > DUMP_FIELD_BYTES:                  # wide planes: the same seeded sample every run
+        rng = np.random.default_rng(20240)
+        keep = np.sort(rng.choice((hi - lo) * layout.plane, DUMP_FIELD_BYTES // elem, replace=False))
+    for name, buf in (("current", E.BUF_CURRENT), ("previous", E.BUF_PREVIOUS)):
+        field = eng.read_planes(lo - layout.zl0, hi - lo, buf).reshape(-1)
+        save(name, field if keep is None else field[keep])
 
 
 def kernel_sources_hash():
@@ -343,7 +390,7 @@ def run_bench(args, guard):
         dist.barrier()
 
     halo_parity = None
-    if world > 1 and not args.no_parity_check:
+    if world > 1 and args.full and not args.no_parity_check:
         guard.phase = "chain parity check on this machine's links"
         halo_parity = chain_parity_check(args, rank, world, local_rank, coll_device, dist, torch)
         dist.barrier()
@@ -371,7 +418,8 @@ def run_bench(args, guard):
 
     # canonical pairing: calibrated hard-source impulse at the centre of the global mesh, one
     # receiver a few nodes away (canonical.h:55-81), both device resident
-    # three more windows after the timed region, each long enough for half a second or so (the driver's K may be 20 steps)
+    # three more windows after the timed region, each long enough for half a second or so (the driver's K may be 20 steps);
+    # the source signal covers them whether they run (--full) or not, so that every run steps the same inputs
     window_steps = 0 if args.no_windows else max(args.steps, min(400, 2 * int(0.25 * 360e9 / (nx * ny * args.nz)) + 2))
     total_steps = args.warmup + args.steps + 3 * window_steps
     signal = np.zeros(total_steps)
@@ -456,8 +504,11 @@ def run_bench(args, guard):
                             "launches": int(launches), "time_steps_per_launch": round(timed_steps / launches, 3)}
         kernel_ms, launches, timed_steps = triple_ms, t_n, 3 * t_n
     eng.enable_kernel_timing(False)
+    if args.dump_outputs:
+        guard.phase = "--dump-outputs"
+        dump_outputs(args, eng, E, layout, src_global, world, rank)
     windows = None
-    if window_steps:
+    if window_steps and args.full:
         guard.phase = "extra timing windows (3 x %d steps)" % window_steps
         rates = []
         for _ in range(3):
@@ -540,7 +591,7 @@ def run_bench(args, guard):
                                           "note": "a three-step pass: boundary launches to t+1, t+2 (ms above; the second also finishes the nodes its 1-D entries face), "
                                                   "to t+3, and the list of every node within two of something that is not a plain node, recomputed from the finished t+2 field"}
     triad = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             triad = round(E.measure_triad(local_rank), 1)
         except Exception:
@@ -607,7 +658,7 @@ def run_bench(args, guard):
     eng.close()
 
     guard.phase = "side measurements"
-    if world == 1 and rank == 0 and not args.no_small and (nx, ny, args.nz) == (1024, 1024, 1024):
+    if world == 1 and rank == 0 and args.full and not args.no_small and (nx, ny, args.nz) == (1024, 1024, 1024):
         # side measurement: BASELINE configs[1] (256^3; the whole working set sits in the 256 MiB
         # Infinity Cache, so it is not an HBM roofline point)
         m2 = M.box_mesh(256, 256, 256, coefficients=M.bench_materials(), surface_of_face=[0, 1, 2, 3, 2, 3])
@@ -644,7 +695,7 @@ def run_bench(args, guard):
             e3.close()
         out["config"]["also_small_meshes"] = small
 
-    if world == 1 and rank == 0 and not args.no_reference_on_gpu:
+    if world == 1 and rank == 0 and args.full and not args.no_reference_on_gpu:
         # the reference's own OpenCL program, JIT-compiled by this box's OpenCL runtime and run on this
         # very GPU (worker process; bounded: 512^3, a few dozen steps) -- context for `value`, not part of it
         try:
@@ -656,7 +707,7 @@ def run_bench(args, guard):
                                                "pressures_promoted_to_f64": ref.bench(512, 30, "f64")}
         except Exception as e:  # a baseline must never sink the bench line
             out["reference_on_gpu"] = {"error": str(e)[:300]}
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, elem)
     elif rank == 0:
         out["cpu_baseline"] = None

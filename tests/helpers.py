@@ -1,7 +1,23 @@
 """Shared test plumbing: run a golden case through the oracle or the engine."""
 import hashlib
+import os
+import tarfile
 
 import numpy as np
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def unpack_reference_inputs(dest, prefix):
+    """The members of tests/golden/reference_inputs.tar.xz under `prefix` (data files of the reference tree: demo project bundles,
+    demo models, boundary_test plots; tests/golden/README.md) unpacked into the directory `dest`.  Returns dest/prefix."""
+    with tarfile.open(os.path.join(GOLDEN, "reference_inputs.tar.xz")) as t:
+        members = [m for m in t.getmembers() if m.name == prefix or m.name.startswith(prefix + "/")]
+        if hasattr(tarfile, "data_filter"):
+            t.extractall(dest, members=members, filter="data")
+        else:
+            t.extractall(dest, members=members)
+    return os.path.join(str(dest), prefix)
 
 
 def sha(a):

@@ -33,7 +33,7 @@ import boundary_test_reproduction as B  # noqa: E402
 import boundary_test_svg as SVG  # noqa: E402
 from wayverb_amd import filters as F  # noqa: E402
 
-REFERENCE_DIR = "/root/reference/bin/boundary_test"
+from helpers import unpack_reference_inputs  # noqa: E402
 
 
 def plot_key(name, az, el):
@@ -51,10 +51,11 @@ def test_the_fixtures_hold_nine_plots_of_105_measured_points(which):
         assert np.all(np.isfinite(m[:, 1]))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_DIR), reason="the reference tree is not on this machine")
 @pytest.mark.parametrize("which", ["transparent", "soft"])
-def test_the_fixtures_are_what_the_recovery_script_makes_of_the_references_plots(which):
-    fresh = SVG.extract(os.path.join(REFERENCE_DIR, "output." + which, "boundary_response.svg"))
+def test_the_fixtures_are_what_the_recovery_script_makes_of_the_references_plots(which, tmp_path):
+    # the reference's two plots, byte for byte (bin/boundary_test/output.{transparent,soft}/boundary_response.svg of its tree)
+    plots = unpack_reference_inputs(tmp_path, "boundary_test_reference")
+    fresh = SVG.extract(os.path.join(plots, which + ".boundary_response.svg"))
     kept = np.load(os.path.join(B.REFERENCE, which + ".npz"))
     assert sorted(fresh) == sorted(kept.files)
     for k in fresh:

@@ -40,7 +40,7 @@ def _free_port():
 def run_bench(world, shm_mock, *extra, timeout=600):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rccl-library", shm_mock,
-           "--no-cpu-baseline", "--no-reference-on-gpu"] + [str(a) for a in extra]
+           "--full", "--no-cpu-baseline", "--no-reference-on-gpu"] + [str(a) for a in extra]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, (out.stdout[-2000:], out.stderr[-3000:])

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
-from helpers import run_engine, run_oracle
+from helpers import run_engine, run_oracle, unpack_reference_inputs
 from oracle.oracle import ReferenceSetup
 from wayverb_amd import mesh as M
 
@@ -372,23 +372,16 @@ def test_multi_surface_scene_to_impulse_response(oracle, built_library):
 
 
 # ---- the reference's own models (its mesh tests load bedroom.obj / echo_tunnel.obj) -------------------
-REF_MODELS = "/root/reference/demo/evaluation/models/object"
-
-
-def _have_models():
-    import os
-    return os.path.isdir(REF_MODELS) and ReferenceSetup.available()
-
-
-@pytest.mark.skipif(not _have_models(), reason="needs /root/reference (models + oracle/_ref)")
+@pytest.mark.skipif(not ReferenceSetup.available(), reason="oracle/_ref not built (needs the reference tree at build time)")
 @pytest.mark.parametrize("model,spacing", [("bedroom", 0.1), ("echo_tunnel", 0.5), ("concert", 0.4417), ("vault", 0.2)])
-def test_setup_chain_on_reference_models(oracle, built_library, model, spacing):
+def test_setup_chain_on_reference_models(oracle, built_library, model, spacing, tmp_path):
     """tests/mesh_setup_tests.cpp:22-28 / mesh_tests.cpp:33-50 build a mesh from the demo models;
     here the same models go through the reference's three set-up kernels (host-compiled) and
     through the restatement, stage by stage, and must agree word for word."""
     import os
     from wayverb_amd import engine as E
-    v, t, names = S.read_obj(os.path.join(REF_MODELS, model + ".obj"))
+    models = unpack_reference_inputs(tmp_path, "models")      # copies of the reference's demo/evaluation/models/object/*.obj
+    v, t, names = S.read_obj(os.path.join(models, model + ".obj"))
     assert t.shape[0] > 0 and int(t[:, 0].max()) + 1 == len(names)
     lo, hi = S.padded_aabb(v, 0.1)               # make_voxelised_scene_data(scene, 5, 0.1f)
     aabb = (lo, hi)

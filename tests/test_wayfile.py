@@ -86,15 +86,15 @@ def test_concert_hall_configuration_builds_and_steps_on_the_cpu_chain(oracle, bu
     assert (np.abs(out["trace"][:, 0]).max() > 0) == (dist_nodes <= steps)
 
 
-def test_every_demo_bundle_of_the_reference_reads():
+def test_every_demo_bundle_of_the_reference_reads(tmp_path):
     """All thirteen project bundles under the reference's demo/evaluation (boxes, the concert hall, the vault with four materials; microphone and
-    HRTF capsules; two receivers) go through the reader.  Needs the reference tree: skipped where it is not (the GPU box); two of the bundles
-    are fixtures of this repository anyway (tests/golden/concert.way, sample.way)."""
+    HRTF capsules; two receivers) go through the reader: copies of them, as the reference's demo/evaluation lays them out, in
+    tests/golden/reference_inputs.tar.xz."""
     import glob
     import os
-    bundles = sorted(glob.glob("/root/reference/demo/evaluation/*/*.way"))
-    if not bundles:
-        pytest.skip("no reference tree here")
+    from helpers import unpack_reference_inputs
+    here = unpack_reference_inputs(tmp_path, "demo_evaluation")
+    bundles = sorted(glob.glob(os.path.join(here, "*", "*.way")))
     assert len(bundles) == 13
     modes = set()
     for path in bundles:

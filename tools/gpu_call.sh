@@ -3,7 +3,7 @@
 # prints a one-line summary; what is to be judged is copied from there into profiles/<round>/.  Tasks:
 #   tests[:<pytest selection>]   pytest -m gpu (default: the whole suite) -> pytest_gpu[_N].txt
 #   smoke                        __graft_entry__.smoke()
-#   bench[:<bench.py args>]      bench.py -> bench[_N].json
+#   bench[:<bench.py args>]      bench.py --full -> bench[_N].json
 #   kernels                      rocprofv3 --kernel-trace --stats of bench.py (short) -> rocprof_kernel_stats.csv
 #   pmc                          FETCH_SIZE / WRITE_SIZE passes of bench.py (separate passes, kernel trace only) -> pmc_summary.json
 #   slabs[:<worlds>[:<tuning>]]  tools/slab_overhead.py for the given worlds (default 2,4,8), twice each -> slab_overhead_one_gpu.txt
@@ -25,7 +25,7 @@ for task in "$@"; do
       grep -h "passed\|failed\|error" $O/pytest_gpu_$n.txt | tail -3 ;;
     smoke) python __graft_entry__.py --smoke > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt ;;
     bench)
-      python bench.py $arg > $O/bench_$n.json 2> $O/bench_$n.err; tail -1 $O/bench_$n.json | cut -c1-400
+      python bench.py --full $arg > $O/bench_$n.json 2> $O/bench_$n.err; tail -1 $O/bench_$n.json | cut -c1-400
       python3 -c "
 import json,sys
 d=json.loads(open('$O/bench_$n.json').read().strip().splitlines()[-1]); r=d['roofline']
