@@ -336,6 +336,23 @@ int wv_run_group(wv_engine* const* engines, int32_t n, uint64_t n_steps, uint64_
  * stencil's byte mix), mean of `iters` launches: the bandwidth yardstick of SURVEY.md 8(d). */
 int wv_measure_triad(int32_t device, uint64_t n_doubles, int32_t iters, double* gb_per_s);
 
+/* ---- transparent sources ------------------------------------------------------------------------ */
+/* compressed_rectangular_waveguide::run_hard_source / run_soft_source
+ * (src/waveguide/compensation_signal/lib/include/compensation_signal/waveguide.h:42-131): a free-field mesh
+ * folded onto x >= y >= z >= 0 of dim = (steps + 1) / 2 shells (shell dim held at 0), stepped 2 * dim times
+ * on the device.  Per step k: node 0 of the current field is set to input[k] (WV_SOURCE_HARD) or has it added
+ * (WV_SOURCE_SOFT), 0 once the input is over; every node is updated; the fields swap; output[k] = node 0.
+ * Bit-identical to the reference's float arithmetic.  `device` as wv_options::device (-1 = current).
+ * WV_E_INVALID_ARGUMENT when the two fields (4 * tetrahedron(dim + 1) bytes each) do not fit in the device's
+ * free memory (and for steps > 65536); WV_E_NO_DEVICE without a GPU (no CPU fallback). */
+int wv_compressed_waveguide_run(int32_t device, uint64_t steps, int32_t source_kind, const float* input,
+                                uint64_t n_input, float* output /* [2 * ((steps + 1) / 2)] */);
+/* waveguide::make_transparent (src/waveguide/src/make_transparent.cpp:10-30), host only: the response under
+ * core::right_hanning(taps) (float, as core/sinc.h:59-72 makes it), convolved with the input (accumulated in
+ * double), subtracted from the input: out[i] = (i < n ? input[i] : 0) - conv[i].  taps >= 2. */
+int wv_make_transparent(const float* input, uint64_t n, const float* response, uint32_t taps,
+                        float* out /* [n + taps - 1] */);
+
 /* ---- unit kernel of the boundary IIR step ------------------------------------------------------- */
 /* The reference's `filter_test_2` test kernel (src/waveguide/src/cl/filters.cpp:66-75, launched by
  * tests/rectangular_kernel.cpp:170-190): n_filters independent order-6 filters, each fed

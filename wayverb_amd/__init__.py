@@ -7,6 +7,7 @@
   wayfile     wayverb `.way` project bundles (config.json + model.model)
   filters     wall filter design (host C++ in the library)
   postprocess receiver traces -> audio
+  transparent transparent sources: the folded free-field mesh's response (GPU), make_transparent
   simulation  compute_voxels_and_mesh / canonical / impulse_response
   build       hipcc build of libwayverb_amd.so (gfx950)
 """
