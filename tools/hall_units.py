@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How the two-step march's units look on a real room (the concert hall at a given cutoff): per unit (a strip of 4 rows
-through a chunk of 32 planes) the span of live waves, as wayverb_amd/csrc/engine_pair.hip.h (build_pair_units) computes it.
+through a chunk of 32 planes) the span of live waves, as wayverb_amd/csrc/march_plan.h (plan_units) computes it.
     python tools/hall_units.py [cutoff_hz=1600]"""
 import os
 import sys

@@ -7,8 +7,11 @@
 //                        work lists for rooms that leave much of the mesh outside; release
 //   engine_single.hip.h  one time step per pass: sweep + boundary launches, source / receiver launch, the slab form
 //                        (faces first, exchange, interior), hipGraph replay for small meshes
-//   engine_pair.hip.h    two time steps per pass: eligibility, pair map + fix-up lists, march geometry, parts A / B
+//   engine_pair.hip.h    two time steps per pass: eligibility, pair map + fix-up lists, march geometry, parts A / B; the launch
+//                        sequences both kinds of pass share (source / receiver launch, boundary launch that carries one, wall copies)
 //   engine_triple.hip.h  three time steps per pass: eligibility, triple map + third-level list, march geometry, the pass
+//   march_plan.h         (host only, no HIP) MarchPlan and the planners of both marches: windows of a long row, chunks along z, the
+//                        work list of a sparse room, plan -> kernel arguments
 //   engine_batch.hip.h   wv_step / wv_run: batches of steps, flag words, kernel timing
 //   engine_io.hip.h      everything a caller reads or writes: values, fields, planes, filter memories, source,
 //                        receivers
@@ -16,6 +19,7 @@
 // There is no CPU path: without a HIP device every entry point fails.
 #pragma once
 #include "engine_base.h"
+#include "march_plan.h"
 
 #include "boundary_kernels.hip.h"
 #include "pair_kernels.hip.h"
@@ -73,7 +77,7 @@ public:
     // ---- engine_pair.hip.h
     bool pair_eligible();
     int ensure_pair();
-    int build_pair_units(int owned);
+    int build_pair_units();
     static void parallel_sort(std::vector<uint64_t>& v);
     int enqueue_pair_a(int slot, uint64_t signal_pos, bool source_live, bool fuse_mid);
     int launch_fixup(uint32_t first, uint32_t n, const Real* t1, const Real* cur, Real* out2, int* flag2);
@@ -157,6 +161,18 @@ public:
 
 private:
     void release();  // engine_setup.hip.h
+    // ---- engine_pair.hip.h: launch sequences the passes share
+    void launch_pre_post(const wv::PrePostArgs<Real>& pp);
+    void launch_pre_post(Real* field, int slot, uint64_t signal_pos, bool source_live, bool clear_flag, int* flag2 = nullptr, bool with_pre_post = true);
+    // who does the source / receiver work that goes with a boundary launch: nobody here, the launch's last workgroup, a launch behind it
+    enum class IoRide { none, carried, behind };
+    int launch_boundary_with_io(int part, Real* prev, const Real* cur, int* flag, int z0, int z1, Real* out, bool fix_inner, bool levels, int xw3,
+                                const wv::PrePostArgs<Real>& io, IoRide ride);
+    void carry_short_list(wv::PrePostArgs<Real>& io, const Real* cur, Real* out2, int* flag2) const;
+    void refresh_xwall_copies(Real* prev, const Real* cur, int* flag);
+    void rotate_after_pass();
+    int march_activity(int strips, int row_waves, int wave_cols, std::vector<uint8_t>* active, std::vector<uint16_t>* wave_bits);
+    int upload_units(const wv::MarchPlan& plan, uint32_t** dev, const char* what);
     // rooms that leave much of the mesh outside: visit live tiles / units only (wv_options::all_tiles, wv_tuning::tile_lists)
     bool use_work_lists() const { return !opt_.all_tiles && opt_.tuning.tile_lists != 0; }
 
@@ -207,16 +223,12 @@ private:
     uint8_t* pair_map_ = nullptr;
     uint32_t* pair_list_ = nullptr;
     uint32_t* pair_counter_ = nullptr;
-    uint32_t* pair_units_ = nullptr;               // march work list (build_pair_units), null = every unit
-    uint32_t pair_unit_start_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t pair_units_longest_ = 0;
+    wv::MarchPlan pair_plan_;                      // the two-step march: planes, geometry, windows, work list (ensure_pair, build_pair_units)
+    uint32_t* pair_units_ = nullptr;               // its work list on the device, null = every unit
     bool pair_sparse_ok_ = true;                   // sparse room: the march's live units cost less than the sweep's live tiles
     double tile_active_frac_ = 1.0;
-    double pair_live_frac_ = 1.0;                  // live waves of listed units / all waves of all units (build_pair_units)
     uint32_t pair_list_n_ = 0;  // fix-up nodes of the marched planes
-    int pair_z0_ = 0, pair_z1_ = 0;                // planes the march produces
     uint64_t pair_source_ = 0;
-    int pair_nw_ = 1, pair_strips_ = 0, pair_zc_ = 0, pair_chunks_ = 1;
     uint64_t timed_steps_ = 0;
     bool batch_can_fuse_ = false, batch_source_live_ = false;  // plan_batch's decisions for the batch being enqueued
     bool io_plain_known_ = false, io_plain_ = false;
@@ -230,8 +242,6 @@ private:
     uint64_t io_generation_ = 0;                      // bumped by set_source / set_receivers (GraphKey)
     bool pair_list_early_ok_ = false;             // ensure_pair
     bool pair_unit_waves_ = false;                // the unit list carries each unit's live waves (build_pair_units)
-    int pair_windows_ = 0;                        // WIDE march: workgroups side by side per row (0: one)
-    uint8_t pair_win_[4][wv::kPairMaxWindows] = {};  // first wave, waves, first storing wave, end of the storing waves
     bool pair_mid_done_ = false, pair_list_done_ = false;  // part A of the pass in flight has served t+1's source / receivers, the list
     int outside_dirty_ = 0;           // steps until the outside nodes are known to be 0 in both fields again
     uint32_t* ref_to_pos_ = nullptr;  // [n_entries] caller's (class offset + boundary_index) -> processing position
@@ -282,19 +292,16 @@ private:
     int* suspect_ = nullptr;           // [kRing] per step slot: the march saw an inf / nan
     uint64_t triple_source_ = 0, triple_io_generation_ = ~0ull;
     bool triple_failed_ = false, triple_ready_ = false, triple_attr_set_ = false;
-    uint32_t* triple_units_ = nullptr; // sparse rooms: the three-step march's work list (build_triple_units), XCD k's run at triple_unit_start_[k]
-    uint32_t triple_unit_start_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t triple_units_longest_ = 0;
-    double triple_live_frac_ = 1.0;    // live waves of listed units / all waves of all units
+    // the three-step march: its planes (the owned ones, less the face plane and the plane next to it where a neighbour follows), geometry,
+    // windows, work list (ensure_triple, build_triple_units)
+    wv::MarchPlan triple_plan_;
+    uint32_t* triple_units_ = nullptr; // its work list on the device
     bool triple_xw_ = false;           // the passes' three levels take the x-facing walls on their compact copies (and the third-level list leaves the nodes they face out)
     // stored nodes from which the engine takes three-step passes by itself (tools/pass_forms_by_size.py, profiles/r06/pass_forms_by_size_*.txt:
     // Gnode-updates/s two-step / three-step at the end of round 6, fp64: 224^3 187 / 200, 256^3 213 / 243, 320^3 214 / 255, 384^3 267 / 321,
     // 512^3 286 / 362, 768^3 326 / 416, 1024^3 338 / 443; fp32: 384^3 352 / 421, 512^3 487 / 587, 640^3 460 / 484, 768^3 557 / 590,
     // 896^3 536 / 649, 1024^3 626 / 765 -- wherever two-step passes run at all in fp64; in fp32 from the first size measured)
     uint64_t triple_min_nodes_ = sizeof(Real) == 8 ? (12ull << 20) : (24ull << 20);
-    int triple_z0_ = 0, triple_z1_ = 0;  // the planes the march produces: the owned ones, less the face plane and the plane next to it where a neighbour follows
-    int triple_nw_ = 1, triple_strips_ = 0, triple_zc_ = 0, triple_chunks_ = 1, triple_windows_ = 0;
-    uint8_t triple_win_[4][wv::kTripleMaxWindows] = {};
     int triple_lb_ = 8;                // bytes of a row per lane of the march as set up (triple_lane_bytes)
     // stored row length (elements) from which doubles march on 16-byte lanes (profiles/r06/lane_width_by_size.txt: Gnode-updates/s with
     // 8- / 16-byte lanes 256^3 234 / 226, 320^3 220 / 234, 384^3 281 / 309, 512^3 346 / 340, 768^3 360 / 378, 1024^3 343 / 403)

@@ -372,16 +372,16 @@ int Engine<Real>::query(int what, uint64_t* value) {
         }
         // (the march that runs: a sparse room's three-step passes have a work list of their own, narrower waves and all)
         case WV_QUERY_MARCH_LIVE_PERMILLE:
-            *value = (triple_units_ && triple_ready_) ? (uint64_t)(triple_live_frac_ * 1000.0 + 0.5) : pair_units_ ? (uint64_t)(pair_live_frac_ * 1000.0 + 0.5) : 1000;
+            *value = (triple_units_ && triple_ready_) ? (uint64_t)(triple_plan_.live_frac * 1000.0 + 0.5) : pair_units_ ? (uint64_t)(pair_plan_.live_frac * 1000.0 + 0.5) : 1000;
             return WV_OK;
         case WV_QUERY_MARCH_ROUNDS: {
-            if (!pair_map_ || pair_nw_ < 1) {
+            if (!pair_map_ || pair_plan_.nw < 1) {
                 *value = 0;
                 return WV_OK;
             }
-            const uint64_t slots = 256ull * (uint64_t)std::max(1, wv::kPairMaxWaves / pair_nw_);
-            const uint64_t wgs = pair_units_ ? 8ull * pair_units_longest_
-                                             : 8ull * (uint64_t)((pair_strips_ + 7) / 8) * (uint64_t)pair_chunks_ * (uint64_t)std::max(1, pair_windows_);
+            const uint64_t slots = 256ull * (uint64_t)std::max(1, wv::kPairMaxWaves / pair_plan_.nw);
+            wv::PairArgs<Real> a{};
+            const uint64_t wgs = wv::fill_march_args(a, pair_plan_, pair_units_);  // (the grid enqueue_pair_a launches)
             *value = (wgs + slots - 1) / slots;
             return WV_OK;
         }

@@ -81,10 +81,10 @@ int Engine<Real>::ensure_pair() {
     m.z_begin = z_begin_;
     m.z_end = z_end_;
     // a slab's face planes are not marched: their t+2 needs the neighbour's t+1 face (enqueue_pair)
-    pair_z0_ = z_begin_ + (opt_.ghost_lo ? 1 : 0);
-    pair_z1_ = z_end_ - (opt_.ghost_hi ? 1 : 0);
-    m.march_begin = pair_z0_;
-    m.march_end = pair_z1_;
+    pair_plan_.z0 = z_begin_ + (opt_.ghost_lo ? 1 : 0);
+    pair_plan_.z1 = z_end_ - (opt_.ghost_hi ? 1 : 0);
+    m.march_begin = pair_plan_.z0;
+    m.march_end = pair_plan_.z1;
     // ... and when the planes next to the faces are stepped to t+1 with them (slab_early_now), the march stores its t+1 values one
     // plane further in
     pair_s0_ = z_begin_ + (opt_.ghost_lo ? 2 : 0);
@@ -183,256 +183,143 @@ int Engine<Real>::ensure_pair() {
     }
     if (!xw_active_) xw_valid_ = false;  // passes that do not maintain the copies leave them behind
     // march geometry: strips of 4 rows, all planes unless there are too few strips to fill the chip
+    static_assert(wv::kPairMaxWindows == wv::kMarchMaxWindows, "PairArgs' window words hold MarchPlan's table");
     constexpr int WX = 64 * (16 / (int)sizeof(Real));
-    pair_nw_ = pitch_ / WX;
-    pair_windows_ = 0;
-    if (pair_nw_ > wv::kPairMaxWaves) {
+    wv::MarchPlan& p = pair_plan_;
+    p.nw = pitch_ / WX;
+    p.windows = 0;
+    if (p.nw > wv::kPairMaxWaves) {
         // windows of up to kPairMaxWaves waves, one halo wave on every interior side (pair_march_kernel<.., WIDE>)
-        const int row_waves = pair_nw_;
-        int at = 0, widest = 0;
-        while (at < row_waves && pair_windows_ < wv::kPairMaxWindows) {
-            const int lo_halo = at > 0 ? 1 : 0;
-            int end = at + wv::kPairMaxWaves - lo_halo;            // storing [at, end) with no halo above ...
-            if (end < row_waves) end -= 1;                          // ... or one wave less and a halo wave
-            end = std::min(end, row_waves);
-            const int first = at - lo_halo, count = end + (end < row_waves ? 1 : 0) - first;
-            pair_win_[0][pair_windows_] = (uint8_t)first;
-            pair_win_[1][pair_windows_] = (uint8_t)count;
-            pair_win_[2][pair_windows_] = (uint8_t)at;
-            pair_win_[3][pair_windows_] = (uint8_t)end;
-            widest = std::max(widest, count);
-            ++pair_windows_;
-            at = end;
-        }
-        if (at < row_waves) return fail(WV_E_STATE, "row too long for the two-step pass");  // (pair_eligible rules it out)
-        pair_nw_ = widest;  // waves per workgroup
-    } else if (opt_.tuning.pair_split_rows != 0 && pair_nw_ >= 3) {
+        p.windows = wv::split_row(pitch_ / WX, wv::kPairMaxWaves, p.win, &p.nw);  // (p.nw: waves per workgroup)
+        if (p.windows < 0) return fail(WV_E_STATE, "row too long for the two-step pass");  // (pair_eligible rules it out)
+    } else if (opt_.tuning.pair_split_rows != 0 && p.nw >= 3) {
         // Measurement (wv_tuning::pair_split_rows): a row of 3 .. 8 waves is one workgroup per CU where 8 wave slots are free, and
         // such marches run at 3.5 TB/s.  The same row as windows of at most 4 waves (halo waves included, as in
         // the WIDE march above) puts two workgroups on a CU -- for 40-57 % more waves run than stored.
-        const int row_waves = pair_nw_, cap = opt_.tuning.pair_split_rows > 1 ? opt_.tuning.pair_split_rows : 4;
-        int at = 0, widest = 0;
-        while (at < row_waves && pair_windows_ < wv::kPairMaxWindows) {
-            const int lo_halo = at > 0 ? 1 : 0;
-            int end = at + cap - lo_halo;
-            if (end < row_waves) end -= 1;
-            end = std::max(at + 1, std::min(end, row_waves));
-            const int first = at - lo_halo, count = end + (end < row_waves ? 1 : 0) - first;
-            pair_win_[0][pair_windows_] = (uint8_t)first;
-            pair_win_[1][pair_windows_] = (uint8_t)count;
-            pair_win_[2][pair_windows_] = (uint8_t)at;
-            pair_win_[3][pair_windows_] = (uint8_t)end;
-            widest = std::max(widest, count);
-            ++pair_windows_;
-            at = end;
-        }
-        if (at < row_waves) return fail(WV_E_STATE, "pair_split_rows: too many windows");
-        pair_nw_ = widest;
+        p.windows = wv::split_row(pitch_ / WX, opt_.tuning.pair_split_rows > 1 ? opt_.tuning.pair_split_rows : 4, p.win, &p.nw);
+        if (p.windows < 0) return fail(WV_E_STATE, "pair_split_rows: too many windows");
     }
-    pair_strips_ = (ny_ + wv::kPairRows - 1) / wv::kPairRows;
-    const int owned = pair_z1_ - pair_z0_;
-    // Workgroups the chip holds at once: 256 CUs x (8 wave slots at 2 waves / SIMD) / waves per
-    // workgroup.  Chunks along z are chosen so that the workgroups fill whole rounds of that, weighed
-    // against the three planes every chunk recomputes or loads before its first output plane.
-    const int64_t slots = 256ll * std::max(1, wv::kPairMaxWaves / pair_nw_);
-    int chunks = opt_.tuning.pair_chunks;
-    if (chunks <= 0) {
-        // A slab with a neighbour: the exchange of its t+1 faces is to run under the march, and whatever carries it (RCCL's
-        // send / receive kernels, the runtime's copy kernels) needs a CU -- a march of ONE round holds every register of every
-        // CU until all its workgroups retire together at the end, and the exchange would start after it.  At least two rounds
-        // then: the first round's end is where the exchange gets in.
-        // (... where that costs little: a mesh that fills two rounds only with much shorter chunks keeps the unconstrained choice)
-        // (slabs of one process that share this device take turns at the march -- SlabComm::bulk_begin -- and nothing runs beside
-        // it that the next slab's march would not displace anyway: one round there)
-        const int64_t want_rounds = ((opt_.ghost_lo || opt_.ghost_hi) && (!comm_ || comm_->peers_elsewhere())) ? 2 : 1;
-        double best[2] = {0, 0};
-        int at[2] = {0, 0};  // [0] any number of rounds, [1] at least `want_rounds`
-        for (int c = 1; c <= std::max(1, owned / 8) && c <= 256; ++c) {
-            const int64_t wgs = (int64_t)pair_strips_ * c;
-            const int64_t rounds = (wgs + slots - 1) / slots;
-            const double zc = (double)((owned + c - 1) / c);
-            const double cost = (double)(rounds * slots) / (double)wgs * (zc + 3.0) / zc;
-            for (int k = 0; k < 2; ++k)
-                if ((k == 0 || rounds >= want_rounds) && (at[k] == 0 || cost < best[k] - 1e-9)) {
-                    best[k] = cost;
-                    at[k] = c;
-                }
-        }
-        chunks = (at[1] && best[1] <= 1.06 * best[0]) ? at[1] : at[0];
-    }
-    chunks = std::max(1, std::min(chunks, std::max(1, owned / 8)));
-    pair_zc_ = (owned + chunks - 1) / chunks;
-    pair_chunks_ = (owned + pair_zc_ - 1) / pair_zc_;
-    return build_pair_units(owned);
+    p.strips = (ny_ + wv::kPairRows - 1) / wv::kPairRows;
+    // Workgroups the chip holds at once: 256 CUs x (8 wave slots at 2 waves / SIMD) / waves per workgroup; three planes every chunk
+    // recomputes or loads before its first output plane (choose_chunks).
+    // Two rounds are wanted of a slab with a neighbour -- but slabs of one process that share this device take turns at the march
+    // (SlabComm::bulk_begin), and nothing runs beside it that the next slab's march would not displace anyway: one round there.
+    const int64_t want_rounds = ((opt_.ghost_lo || opt_.ghost_hi) && (!comm_ || comm_->peers_elsewhere())) ? 2 : 1;
+    wv::choose_chunks(p, p.strips, 256ll * std::max(1, wv::kPairMaxWaves / p.nw), 3, 8, 8, want_rounds, opt_.tuning.pair_chunks);
+    return build_pair_units();
 }
 
-// Rooms that leave much of the mesh outside: a unit of the march (a strip of 4 rows through one chunk
-// of planes) without a single node to update produces nothing but the zeros its outputs already hold,
-// so only the other units are launched -- each XCD a run of neighbouring strips with about the same
-// number of units.  (A mesh that is nearly all room keeps the arithmetic mapping.)
+// Rooms that leave much of the mesh outside: only the units of the march (a strip of 4 rows through one chunk of planes) that hold a
+// node to update are launched (plan_units, march_plan.h).  (A mesh that is nearly all room keeps the arithmetic mapping.)
 template <typename Real>
-int Engine<Real>::build_pair_units(int owned) {
+int Engine<Real>::build_pair_units() {
+    wv::MarchPlan& p = pair_plan_;
     if (pair_units_) {
         (void)hipFree(pair_units_);
         pair_units_ = nullptr;
     }
+    p.units.clear();
     pair_sparse_ok_ = true;
-    if (!use_work_lists() || pair_strips_ >= (1 << 16) || pair_windows_) return WV_OK;
-    // activity per (plane, strip)
-    const int64_t n_cells = (int64_t)nz_ * pair_strips_;
-    ScopedDevice act_mem;
-    WV_HIP(hipMalloc(&act_mem.p, (size_t)n_cells));
-    wv::TileActivityArgs t{};
-    t.cls = cls_;
-    t.active = static_cast<uint8_t*>(act_mem.p);
-    t.ny = ny_;
-    t.nz = nz_;
-    t.pitch = pitch_;
-    t.cls_pitch = cls_pitch_;
-    t.tile_rows = wv::kPairRows;
-    t.tile_cols = pitch_;
-    t.tiles_x = 1;
-    t.tiles_y = pair_strips_;
-    hipLaunchKernelGGL(wv::tile_activity_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, stream_, t);
-    WV_HIP(hipGetLastError());
-    std::vector<uint8_t> active((size_t)n_cells);
-    WV_HIP(hipMemcpyAsync(active.data(), act_mem.p, (size_t)n_cells, hipMemcpyDeviceToHost, stream_));
-    WV_HIP(hipStreamSynchronize(stream_));
+    // (too many strips for an entry's bits: plan_units says so, after the activity has been gathered -- more than 262 000 rows, a limit
+    // stated once)
+    if (!use_work_lists() || p.windows) return WV_OK;
+    // activity per (plane, strip); the live waves of each where the list is to carry them
+    const int owned = p.z1 - p.z0;
+    const bool spans = opt_.tuning.pair_unit_waves != 0 && p.nw > 1;
+    std::vector<uint8_t> active;
+    std::vector<uint16_t> wave_bits;
+    int rc = march_activity(p.strips, p.nw, 64 * (16 / (int)sizeof(Real)), &active, nullptr);
+    if (rc) return rc;
     uint64_t live = 0;
-    for (int z = pair_z0_; z < pair_z1_; ++z)
-        for (int sidx = 0; sidx < pair_strips_; ++sidx) live += active[(size_t)z * pair_strips_ + sidx];
-    if (live * 100 >= (uint64_t)owned * pair_strips_ * 92) return WV_OK;  // (nearly) all room
-    // finer chunks than a full mesh would take: skipping works in whole units.  How many planes to a unit?  About
-    // pair_unit_planes (32), and among the heights near it the one whose units fill the chip's workgroup slots in the
-    // fewest, fullest rounds: an XCD runs 32 x (8 / waves per workgroup) of its units at a time, a round of them takes
-    // (height + 3 prologue planes), and a last round with two units in it costs as much as a full one -- the concert
-    // hall at 1 600 Hz made 1 538 units of 32 planes for 256 slots: six rounds and one nearly empty.
-    const int64_t slots_per_xcd = 32ll * std::max(1, wv::kPairMaxWaves / pair_nw_);
-    auto rounds_cost = [&](int height) -> double {
-        const int n_chunks = (owned + height - 1) / height;
-        std::vector<uint32_t> per_strip((size_t)pair_strips_, 0u);
-        uint64_t units = 0;
-        for (int sidx = 0; sidx < pair_strips_; ++sidx)
-            for (int c = 0; c < n_chunks; ++c) {
-                const int zb = pair_z0_ + c * height, ze = std::min(zb + height, pair_z1_);
-                bool any = false;
-                for (int z = zb; z < ze && !any; ++z) any = active[(size_t)z * pair_strips_ + sidx] != 0;
-                per_strip[(size_t)sidx] += any;
-                units += any;
-            }
-        if (!units) return 0.0;
-        uint64_t longest = 0, so_far = 0, start = 0;  // the same partition into eight runs of strips as below
-        int sidx = 0;
-        for (int k = 0; k < 8; ++k) {
-            const uint64_t want = units * (uint64_t)(k + 1) / 8;
-            while (sidx < pair_strips_ && (so_far < want || k == 7)) so_far += per_strip[(size_t)sidx++];
-            longest = std::max(longest, so_far - start);
-            start = so_far;
-        }
-        return (double)((longest + slots_per_xcd - 1) / slots_per_xcd) * (double)(height + 3);
-    };
-    int zc = std::max(8, std::min(pair_zc_, opt_.tuning.pair_unit_planes));
-    if (zc == opt_.tuning.pair_unit_planes && opt_.tuning.pair_units_by_chunk != 0) {
-        double best = rounds_cost(zc);
-        for (int height = zc * 3 / 4; height <= zc * 5 / 4; ++height) {
-            if (height < 8 || height > owned || (owned + height - 1) / height >= (1 << 9)) continue;
-            const double cost = rounds_cost(height);
-            if (cost > 0 && cost < best * 0.97) {  // (only a clear win moves the height)
-                best = cost;
-                zc = height;
-            }
-        }
-    }
-    const int chunks = (owned + zc - 1) / zc;
-    if (chunks >= (1 << 9)) return WV_OK;  // (9 bits of a list entry)
-    // Which waves of a row does a unit need?  Those between the first and the last column block that holds anything
-    // but `none` nodes in the unit's rows +- a strip and planes +- 2 (all it reads, produces or hands on): beyond
-    // them every field is zero, which is what a missing neighbour counts as (pair_march_kernel, unit lists).
-    std::vector<uint8_t> raw;
-    pair_unit_waves_ = false;
-    if (opt_.tuning.pair_unit_waves != 0 && pair_nw_ > 1) {
-        ScopedDevice raw_mem;
-        WV_HIP(hipMalloc(&raw_mem.p, (size_t)n_cells));
-        wv::WaveActivityArgs w{};
-        w.cls = cls_;
-        w.raw = static_cast<uint8_t*>(raw_mem.p);
-        w.ny = ny_;
-        w.nz = nz_;
-        w.pitch = pitch_;
-        w.cls_pitch = cls_pitch_;
-        w.strips = pair_strips_;
-        w.nw = pair_nw_;
-        w.wave_cols = 64 * (16 / (int)sizeof(Real));
-        hipLaunchKernelGGL(wv::pair_wave_activity_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, stream_, w);
-        WV_HIP(hipGetLastError());
-        raw.resize((size_t)n_cells);
-        WV_HIP(hipMemcpyAsync(raw.data(), raw_mem.p, (size_t)n_cells, hipMemcpyDeviceToHost, stream_));
-        WV_HIP(hipStreamSynchronize(stream_));
-        pair_unit_waves_ = true;
-    }
-    std::vector<std::vector<uint32_t>> of_strip((size_t)pair_strips_);
-    uint64_t total = 0, live_waves = 0;
-    for (int sidx = 0; sidx < pair_strips_; ++sidx)
-        for (int c = 0; c < chunks; ++c) {
-            bool any = false;
-            const int zb = pair_z0_ + c * zc, ze = std::min(pair_z0_ + (c + 1) * zc, pair_z1_);
-            for (int z = zb; z < ze && !any; ++z) any = active[(size_t)z * pair_strips_ + sidx] != 0;
-            if (!any) continue;
-            uint32_t entry = (uint32_t)sidx | ((uint32_t)c << 16), span = (uint32_t)pair_nw_;
-            if (pair_unit_waves_) {
-                uint32_t bits = 0;
-                for (int z = std::max(0, zb - 2); z < std::min(nz_, ze + 2); ++z)
-                    for (int ss = std::max(0, sidx - 1); ss <= std::min(pair_strips_ - 1, sidx + 1); ++ss)
-                        bits |= raw[(size_t)z * pair_strips_ + ss];
-                const uint32_t lo = (uint32_t)__builtin_ctz(bits | (1u << 31)), hi = 32u - (uint32_t)__builtin_clz(bits | 1u);
-                span = hi > lo ? hi - lo : 1u;
-                entry |= (std::min(lo, (uint32_t)pair_nw_ - 1) << 25) | ((span - 1) << 28);
-            }
-            of_strip[(size_t)sidx].push_back(entry);
-            live_waves += span;
-            ++total;
-        }
-    if (!total) return WV_OK;
+    for (int z = p.z0; z < p.z1; ++z)
+        for (int sidx = 0; sidx < p.strips; ++sidx) live += active[(size_t)z * p.strips + sidx];
+    if (live * 100 >= (uint64_t)owned * p.strips * 92) return WV_OK;  // (nearly) all room
+    if (spans && (rc = march_activity(p.strips, p.nw, 64 * (16 / (int)sizeof(Real)), nullptr, &wave_bits))) return rc;
+    // finer chunks than a full mesh would take: skipping works in whole units.  About pair_unit_planes (32) to a unit, or the best height
+    // near that -- where the full mesh's chunks are not shorter still, and the list is in the order the search reckons with
+    wv::UnitRules r{};
+    r.nz = nz_;
+    r.row_waves = p.nw;
+    r.warmup = 3;
+    r.halo = 2;
+    r.slots_per_xcd = 32ll * std::max(1, wv::kPairMaxWaves / p.nw);
+    r.start_height = std::max(8, std::min(p.zc, opt_.tuning.pair_unit_planes));
+    r.search = r.start_height == opt_.tuning.pair_unit_planes && opt_.tuning.pair_units_by_chunk != 0;
+    r.search_in_limit = true;
+    r.search_follows = true;
+    r.chunk_shift = 16;  // (PairArgs::unit_list)
+    r.first_shift = 25;
+    r.span_shift = 28;
+    r.spans = spans;
+    r.by_chunk = opt_.tuning.pair_units_by_chunk != 0;
+    if (!wv::plan_units(p, r, active.data(), wave_bits.data())) return WV_OK;
+    pair_unit_waves_ = spans;
     // Is the march still the better deal here?  It visits whole rows (strip x chunk units) and moves 32 B per
     // node for two steps; the sweep visits 128 x 16 x 1 tiles and moves 48 B.  Sphere inscribed in 768^3: 80 % of
     // the units against 55 % of the tiles are live, and the two run level (1.59-1.73 vs 1.63 ms per step).
     (void)build_tile_lists(z_begin_, z_end_);
     // (with the live waves of a unit only, what the march moves goes by waves, not by units)
-    const double unit_frac = (double)live_waves / ((double)pair_strips_ * chunks * pair_nw_);
-    pair_sparse_ok_ = unit_frac * 32.0 * 1.15 < tile_active_frac_ * 48.0;
-    pair_live_frac_ = unit_frac;
-    std::vector<uint32_t> list;
-    list.reserve((size_t)total);
-    pair_units_longest_ = 0;
-    int sidx = 0;
-    for (int k = 0; k < 8; ++k) {
-        pair_unit_start_[k] = (uint32_t)list.size();
-        const uint64_t want = total * (uint64_t)(k + 1) / 8;  // cumulative share of XCDs 0 .. k
-        const size_t first = list.size();
-        while (sidx < pair_strips_ && (list.size() < want || k == 7)) {
-            list.insert(list.end(), of_strip[(size_t)sidx].begin(), of_strip[(size_t)sidx].end());
-            ++sidx;
-        }
-        // An XCD takes its units chunk by chunk, the strips of a chunk side by side -- as the arithmetic mapping of a
-        // full mesh does -- so that the workgroups it runs at one time are NEIGHBOURING strips at the same planes and
-        // the ring rows two of them both load meet in its L2.  (Until round 3 the order was strip by strip: the 32
-        // workgroups of an XCD were 29 chunks of one strip and shared nothing; every ring row came from HBM -- the
-        // concert hall's march ran at 3.3 TB/s where a box's runs at 5.85.)
-        if (opt_.tuning.pair_units_by_chunk != 0)
-            std::stable_sort(list.begin() + (std::ptrdiff_t)first, list.end(),
-                             [](uint32_t a, uint32_t b) { return ((a >> 16) & 0x1FFu) < ((b >> 16) & 0x1FFu); });
-        pair_units_longest_ = std::max<uint32_t>(pair_units_longest_, (uint32_t)list.size() - pair_unit_start_[k]);
+    pair_sparse_ok_ = p.live_frac * 32.0 * 1.15 < tile_active_frac_ * 48.0;
+    return upload_units(p, &pair_units_, "copying the march's unit list to the device failed");
+}
+
+// What plan_units goes by: per (plane, strip of four rows) of the whole mesh, `active` -- a node to update -- and / or `wave_bits` -- which
+// of the row's `row_waves` waves of `wave_cols` columns hold anything but `none` nodes.
+template <typename Real>
+int Engine<Real>::march_activity(int strips, int row_waves, int wave_cols, std::vector<uint8_t>* active, std::vector<uint16_t>* wave_bits) {
+    static_assert(wv::kTripleRows == wv::kPairRows, "pair_wave_activity_kernel counts strips of kPairRows rows");
+    const int64_t n_cells = (int64_t)nz_ * strips;
+    const unsigned grid = (unsigned)((n_cells + 255) / 256);
+    ScopedDevice act_mem, bits_mem;
+    if (active) {
+        WV_HIP(hipMalloc(&act_mem.p, (size_t)n_cells));
+        wv::TileActivityArgs t{};
+        t.cls = cls_;
+        t.active = static_cast<uint8_t*>(act_mem.p);
+        t.ny = ny_;
+        t.nz = nz_;
+        t.pitch = pitch_;
+        t.cls_pitch = cls_pitch_;
+        t.tile_rows = wv::kPairRows;
+        t.tile_cols = pitch_;
+        t.tiles_x = 1;
+        t.tiles_y = strips;
+        hipLaunchKernelGGL(wv::tile_activity_kernel, dim3(grid), dim3(256), 0, stream_, t);
+        WV_HIP(hipGetLastError());
+        active->resize((size_t)n_cells);
+        WV_HIP(hipMemcpyAsync(active->data(), act_mem.p, (size_t)n_cells, hipMemcpyDeviceToHost, stream_));
     }
-    pair_unit_start_[8] = (uint32_t)list.size();
-    pair_zc_ = zc;
-    pair_chunks_ = chunks;
+    if (wave_bits) {
+        WV_HIP(hipMalloc(&bits_mem.p, (size_t)n_cells * sizeof(uint16_t)));
+        wv::WaveActivityArgs w{};
+        w.cls = cls_;
+        w.raw16 = static_cast<uint16_t*>(bits_mem.p);
+        w.ny = ny_;
+        w.nz = nz_;
+        w.pitch = pitch_;
+        w.cls_pitch = cls_pitch_;
+        w.strips = strips;
+        w.nw = row_waves;
+        w.wave_cols = wave_cols;
+        hipLaunchKernelGGL(wv::pair_wave_activity_kernel, dim3(grid), dim3(256), 0, stream_, w);
+        WV_HIP(hipGetLastError());
+        wave_bits->resize((size_t)n_cells);
+        WV_HIP(hipMemcpyAsync(wave_bits->data(), bits_mem.p, (size_t)n_cells * sizeof(uint16_t), hipMemcpyDeviceToHost, stream_));
+    }
+    WV_HIP(hipStreamSynchronize(stream_));
+    return WV_OK;
+}
+
+// A plan's unit list to the device, staged: a list that did not arrive whole is never launched with.
+template <typename Real>
+int Engine<Real>::upload_units(const wv::MarchPlan& plan, uint32_t** dev, const char* what) {
     uint32_t* staged = nullptr;
-    WV_HIP(hipMalloc((void**)&staged, list.size() * sizeof(uint32_t)));
-    if (hipMemcpy(staged, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    WV_HIP(hipMalloc((void**)&staged, plan.units.size() * sizeof(uint32_t)));
+    if (hipMemcpy(staged, plan.units.data(), plan.units.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(staged);
-        return fail(WV_E_HIP, "copying the march's unit list to the device failed");
+        return fail(WV_E_HIP, what);
     }
-    pair_units_ = staged;
+    *dev = staged;
     return WV_OK;
 }
 
@@ -561,9 +448,7 @@ int Engine<Real>::enqueue_pair_a(int slot, uint64_t signal_pos, bool source_live
         if ((rc = end_halo_wait_timing(token))) return rc;
     }
     if (!pre_post_done_ && !(batch_flags_reset_ && !n_recv_ && !source_live)) {  // step t: flag words of both steps, source sample into t, receivers from t
-        wv::PrePostArgs<Real> pp = pre_post_args(B, slot, true, signal_pos, source_live);
-        pp.flag2 = flag2;
-        hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, pp);
+        launch_pre_post(B, slot, signal_pos, source_live, true, flag2);
     }
     pre_post_done_ = false;  // (else: the boundary launch before this pass has done it)
     if (comm_) {
@@ -583,41 +468,21 @@ int Engine<Real>::enqueue_pair_a(int slot, uint64_t signal_pos, bool source_live
     a.nz = nz_;
     a.pitch = pitch_;
     a.cls_pitch = cls_pitch_;
-    a.z_begin = pair_z0_;
-    a.z_end = pair_z1_;
-    a.out1_z0 = early ? pair_s0_ : pair_z0_;
-    a.out1_z1 = early ? pair_s1_ : pair_z1_;
-    a.nw = pair_nw_;
-    a.zc = pair_zc_;
-    a.chunks = pair_chunks_;
-    a.strips = pair_strips_;
-    a.strips_per_xcd = (pair_strips_ + 7) / 8;
-    unsigned grid = 8u * (unsigned)a.strips_per_xcd * (unsigned)pair_chunks_;
-    if (pair_units_) {
-        a.unit_list = pair_units_;
-        for (int k = 0; k < 9; ++k) a.list_start[k] = pair_unit_start_[k];
-        grid = 8u * pair_units_longest_;
-    }
+    a.z_begin = pair_plan_.z0;
+    a.z_end = pair_plan_.z1;
+    a.out1_z0 = early ? pair_s0_ : pair_plan_.z0;
+    a.out1_z1 = early ? pair_s1_ : pair_plan_.z1;
+    const unsigned grid = wv::fill_march_args(a, pair_plan_, pair_units_);
+    const dim3 block(64u * (unsigned)pair_plan_.nw);
     if (comm_ && !comm_->bulk_begin(stream_, &cerr)) return fail(WV_E_COMM, cerr);  // (slabs of one device take turns at the march)
     const bool timed = time_this_launch();
     if (timed) WV_HIP(hipEventRecord(events_[ev_used_], stream_));
     // (a variant with the row length as a compile-time constant, NWC, was worth 6 % until the divide sequence went
     // (div3); at the memory ceiling it runs level with this one: tools/pair_tune.hip still prices it)
-    if (pair_units_ && pair_unit_waves_) {  // rooms narrower than their rows: the live waves of each unit only
-        hipLaunchKernelGGL((wv::pair_march_kernel<Real, 0, 0, true>), dim3(grid), dim3(64u * (unsigned)pair_nw_), 0, stream_, a);
-    } else if (pair_windows_) {
-        a.windows = pair_windows_;
-        for (int k = 0; k < pair_windows_; ++k) {
-            a.win_first |= (uint64_t)pair_win_[0][k] << (8 * k);
-            a.win_count |= (uint64_t)pair_win_[1][k] << (8 * k);
-            a.win_store_lo |= (uint64_t)pair_win_[2][k] << (8 * k);
-            a.win_store_hi |= (uint64_t)pair_win_[3][k] << (8 * k);
-        }
-        hipLaunchKernelGGL((wv::pair_march_kernel<Real, 0, 0, true>), dim3(grid * (unsigned)pair_windows_),
-                           dim3(64u * (unsigned)pair_nw_), 0, stream_, a);
-    } else {
-        hipLaunchKernelGGL((wv::pair_march_kernel<Real, 0, 0>), dim3(grid), dim3(64u * (unsigned)pair_nw_), 0, stream_, a);
-    }
+    if ((pair_units_ && pair_unit_waves_) || pair_plan_.windows)  // rooms narrower than their rows: the live waves of each unit only; windows
+        hipLaunchKernelGGL((wv::pair_march_kernel<Real, 0, 0, true>), dim3(grid), block, 0, stream_, a);
+    else
+        hipLaunchKernelGGL((wv::pair_march_kernel<Real, 0, 0>), dim3(grid), block, 0, stream_, a);
     if (timed) {
         WV_HIP(hipEventRecord(events_[ev_used_ + 1], stream_));
         ev_used_ += 2;
@@ -630,40 +495,88 @@ int Engine<Real>::enqueue_pair_a(int slot, uint64_t signal_pos, bool source_live
     // boundary nodes, t+1: own old value from t-1, neighbours from t, result into the t+1 field
     pair_mid_done_ = pair_list_done_ = false;
     if (xw_active_ && !xw_valid_) {  // the x-facing walls' compact copies, from fields t-1 and t
-        wv::BoundaryArgs<Real> g = boundary_args(A, B, flag1);
-        xwall_args(g);
-        hipLaunchKernelGGL(wv::xwall_gather_kernel<Real>, dim3(g.xw_pad / 256), dim3(256), 0, stream_, g);
+        refresh_xwall_copies(A, B, flag1);
         xw_valid_ = true;
     }
-    if (fuse_mid && n_entries_ && (n_recv_ || source_live)) {
-        // ... and, by its last workgroup, step t+1's source sample / receivers (none of those nodes is a
-        // boundary node: they have been final since the march) and then the few listed nodes
-        wv::PrePostArgs<Real> nx = pre_post_args(O1, slot + 1, true, signal_pos + 1, source_live);
-        nx.flag = nullptr;  // reset with step t's, and already written to by the march
-        if (pair_list_early_ok_ && pair_list_n_) {
-            nx.fix_nodes = pair_list_;
-            nx.fix_n = pair_list_n_;
-            nx.fix_cur = B;
-            nx.fix_out2 = O2;
-            nx.fix_flag = flag2;
-            nx.nx = nx_;
-            nx.ny = ny_;
-            nx.nz = nz_;
-            nx.pitch = pitch_;
-            pair_list_done_ = true;
-        }
-        const int token = begin_part_timing(0);
-        if ((rc = launch_boundary(A, B, flag1, pair_z0_, pair_z1_, &nx, O1, false, true))) return rc;
-        if ((rc = end_part_timing(0, token))) return rc;
-        pair_mid_done_ = true;
-    } else {
-        const int token = begin_part_timing(0);
-        // (early: the planes next to the faces have been to t+1 already)
-        if ((rc = launch_boundary(A, B, flag1, early ? pair_s0_ : pair_z0_, early ? pair_s1_ : pair_z1_, nullptr, O1, false, true))) return rc;
-        if ((rc = end_part_timing(0, token))) return rc;
+    // ... and, by its last workgroup, step t+1's source sample / receivers (none of those nodes is a
+    // boundary node: they have been final since the march) and then the few listed nodes
+    const bool carry = fuse_mid && n_entries_ && (n_recv_ || source_live);
+    wv::PrePostArgs<Real> nx = pre_post_args(O1, slot + 1, true, signal_pos + 1, source_live);
+    nx.flag = nullptr;  // reset with step t's, and already written to by the march
+    if (carry && pair_list_early_ok_ && pair_list_n_) {
+        carry_short_list(nx, B, O2, flag2);
+        pair_list_done_ = true;
     }
+    // (not carried, early: the planes next to the faces have been to t+1 already; step t+1's source / receiver work is part B's)
+    const bool inner = !carry && early;
+    if ((rc = launch_boundary_with_io(0, A, B, flag1, inner ? pair_s0_ : pair_plan_.z0, inner ? pair_s1_ : pair_plan_.z1, O1, false, true, 0, nx,
+                                      carry ? IoRide::carried : IoRide::none))) return rc;
+    pair_mid_done_ = carry;
     WV_HIP(hipGetLastError());
     return WV_OK;
+}
+
+// ---- launch sequences the two- and three-step passes share ------------------------------------------------------------------------
+// The source / receiver launch of a step: the sample into `field`, receivers from it.  `clear_flag`: the step's flag word is reset here
+// (not where the batch's flag words were reset in one go, or the march has written to it already); `flag2`: ... and the next step's, at
+// the head of a two-step pass.
+template <typename Real>
+void Engine<Real>::launch_pre_post(Real* field, int slot, uint64_t signal_pos, bool source_live, bool clear_flag, int* flag2, bool with_pre_post) {
+    wv::PrePostArgs<Real> pp = pre_post_args(field, slot, with_pre_post, signal_pos, source_live);
+    if (!clear_flag) pp.flag = nullptr;
+    pp.flag2 = flag2;
+    launch_pre_post(pp);
+}
+
+template <typename Real>
+void Engine<Real>::launch_pre_post(const wv::PrePostArgs<Real>& pp) {
+    hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, pp);
+}
+
+// A pass's boundary launch of one level, timed as `part`, and the source / receiver work `io` of the step its result is: carried -- the
+// launch's last workgroup does it (the caller has seen to it that the launch writes none of the nodes concerned) --, in a launch of its own
+// behind it, or none of this call's business (`io` is not read then).
+template <typename Real>
+int Engine<Real>::launch_boundary_with_io(int part, Real* prev, const Real* cur, int* flag, int z0, int z1, Real* out, bool fix_inner, bool levels,
+                                          int xw3, const wv::PrePostArgs<Real>& io, IoRide ride) {
+    int rc;
+    const int token = begin_part_timing(part);
+    if ((rc = launch_boundary(prev, cur, flag, z0, z1, ride == IoRide::carried ? &io : nullptr, out, fix_inner, levels, nullptr, xw3))) return rc;
+    if (ride == IoRide::behind) launch_pre_post(io);
+    return end_part_timing(part, token);
+}
+
+// ... with the second level's fix-up list behind it, where that is short and none of its nodes has a boundary node for a neighbour
+// (pair_list_early_ok_: the source's neighbours, typically)
+template <typename Real>
+void Engine<Real>::carry_short_list(wv::PrePostArgs<Real>& io, const Real* cur, Real* out2, int* flag2) const {
+    io.fix_nodes = pair_list_;
+    io.fix_n = pair_list_n_;
+    io.fix_cur = cur;
+    io.fix_out2 = out2;
+    io.fix_flag = flag2;
+    io.nx = nx_;
+    io.ny = ny_;
+    io.nz = nz_;
+    io.pitch = pitch_;
+}
+
+// The x-facing walls' compact copies, gathered from fields (prev, cur) = (t-1, t).
+template <typename Real>
+void Engine<Real>::refresh_xwall_copies(Real* prev, const Real* cur, int* flag) {
+    wv::BoundaryArgs<Real> g = boundary_args(prev, cur, flag);
+    xwall_args(g);
+    hipLaunchKernelGGL(wv::xwall_gather_kernel<Real>, dim3(g.xw_pad / 256), dim3(256), 0, stream_, g);
+}
+
+// Roles after a pass: (previous, current) = the last two levels it produced; the fields that held t-1 and t are the spares now.
+template <typename Real>
+void Engine<Real>::rotate_after_pass() {
+    const int a_idx = prv_, b_idx = cur_;
+    prv_ = spare_[0];
+    cur_ = spare_[1];
+    spare_[0] = a_idx;
+    spare_[1] = b_idx;
 }
 
 template <typename Real>
@@ -718,11 +631,7 @@ int Engine<Real>::enqueue_pair_b(int slot, uint64_t signal_pos, bool source_live
         if (!comm_->wait_ghosts(stream_, spare_[0], &cerr)) return fail(WV_E_COMM, cerr);  // ghost planes of t+1
         if ((rc = end_halo_wait_timing(token))) return rc;
     }
-    if (io_mid) {
-        wv::PrePostArgs<Real> pp = pre_post_args(O1, slot + 1, true, signal_pos + 1, source_live);
-        pp.flag = nullptr;  // reset in part A, and already written to by the march
-        hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, pp);
-    }
+    if (io_mid) launch_pre_post(O1, slot + 1, signal_pos + 1, source_live, false);  // (the flag word: reset in part A, and already written to by the march)
     if (comm_ && !pair_early_) {
         // the face planes to t+2: one more plain step of theirs, from the t+1 field with its ghost planes in place
         if ((rc = launch_faces(B, O1, flag2, O2))) return rc;
@@ -732,29 +641,20 @@ int Engine<Real>::enqueue_pair_b(int slot, uint64_t signal_pos, bool source_live
     // t+2 of the nodes next to a boundary node / the source, from the complete t+1; then the boundary nodes
     // (most of them are faced by a boundary node and finished by its entry in the launch after this one)
     if (!pair_list_done_ && (rc = launch_fixup(0, pair_list_n_, O1, B, O2, flag2))) return rc;
-    const int part_token = begin_part_timing(1);
-    if (fuse_next && n_entries_ && io_nodes_unfaced()) {
-        // what follows reads its source / receiver nodes from the t+2 field: none of them is written by
-        // this launch (no boundary node, no node an entry finishes)
-        wv::PrePostArgs<Real> nx = pre_post_args(O2, slot + 2, true, signal_pos + 2, source_live);
-        if (fuse_next == 2) nx.flag2 = flags_ + slot + 3;
-        if ((rc = launch_boundary(B, O1, flag2, pair_z0_, pair_z1_, &nx, O2, pair_inner_ok_ > 0, true))) return rc;
-        pre_post_done_ = true;
-    } else if ((rc = launch_boundary(B, O1, flag2, pair_z0_, pair_z1_, nullptr, O2, pair_inner_ok_ > 0, true))) {
-        return rc;
-    }
-    if ((rc = end_part_timing(1, part_token))) return rc;
+    // what follows reads its source / receiver nodes from the t+2 field: none of them is written by
+    // this launch (no boundary node, no node an entry finishes)
+    const bool carry = fuse_next && n_entries_ && io_nodes_unfaced();
+    wv::PrePostArgs<Real> nx = pre_post_args(O2, slot + 2, true, signal_pos + 2, source_live);
+    if (fuse_next == 2) nx.flag2 = flags_ + slot + 3;
+    if ((rc = launch_boundary_with_io(1, B, O1, flag2, pair_plan_.z0, pair_plan_.z1, O2, pair_inner_ok_ > 0, true, 0, nx,
+                                      carry ? IoRide::carried : IoRide::none))) return rc;  // (not carried: the next step's or pass's own launch)
+    if (carry) pre_post_done_ = true;
     pass_timed_ = false;
     WV_HIP(hipGetLastError());
     if (comm_ && !comm_->step_done(stream_, &cerr)) return fail(WV_E_COMM, cerr);
     ++passes_taken_;
     early_passes_ += pair_early_ ? 1 : 0;
-    // roles: (previous, current) = (t+1, t+2); the fields that held t-1 and t are the spares now
-    const int a_idx = prv_, b_idx = cur_;
-    prv_ = spare_[0];
-    cur_ = spare_[1];
-    spare_[0] = a_idx;
-    spare_[1] = b_idx;
+    rotate_after_pass();  // (previous, current) = (t+1, t+2)
     return WV_OK;
 }
 

@@ -403,8 +403,7 @@ int Engine<Real>::enqueue_step(int slot, bool with_pre_post, uint64_t signal_pos
     }
     // (the flag words of a batch are reset when it is planned: a slab without source or receivers has nothing to do here)
     if (!pre_post_done_ && !(batch_flags_reset_ && !n_recv_ && !(with_pre_post && source_live))) {
-        const wv::PrePostArgs<Real> pp = pre_post_args(cur, slot, with_pre_post, signal_pos, source_live);
-        hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, pp);
+        launch_pre_post(cur, slot, signal_pos, source_live, true, nullptr, with_pre_post);
     }
     pre_post_done_ = false;
     // Order on the one compute stream: a plane's sweep, then that plane's boundary nodes.

@@ -69,8 +69,8 @@ template <typename Real>
 int Engine<Real>::ensure_triple() {
     int rc = ensure_pair();
     if (rc) return rc;
-    triple_z0_ = z_begin_ + (opt_.ghost_lo ? 2 : 0);
-    triple_z1_ = z_end_ - (opt_.ghost_hi ? 2 : 0);
+    triple_plan_.z0 = z_begin_ + (opt_.ghost_lo ? 2 : 0);
+    triple_plan_.z1 = z_end_ - (opt_.ghost_hi ? 2 : 0);
     if (pair_failed_ || (!pair_sparse_ok_ && opt_.tuning.triple < 0)) {  // (a room so sparse that the sweep's tiles beat the march's units keeps single steps)
         triple_ready_ = false;
         return WV_OK;
@@ -117,8 +117,8 @@ int Engine<Real>::ensure_triple() {
     m.nz = nz_;
     m.pitch = pitch_;
     m.cls_pitch = cls_pitch_;
-    m.z_begin = triple_z0_;  // (the third level's list: the march's planes)
-    m.z_end = triple_z1_;
+    m.z_begin = triple_plan_.z0;  // (the third level's list: the march's planes)
+    m.z_end = triple_plan_.z1;
     ScopedDevice covered;  // the nodes those entries finish at the third level: not on its list
     if (xw) {
         const size_t words = (size_t)((stored_nodes_ + 31) / 32) + 1;
@@ -187,50 +187,30 @@ int Engine<Real>::ensure_triple() {
     triple_io_generation_ = io_generation_;
     // march geometry: strips of four rows; windows where a row is longer than a workgroup; chunks along z so that the workgroups fill
     // whole rounds of the chip's workgroup slots, weighed against the four warm-up planes every chunk marches before its first output
+    static_assert(wv::kTripleMaxWindows == wv::kMarchMaxWindows, "TripleArgs' window words hold MarchPlan's table");
+    wv::MarchPlan& p = triple_plan_;
     const int lb = triple_lb_ = triple_lane_bytes();
     const int WX = 64 * (lb / (int)sizeof(Real));
-    int widest = 0;
-    triple_windows_ = wv::triple_windows(pitch_ / WX, triple_win_, &widest, false, wv::triple_max_waves(lb));
-    if (triple_windows_ < 0) {
+    p.windows = wv::triple_windows(pitch_ / WX, p.win, &p.nw, false, wv::triple_max_waves(lb));
+    if (p.windows < 0) {
         triple_ready_ = false;
         return WV_OK;
     }
-    triple_nw_ = widest;
-    triple_strips_ = (ny_ + wv::kTripleRows - 1) / wv::kTripleRows;
-    const size_t lds = wv::triple_lds_bytes(triple_nw_, false, lb);
+    p.strips = (ny_ + wv::kTripleRows - 1) / wv::kTripleRows;
+    const size_t lds = wv::triple_lds_bytes(p.nw, false, lb);
     const int by_lds = std::max<int>(1, (int)((160u * 1024u) / lds));
-    const int by_waves = std::max(1, (lb == 16 ? 8 : 12) / triple_nw_);
-    const int64_t slots = 256ll * std::min(by_lds, by_waves);
-    const int owned = triple_z1_ - triple_z0_;
-    int chunks = opt_.tuning.triple_chunks;
-    if (chunks <= 0) {
-        // (a slab with a neighbour on another GPU: at least two rounds where that costs little, so that the exchange of the t+1 faces --
-        // enqueued ahead of the march, but in need of a CU where it is carried by kernels -- gets in at the first round's end instead
-        // of after the march: as ensure_pair chooses for the two-step march)
-        const int64_t want_rounds = ((opt_.ghost_lo || opt_.ghost_hi) && comm_ && comm_->peers_elsewhere()) ? 2 : 1;
-        double best[2] = {0, 0};
-        int at[2] = {0, 0};  // [0] any number of rounds, [1] at least `want_rounds`
-        for (int c = 1; c <= std::max(1, owned / 12) && c <= 256; ++c) {
-            const int64_t wgs = (int64_t)triple_strips_ * c * std::max(1, triple_windows_);
-            const int64_t rounds = (wgs + slots - 1) / slots;
-            const double zc = (double)((owned + c - 1) / c);
-            const double cost = (double)(rounds * slots) / (double)wgs * (zc + 4.0) / zc;
-            for (int k = 0; k < 2; ++k)
-                if ((k == 0 || rounds >= want_rounds) && (at[k] == 0 || cost < best[k] - 1e-9)) {
-                    best[k] = cost;
-                    at[k] = c;
-                }
-        }
-        chunks = (at[1] && best[1] <= 1.06 * best[0]) ? at[1] : std::max(1, at[0]);
-    }
-    chunks = std::max(1, std::min(chunks, std::max(1, owned / 4)));
-    triple_zc_ = (owned + chunks - 1) / chunks;
-    triple_chunks_ = (owned + triple_zc_ - 1) / triple_zc_;
+    const int by_waves = std::max(1, (lb == 16 ? 8 : 12) / p.nw);
+    // (a slab with a neighbour on another GPU: at least two rounds where that costs little, so that the exchange of the t+1 faces --
+    // enqueued ahead of the march, but in need of a CU where it is carried by kernels -- gets in at the first round's end instead
+    // of after the march: as ensure_pair chooses for the two-step march)
+    const int64_t want_rounds = ((opt_.ghost_lo || opt_.ghost_hi) && comm_ && comm_->peers_elsewhere()) ? 2 : 1;
+    wv::choose_chunks(p, (int64_t)p.strips * std::max(1, p.windows), 256ll * std::min(by_lds, by_waves), 4, 12, 4, want_rounds, opt_.tuning.triple_chunks);
     // a room that leaves much of its mesh outside (the two-step march runs over a work list): so does this one
     if (triple_units_) {
         (void)hipFree(triple_units_);
         triple_units_ = nullptr;
     }
+    p.units.clear();
     if (pair_units_ && (rc = build_triple_units())) return rc;
     if (pair_units_ && !triple_units_) {  // (no list to be had: two-step passes)
         triple_ready_ = false;
@@ -247,155 +227,46 @@ int Engine<Real>::ensure_triple() {
     return WV_OK;
 }
 
-// The three-step march's work list for a room that leaves much of its mesh outside, after build_pair_units (engine_pair.hip.h): a unit is a
-// strip of four rows through one chunk of planes, listed when it holds a node to update, with the waves of its row between the first and
-// the last that hold anything but `none` nodes in what it reads or hands on (its rows +- a strip, its planes +- 3).  Each XCD takes a
-// run of neighbouring strips with about the same number of units, chunk by chunk.  Sets triple_zc_ / triple_chunks_ to the units' height.
+// The three-step march's work list for a room that leaves much of its mesh outside, after build_pair_units (engine_pair.hip.h; plan_units,
+// march_plan.h): what a unit reads or hands on are its rows +- a strip and its planes +- 3.  Sets the plan's zc / chunks to the units' height.
 template <typename Real>
 int Engine<Real>::build_triple_units() {
-    // (a slab: the march's planes; a unit that ends at either end of them also stores t+2 on the plane beyond it -- TripleArgs::z2_lo /
-    // z2_hi --, so a node to update there makes the unit live as well)
-    const int owned = triple_z1_ - triple_z0_;
-    const int z_lo = triple_z0_, z_hi = triple_z1_, extra_lo = triple_z0_ > z_begin_ ? 1 : 0, extra_hi = triple_z1_ < z_end_ ? 1 : 0;
+    wv::MarchPlan& p = triple_plan_;
+    const int owned = p.z1 - p.z0;
     const int lb = triple_lb_;
     const int WX = 64 * (lb / (int)sizeof(Real));
-    const int row_waves = pitch_ / WX;
-    if (triple_windows_ || triple_strips_ >= (1 << 14) || row_waves > 16) return WV_OK;
-    const int64_t n_cells = (int64_t)nz_ * triple_strips_;
-    ScopedDevice act_mem, raw_mem;
-    WV_HIP(hipMalloc(&act_mem.p, (size_t)n_cells));
-    WV_HIP(hipMalloc(&raw_mem.p, (size_t)n_cells * sizeof(uint16_t)));
-    wv::TileActivityArgs t{};
-    t.cls = cls_;
-    t.active = static_cast<uint8_t*>(act_mem.p);
-    t.ny = ny_;
-    t.nz = nz_;
-    t.pitch = pitch_;
-    t.cls_pitch = cls_pitch_;
-    t.tile_rows = wv::kTripleRows;
-    t.tile_cols = pitch_;
-    t.tiles_x = 1;
-    t.tiles_y = triple_strips_;
-    hipLaunchKernelGGL(wv::tile_activity_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, stream_, t);
-    WV_HIP(hipGetLastError());
-    static_assert(wv::kTripleRows == wv::kPairRows, "pair_wave_activity_kernel counts strips of kPairRows rows");
-    wv::WaveActivityArgs w{};
-    w.cls = cls_;
-    w.raw16 = static_cast<uint16_t*>(raw_mem.p);
-    w.ny = ny_;
-    w.nz = nz_;
-    w.pitch = pitch_;
-    w.cls_pitch = cls_pitch_;
-    w.strips = triple_strips_;
-    w.nw = row_waves;
-    w.wave_cols = WX;
-    hipLaunchKernelGGL(wv::pair_wave_activity_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, stream_, w);
-    WV_HIP(hipGetLastError());
-    std::vector<uint8_t> active((size_t)n_cells);
-    std::vector<uint16_t> raw((size_t)n_cells);
-    WV_HIP(hipMemcpyAsync(active.data(), act_mem.p, (size_t)n_cells, hipMemcpyDeviceToHost, stream_));
-    WV_HIP(hipMemcpyAsync(raw.data(), raw_mem.p, (size_t)n_cells * sizeof(uint16_t), hipMemcpyDeviceToHost, stream_));
-    WV_HIP(hipStreamSynchronize(stream_));
+    if (p.windows) return WV_OK;  // (too many strips, rows wider than the masks: plan_units' to say, once the activity is gathered)
+    wv::UnitRules r{};
+    r.nz = nz_;
+    r.row_waves = pitch_ / WX;
+    r.warmup = 4;
+    r.halo = 3;
+    // (a slab: the march's planes; a unit that ends at either end of them also stores t+2 on the plane beyond it -- TripleArgs::z2_lo /
+    // z2_hi --, so a node to update there makes the unit live as well)
+    r.extra_lo = p.z0 > z_begin_ ? 1 : 0;
+    r.extra_hi = p.z1 < z_end_ ? 1 : 0;
+    r.slots_per_xcd = 32ll * std::max(1, (lb == 16 ? 8 : 12) / std::max(1, p.nw));
     // How many planes to a unit?  About wv_tuning::pair_unit_planes + 8 (a unit marches four warm-up planes before its first output where
-    // a two-step unit marches three), and among the heights near that the one whose units fill the chip's workgroup slots in the fewest,
-    // fullest rounds -- as build_pair_units chooses.  wv_tuning::triple_chunks > 0 sets the number of chunks instead.
-    const int per_cu = std::max(1, (lb == 16 ? 8 : 12) / std::max(1, triple_nw_));
-    const int64_t slots_per_xcd = 32ll * per_cu;
-    auto units_of = [&](int height, std::vector<uint32_t>* per_strip) -> uint64_t {
-        const int n_chunks = (owned + height - 1) / height;
-        uint64_t units = 0;
-        for (int sidx = 0; sidx < triple_strips_; ++sidx)
-            for (int c = 0; c < n_chunks; ++c) {
-                const int zb = z_lo + c * height, ze = std::min(zb + height, z_hi);
-                bool any = false;
-                for (int z = zb - (zb == z_lo ? extra_lo : 0); z < ze + (ze == z_hi ? extra_hi : 0) && !any; ++z) any = active[(size_t)z * triple_strips_ + sidx] != 0;
-                if (per_strip) (*per_strip)[(size_t)sidx] += any;
-                units += any;
-            }
-        return units;
-    };
-    auto rounds_cost = [&](int height) -> double {
-        std::vector<uint32_t> per_strip((size_t)triple_strips_, 0u);
-        const uint64_t units = units_of(height, &per_strip);
-        if (!units) return 0.0;
-        uint64_t longest = 0, so_far = 0, start = 0;  // the same partition into eight runs of strips as below
-        int sidx = 0;
-        for (int k = 0; k < 8; ++k) {
-            const uint64_t want = units * (uint64_t)(k + 1) / 8;
-            while (sidx < triple_strips_ && (so_far < want || k == 7)) so_far += per_strip[(size_t)sidx++];
-            longest = std::max(longest, so_far - start);
-            start = so_far;
-        }
-        return (double)((longest + slots_per_xcd - 1) / slots_per_xcd) * (double)(height + 4);
-    };
-    int zc;
-    if (opt_.tuning.triple_chunks > 0) {
-        zc = std::max(4, (owned + opt_.tuning.triple_chunks - 1) / opt_.tuning.triple_chunks);
-    } else {
-        const int base = std::max(8, std::min(owned, opt_.tuning.pair_unit_planes + 8));
-        zc = base;
-        double best = rounds_cost(zc);
-        for (int height = base * 3 / 4; height <= base * 5 / 4; ++height) {
-            if (height < 8 || height > owned) continue;
-            const double cost = rounds_cost(height);
-            if (cost > 0 && cost < best * 0.97) {  // (only a clear win moves the height)
-                best = cost;
-                zc = height;
-            }
-        }
-    }
-    const int chunks = (owned + zc - 1) / zc;
-    if (chunks >= (1 << 9)) return WV_OK;  // (9 bits of a list entry)
-    std::vector<std::vector<uint32_t>> of_strip((size_t)triple_strips_);
-    uint64_t total = 0, live_waves = 0;
-    for (int sidx = 0; sidx < triple_strips_; ++sidx)
-        for (int c = 0; c < chunks; ++c) {
-            const int zb = z_lo + c * zc, ze = std::min(zb + zc, z_hi);
-            bool any = false;
-            for (int z = zb - (zb == z_lo ? extra_lo : 0); z < ze + (ze == z_hi ? extra_hi : 0) && !any; ++z) any = active[(size_t)z * triple_strips_ + sidx] != 0;
-            if (!any) continue;
-            uint32_t bits = 0;
-            for (int z = std::max(0, zb - 3); z < std::min(nz_, ze + 3); ++z)
-                for (int ss = std::max(0, sidx - 1); ss <= std::min(triple_strips_ - 1, sidx + 1); ++ss) bits |= raw[(size_t)z * triple_strips_ + ss];
-            const uint32_t lo = std::min((uint32_t)__builtin_ctz(bits | (1u << 31)), (uint32_t)row_waves - 1u);
-            const uint32_t hi = std::min(32u - (uint32_t)__builtin_clz(bits | 1u), (uint32_t)row_waves);
-            const uint32_t span = hi > lo ? hi - lo : 1u;
-            of_strip[(size_t)sidx].push_back(wv::triple_unit_entry((uint32_t)sidx, (uint32_t)c, lo, span));
-            live_waves += span;
-            ++total;
-        }
-    if (!total) return WV_OK;
-    triple_live_frac_ = (double)live_waves / ((double)triple_strips_ * chunks * row_waves);
-    std::vector<uint32_t> list;
-    list.reserve((size_t)total);
-    triple_units_longest_ = 0;
-    int sidx = 0;
-    for (int k = 0; k < 8; ++k) {
-        triple_unit_start_[k] = (uint32_t)list.size();
-        const uint64_t want = total * (uint64_t)(k + 1) / 8;  // cumulative share of XCDs 0 .. k
-        const size_t first = list.size();
-        while (sidx < triple_strips_ && (list.size() < want || k == 7)) {
-            list.insert(list.end(), of_strip[(size_t)sidx].begin(), of_strip[(size_t)sidx].end());
-            ++sidx;
-        }
-        // (chunk by chunk, the strips of a chunk side by side: what an XCD runs at one time are neighbouring strips at the same planes)
-        std::stable_sort(list.begin() + (std::ptrdiff_t)first, list.end(), [](uint32_t a, uint32_t b) { return ((a >> 14) & 0x1FFu) < ((b >> 14) & 0x1FFu); });
-        triple_units_longest_ = std::max<uint32_t>(triple_units_longest_, (uint32_t)list.size() - triple_unit_start_[k]);
-    }
-    triple_unit_start_[8] = (uint32_t)list.size();
-    uint32_t* staged = nullptr;
-    WV_HIP(hipMalloc((void**)&staged, list.size() * sizeof(uint32_t)));
-    if (hipMemcpy(staged, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(staged);
-        return fail(WV_E_HIP, "copying the three-step march's unit list to the device failed");
-    }
-    triple_units_ = staged;
-    triple_zc_ = zc;
-    triple_chunks_ = chunks;
-    return WV_OK;
+    // a two-step unit marches three) or the best height near that.  wv_tuning::triple_chunks > 0 sets the number of chunks instead.
+    r.search = opt_.tuning.triple_chunks <= 0;
+    r.start_height = r.search ? std::max(8, std::min(owned, opt_.tuning.pair_unit_planes + 8))
+                              : std::max(4, (owned + opt_.tuning.triple_chunks - 1) / opt_.tuning.triple_chunks);
+    r.search_in_limit = false;
+    r.search_follows = false;
+    r.chunk_shift = 14;  // (triple_unit_entry)
+    r.first_shift = 23;
+    r.span_shift = 27;
+    r.spans = true;
+    r.by_chunk = true;
+    std::vector<uint8_t> active;
+    std::vector<uint16_t> wave_bits;
+    const int rc = march_activity(p.strips, r.row_waves, WX, &active, &wave_bits);
+    if (rc) return rc;
+    if (!wv::plan_units(p, r, active.data(), wave_bits.data())) return WV_OK;
+    return upload_units(p, &triple_units_, "copying the three-step march's unit list to the device failed");
 }
 
-// The march of a pass over the planes [triple_z0_, triple_z1_) (a slab: t+2 also on the plane next to a face, which only the march can
+// The march of a pass over the planes [triple_plan_.z0, triple_plan_.z1) (a slab: t+2 also on the plane next to a face, which only the march can
 // supply), timed in an account of its own (WV_QUERY_TRIPLE_MARCH_NS); every eighth timed pass times its other launches too.
 template <typename Real>
 int Engine<Real>::launch_triple_march(int slot, const Real* A, const Real* B, Real* O1, Real* O2, Real* O3) {
@@ -412,36 +283,19 @@ int Engine<Real>::launch_triple_march(int slot, const Real* A, const Real* B, Re
     a.nz = nz_;
     a.pitch = pitch_;
     a.cls_pitch = cls_pitch_;
-    a.z_begin = triple_z0_;
-    a.z_end = triple_z1_;
-    a.z2_lo = triple_z0_ > z_begin_ ? 1 : 0;
-    a.z2_hi = triple_z1_ < z_end_ ? 1 : 0;
-    a.nw = triple_nw_;
-    a.zc = triple_zc_;
-    a.chunks = triple_chunks_;
-    a.strips = triple_strips_;
-    a.strips_per_xcd = (triple_strips_ + 7) / 8;
-    a.windows = triple_windows_;
-    for (int k = 0; k < triple_windows_; ++k) {
-        a.win_first |= (uint64_t)triple_win_[0][k] << (8 * k);
-        a.win_count |= (uint64_t)triple_win_[1][k] << (8 * k);
-        a.win_store_lo |= (uint64_t)triple_win_[2][k] << (8 * k);
-        a.win_store_hi |= (uint64_t)triple_win_[3][k] << (8 * k);
-    }
-    unsigned grid = 8u * (unsigned)a.strips_per_xcd * (unsigned)triple_chunks_ * (unsigned)std::max(1, triple_windows_);
-    if (triple_units_) {
-        a.unit_list = triple_units_;
-        for (int k = 0; k < 9; ++k) a.list_start[k] = triple_unit_start_[k];
-        grid = 8u * triple_units_longest_;
-    }
+    a.z_begin = triple_plan_.z0;
+    a.z_end = triple_plan_.z1;
+    a.z2_lo = triple_plan_.z0 > z_begin_ ? 1 : 0;
+    a.z2_hi = triple_plan_.z1 < z_end_ ? 1 : 0;
+    const unsigned grid = wv::fill_march_args(a, triple_plan_, triple_units_);
     const bool timed = timing && time_this_launch();
     const int token = timed ? begin_part_timing(4, true) : -1;
     if (triple_lb_ == 8)
-        hipLaunchKernelGGL((wv::triple_march_kernel<Real, 0, false, 8>), dim3(grid), dim3(64u * (unsigned)triple_nw_),
-                           wv::triple_lds_bytes(triple_nw_, false, 8), stream_, a);
+        hipLaunchKernelGGL((wv::triple_march_kernel<Real, 0, false, 8>), dim3(grid), dim3(64u * (unsigned)triple_plan_.nw),
+                           wv::triple_lds_bytes(triple_plan_.nw, false, 8), stream_, a);
     else
-        hipLaunchKernelGGL((wv::triple_march_kernel<Real, 0, false, kWideLaneBytes>), dim3(grid), dim3(64u * (unsigned)triple_nw_),
-                           wv::triple_lds_bytes(triple_nw_, false, kWideLaneBytes), stream_, a);
+        hipLaunchKernelGGL((wv::triple_march_kernel<Real, 0, false, kWideLaneBytes>), dim3(grid), dim3(64u * (unsigned)triple_plan_.nw),
+                           wv::triple_lds_bytes(triple_plan_.nw, false, kWideLaneBytes), stream_, a);
     if ((rc = end_part_timing(4, token))) return rc;
     pass_timed_ = timed && (part_timing_calls_++ & 7u) == 0;
     return WV_OK;
@@ -478,8 +332,8 @@ int Engine<Real>::launch_triple_list(int slot, const Real* A, const Real* B, con
     g.nz = nz_;
     g.pitch = pitch_;
     g.cls_pitch = cls_pitch_;
-    g.z_begin = triple_z0_;
-    g.z_end = triple_z1_;
+    g.z_begin = triple_plan_.z0;
+    g.z_end = triple_plan_.z1;
     hipLaunchKernelGGL(wv::triple_list_kernel<Real>, dim3(std::max(1u, (triple_list_n_ + 255) / 256)), dim3(256), 0, stream_, f, g);
     return WV_OK;
 }
@@ -504,100 +358,52 @@ int Engine<Real>::enqueue_triple(int slot, uint64_t signal_pos, bool source_live
     int rc;
     const bool io = n_recv_ || source_live;
     const bool fuse = batch_can_fuse_ && n_entries_ != 0;
-    if (!pre_post_done_ && io) {  // step t: source sample into t, receivers from t
-        wv::PrePostArgs<Real> pp = pre_post_args(B, slot, true, signal_pos, source_live);
-        pp.flag = nullptr;
-        hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, pp);
-    }
+    if (!pre_post_done_ && io) launch_pre_post(B, slot, signal_pos, source_live, false);  // step t: source sample into t, receivers from t
     pre_post_done_ = false;
     if ((rc = launch_triple_march(slot, A, B, O1, O2, O3))) return rc;
     // level 1: boundary nodes to t+1 -- and, by the launch's last workgroup, step t+1's source sample / receivers (none of those nodes
     // is a boundary node: their t+1 has been final since the march) and then the second level's list where it is short and none of its
     // nodes has a boundary node for a neighbour (the source's neighbours, typically)
-    bool list2_done = false;
     const bool xw = triple_xw_ && xw_active_;
-    if (xw && !xw_valid_) {  // the x-facing walls' compact copies, from fields t-1 and t
-        wv::BoundaryArgs<Real> g = boundary_args(A, B, flag1);
-        xwall_args(g);
-        hipLaunchKernelGGL(wv::xwall_gather_kernel<Real>, dim3(g.xw_pad / 256), dim3(256), 0, stream_, g);
-    }
+    if (xw && !xw_valid_) refresh_xwall_copies(A, B, flag1);  // the x-facing walls' compact copies, from fields t-1 and t
     xw_valid_ = xw;  // (passes that do not maintain the copies leave them behind)
-    int token = begin_part_timing(0);
-    if (fuse && io) {
-        wv::PrePostArgs<Real> nx = pre_post_args(O1, slot + 1, true, signal_pos + 1, source_live);
-        nx.flag = nullptr;
-        if (pair_list_early_ok_ && pair_list_n_) {
-            nx.fix_nodes = pair_list_;
-            nx.fix_n = pair_list_n_;
-            nx.fix_cur = B;
-            nx.fix_out2 = O2;
-            nx.fix_flag = flag2;
-            nx.nx = nx_;
-            nx.ny = ny_;
-            nx.nz = nz_;
-            nx.pitch = pitch_;
-            list2_done = true;
-        }
-        if ((rc = launch_boundary(A, B, flag1, z_begin_, z_end_, &nx, O1, false, false, nullptr, xw ? 1 : 0))) return rc;
-    } else {
-        if ((rc = launch_boundary(A, B, flag1, z_begin_, z_end_, nullptr, O1, false, false, nullptr, xw ? 1 : 0))) return rc;
-        if (io) {
-            wv::PrePostArgs<Real> pp = pre_post_args(O1, slot + 1, true, signal_pos + 1, source_live);
-            pp.flag = nullptr;
-            hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, pp);
-        }
-    }
-    if ((rc = end_part_timing(0, token))) return rc;
+    wv::PrePostArgs<Real> nx = pre_post_args(O1, slot + 1, true, signal_pos + 1, source_live);
+    nx.flag = nullptr;
+    const bool list2_done = fuse && io && pair_list_early_ok_ && pair_list_n_;
+    if (list2_done) carry_short_list(nx, B, O2, flag2);
+    if ((rc = launch_boundary_with_io(0, A, B, flag1, z_begin_, z_end_, O1, false, false, xw ? 1 : 0, nx,
+                                      fuse && io ? IoRide::carried : io ? IoRide::behind : IoRide::none))) return rc;
     // level 2: the second level's list (as in a two-step pass), then the boundary nodes, whose 1-D entries finish the nodes they face --
     // with step t+2's source / receiver work where none of those nodes is written by the launch
     if (!list2_done && (rc = launch_fixup(0, pair_list_n_, O1, B, O2, flag2))) return rc;
-    token = begin_part_timing(1);
-    if (fuse && io && io_nodes_unfaced()) {
-        wv::PrePostArgs<Real> nx = pre_post_args(O2, slot + 2, true, signal_pos + 2, source_live);
-        nx.flag = nullptr;
-        if ((rc = launch_boundary(B, O1, flag2, z_begin_, z_end_, &nx, O2, pair_inner_ok_ > 0, false, nullptr, xw ? 2 : 0))) return rc;
-    } else {
-        if ((rc = launch_boundary(B, O1, flag2, z_begin_, z_end_, nullptr, O2, pair_inner_ok_ > 0, false, nullptr, xw ? 2 : 0))) return rc;
-        if (io) {
-            wv::PrePostArgs<Real> pp = pre_post_args(O2, slot + 2, true, signal_pos + 2, source_live);
-            pp.flag = nullptr;
-            hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, pp);
-        }
-    }
-    if ((rc = end_part_timing(1, token))) return rc;
+    nx = pre_post_args(O2, slot + 2, true, signal_pos + 2, source_live);
+    nx.flag = nullptr;
+    if ((rc = launch_boundary_with_io(1, B, O1, flag2, z_begin_, z_end_, O2, pair_inner_ok_ > 0, false, xw ? 2 : 0, nx,
+                                      fuse && io && io_nodes_unfaced() ? IoRide::carried : io ? IoRide::behind : IoRide::none))) return rc;
     // level 3: every shell node from the finished t+2 field -- and the exact error bits of what the march was the last to write, should it
     // have seen an inf or a nan (fields t-1 and t are still what the march read) --, then the boundary nodes
-    token = begin_part_timing(3);
+    const int token = begin_part_timing(3);
     if ((rc = launch_triple_list(slot, A, B, O1, O2, O3, source_live))) return rc;
     if ((rc = end_part_timing(3, token))) return rc;
-    token = begin_part_timing(2);
-    if (fuse && fuse_next && (!xw || io_nodes_clear_of_x_walls())) {
-        // what follows reads its source / receiver nodes from the t+3 field: none of them is a boundary node (nor, with the x-facing walls
-        // on their copies, one of the two nodes such an entry finishes)
-        wv::PrePostArgs<Real> nx = pre_post_args(O3, slot + 3, true, signal_pos + 3, source_live);
-        if (fuse_next == 2) nx.flag2 = flags_ + slot + 4;
-        if ((rc = launch_boundary(O1, O2, flag3, z_begin_, z_end_, &nx, O3, false, false, nullptr, xw ? 3 : 0))) return rc;
-        pre_post_done_ = true;
-    } else if ((rc = launch_boundary(O1, O2, flag3, z_begin_, z_end_, nullptr, O3, false, false, nullptr, xw ? 3 : 0))) {
-        return rc;
-    }
-    if ((rc = end_part_timing(2, token))) return rc;
+    // what follows reads its source / receiver nodes from the t+3 field: none of them is a boundary node (nor, with the x-facing walls
+    // on their copies, one of the two nodes such an entry finishes)
+    const bool carry = fuse && fuse_next && (!xw || io_nodes_clear_of_x_walls());
+    nx = pre_post_args(O3, slot + 3, true, signal_pos + 3, source_live);
+    if (fuse_next == 2) nx.flag2 = flags_ + slot + 4;
+    if ((rc = launch_boundary_with_io(2, O1, O2, flag3, z_begin_, z_end_, O3, false, false, xw ? 3 : 0, nx,
+                                      carry ? IoRide::carried : IoRide::none))) return rc;  // (not carried: the next step's or pass's own launch)
+    if (carry) pre_post_done_ = true;
     pass_timed_ = false;
     WV_HIP(hipGetLastError());
     ++triples_taken_;
-    // roles: (previous, current) = (t+2, t+3); the fields that held t-1 and t are the spares now
-    const int a_idx = prv_, b_idx = cur_;
-    prv_ = spare_[0];
-    cur_ = spare_[1];
-    spare_[0] = a_idx;
-    spare_[1] = b_idx;
+    rotate_after_pass();  // (previous, current) = (t+2, t+3)
     return WV_OK;
 }
 
 // ---- three-step passes of a z-slab -----------------------------------------------------------------------------------------------
 // With f = a face plane (a neighbour mirrors it as its ghost plane), n = the owned plane next to it, g = the ghost plane beyond it: from
 // the ghost's t alone the march can produce t+1 from f on, t+2 from n on, t+3 from the plane after n on -- so it marches
-// [triple_z0_, triple_z1_), stores t+2 on n as well (TripleArgs::z2_lo / z2_hi), and f and n take plain steps (launch_faces: sweep + their
+// [triple_plan_.z0, triple_plan_.z1), stores t+2 on n as well (TripleArgs::z2_lo / z2_hi), and f and n take plain steps (launch_faces: sweep + their
 // boundary nodes, as in a two-step pass), each level as soon as the neighbour's face of the level before is here.  Three exchanges per
 // pass, each enqueued ahead of some other work of about its length:
 //   part 0  [ghosts of t]  source / receivers on t -> f, n to t+1 -> march -> EXCHANGE 1 (t+1 faces) -> boundary nodes of its planes to t+1
@@ -630,14 +436,8 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
     const bool io = n_recv_ || source_live;
     const bool xw = triple_xw_ && xw_active_;
     const size_t plane = (size_t)pitch_ * ny_;
-    const int z0 = triple_z0_, z1 = triple_z1_;
+    const int z0 = triple_plan_.z0, z1 = triple_plan_.z1;
     const int n0 = z0 - (opt_.ghost_lo ? 1 : 0), n1 = z1 + (opt_.ghost_hi ? 1 : 0);  // ... and the planes next to the faces
-    auto pre_post = [&](Real* field, int step) {
-        if (!io) return;
-        wv::PrePostArgs<Real> pp = pre_post_args(field, slot + step, true, signal_pos + (uint64_t)step, source_live);
-        pp.flag = nullptr;  // (the batch's flag words were reset in one go: plan_batch)
-        hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, pp);
-    };
     auto wait_for = [&](int field) -> int {
         const int token = begin_halo_wait_timing();
         if (!comm_->wait_ghosts(stream_, field, &cerr)) return fail(WV_E_COMM, cerr);
@@ -651,7 +451,7 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
     if (!batch_flags_reset_) return fail(WV_E_STATE, "a slab's three-step pass without the batch's flag words reset");
     if (part == 0) {
         if ((rc = wait_for(cur_))) return rc;
-        pre_post(B, 0);
+        if (io) launch_pre_post(B, slot, signal_pos, source_live, false);  // (the batch's flag words were reset in one go: plan_batch)
         pre_post_done_ = false;
         if ((rc = launch_faces(A, B, flag1, O1, 2))) return rc;
         WV_HIP(hipGetLastError());
@@ -665,11 +465,7 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
         if ((rc = launch_triple_march(slot, A, B, O1, O2, O3))) return rc;
         if (!comm_->bulk_end(stream_, &cerr)) return fail(WV_E_COMM, cerr);
         if (!ahead && !comm_->exchange_faces(stream_, spare_[1], &cerr)) return fail(WV_E_COMM, cerr);
-        if (xw && !xw_valid_) {  // the x-facing walls' compact copies, from fields t-1 and t
-            wv::BoundaryArgs<Real> g = boundary_args(A, B, flag1);
-            xwall_args(g);
-            hipLaunchKernelGGL(wv::xwall_gather_kernel<Real>, dim3(g.xw_pad / 256), dim3(256), 0, stream_, g);
-        }
+        if (xw && !xw_valid_) refresh_xwall_copies(A, B, flag1);  // the x-facing walls' compact copies, from fields t-1 and t
         xw_valid_ = xw;
         const int token = begin_part_timing(0);
         if ((rc = launch_boundary(A, B, flag1, z0, z1, nullptr, O1, false, false, nullptr, xw ? 1 : 0))) return rc;
@@ -678,7 +474,7 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
         if ((rc = wait_for(spare_[1]))) return rc;
         if (opt_.ghost_lo && (rc = copy_plane(O1, O3, 0))) return rc;
         if (opt_.ghost_hi && (rc = copy_plane(O1, O3, nz_ - 1))) return rc;
-        pre_post(O1, 1);
+        if (io) launch_pre_post(O1, slot + 1, signal_pos + 1, source_live, false);
         if ((rc = launch_faces(B, O1, flag2, O2, 1))) return rc;
         WV_HIP(hipGetLastError());
         if (!comm_->exchange_faces(stream_, spare_[0], &cerr)) return fail(WV_E_COMM, cerr);
@@ -688,7 +484,7 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
         if ((rc = end_part_timing(1, token))) return rc;
     } else {
         if ((rc = wait_for(spare_[0]))) return rc;
-        pre_post(O2, 2);
+        if (io) launch_pre_post(O2, slot + 2, signal_pos + 2, source_live, false);
         if ((rc = launch_faces(O1, O2, flag3, O3, 2))) return rc;
         WV_HIP(hipGetLastError());
         if (!comm_->exchange_faces(stream_, spare_[1], &cerr)) return fail(WV_E_COMM, cerr);
@@ -702,11 +498,7 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
         WV_HIP(hipGetLastError());
         if (!comm_->step_done(stream_, &cerr)) return fail(WV_E_COMM, cerr);
         ++triples_taken_;
-        const int a_idx = prv_, b_idx = cur_;
-        prv_ = spare_[0];
-        cur_ = spare_[1];
-        spare_[0] = a_idx;
-        spare_[1] = b_idx;
+        rotate_after_pass();
     }
     return WV_OK;
 }

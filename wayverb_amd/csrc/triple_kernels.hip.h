@@ -42,6 +42,7 @@
 #pragma once
 #include <type_traits>
 
+#include "march_plan.h"
 #include "pair_kernels.hip.h"
 
 namespace wv {
@@ -106,47 +107,8 @@ __host__ __device__ inline uint32_t triple_unit_entry(uint32_t strip, uint32_t c
     return strip | (chunk << 14) | (wave_first << 23) | ((waves - 1u) << 27);
 }
 
-// How a row of `row_waves` waves is shared out: windows of at most kTripleMaxWaves waves, one halo wave on every interior side.
-// win[0..3][k] = first wave run, waves run, first wave stored, end of the stored waves.  `full_first`: as many full workgroups (12 waves:
-// three on every SIMD) as the row gives and one short one for the rest -- two short ones share a CU -- instead of equal shares (16
-// waves: 12 + 6 instead of 9 + 9, whose 9 waves are 3 + 2 + 2 + 2 on a CU's SIMDs and as slow as 12).
-// Returns the number of windows (0: the row is one workgroup), -1 if the row is too long; *widest = waves per workgroup.
-inline int triple_windows(int row_waves, uint8_t win[4][kTripleMaxWindows], int* widest, bool full_first = true, int max_waves = kTripleMaxWaves) {
-    *widest = row_waves;
-    if (row_waves <= max_waves) return 0;
-    int n = 0, at = 0;
-    *widest = 0;
-    if (full_first) {
-        while (at < row_waves && n < kTripleMaxWindows) {
-            const int lo_halo = at > 0 ? 1 : 0;
-            int end = at + max_waves - lo_halo;  // storing [at, end) with no halo above ...
-            if (end < row_waves) end -= 1;             // ... or one wave less and a halo wave
-            end = end < row_waves ? end : row_waves;
-            const int first = at - lo_halo, last = end + (end < row_waves ? 1 : 0);
-            win[0][n] = (uint8_t)first;
-            win[1][n] = (uint8_t)(last - first);
-            win[2][n] = (uint8_t)at;
-            win[3][n] = (uint8_t)end;
-            if (last - first > *widest) *widest = last - first;
-            ++n;
-            at = end;
-        }
-        return at < row_waves ? -1 : n;
-    }
-    n = 2;  // the widest window stores ceil(row_waves / n) waves and has a halo wave on one side (n = 2) or two
-    while (n <= kTripleMaxWindows && (row_waves + n - 1) / n + (n > 2 ? 2 : 1) > max_waves) ++n;
-    if (n > kTripleMaxWindows) return -1;
-    for (int k = 0; k < n; ++k) {
-        const int lo = row_waves * k / n, hi = row_waves * (k + 1) / n;
-        const int first = lo - (k > 0 ? 1 : 0), last = hi + (k + 1 < n ? 1 : 0);
-        win[0][k] = (uint8_t)first;
-        win[1][k] = (uint8_t)(last - first);
-        win[2][k] = (uint8_t)lo;
-        win[3][k] = (uint8_t)hi;
-        if (last - first > *widest) *widest = last - first;
-    }
-    return n;
-}
+// (how a row is shared out among windows: wv::triple_windows, march_plan.h)
+static_assert(kTripleMaxWindows == kMarchMaxWindows && kTripleMaxWaves == 12, "march_plan.h: triple_windows' table and default");
 
 inline size_t triple_lds_bytes(int nw, bool dma = false, int LB = kTripleLaneBytes) {
     return (size_t)nw * (kTripleLoSlots + (dma ? kTriplePvSlots : 0)) * 64 * LB + (size_t)2 * kTripleEdgeRows * (triple_max_waves(LB) + 2) * 2 * LB;
