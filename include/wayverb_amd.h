@@ -259,6 +259,50 @@ int wv_fetch_receivers(wv_engine* e, uint64_t first, uint64_t n, double* dst);
 /* Number of loop iterations completed since creation. */
 int wv_step_count(wv_engine* e, uint64_t* steps);
 
+/* ---- field snapshots while a run keeps going --------------------------------------------------- */
+/* The reference's application hangs a mesh-pressure visualiser off the per-step callback (src/combined/src/engine.cpp:158-169): it
+ * looks at the field while `run` goes on.  Here the field never leaves the device during wv_run, and reading it (wv_read_planes)
+ * between short runs stops the compute stream for an allocation, a packing launch and a copy.  A snapshot plan has the engine record
+ * the field itself: a box of the mesh, every s-th node along each axis, every `period` steps, as floats (a double rounds to nearest,
+ * exactly as wv_read_planes with elem_size 4 converts), captured ON THE DEVICE directly behind the pass that produced the step and
+ * copied to page-locked host memory on a stream of its own while the next steps already run.
+ *
+ * The snapshot "of step s" is the field after exactly s completed steps: bit for bit the floats wv_read_planes(e, WV_BUF_CURRENT, ...,
+ * 4) returns when wv_step_count says s, subsampled to the box -- what `post` (and `canonical`'s callback) sees at step s, but for the
+ * source's sample of step s, which the loop puts into its node before `post` looks and after the snapshot is taken.  Steps
+ * count from the engine's creation; step first_step + j * period is captured if it is >= the step count when the plan was set (a
+ * step equal to that count: at the start of the next wv_run).  Snapshots are numbered 0, 1, ... in the order taken since the plan
+ * was set; the host holds the last `keep` of them (0: all).
+ *
+ *   - a run that stops on a flag at step f holds no snapshot of a step > f
+ *   - wv_rollback drops the snapshots of steps after the checkpoint; the re-run takes them again, bit-identical
+ *   - wv_step / wv_swap take no snapshots (as they record no receiver rows); snapshot steps they pass are passed
+ *   - on return from wv_run every snapshot of a completed step can be fetched
+ *   - passes end on snapshot steps (a two- or three-step pass never holds the steps inside it as whole fields) and a batch of steps
+ *     holds no more captures than the ring has slots, so a short period costs some of the passes' advantage; results are
+ *     bit-identical with and without a plan
+ *
+ * wv_set_snapshots allocates the device ring and its page-locked twin (WV_E_HIP when there is no room, the engine and any earlier
+ * plan untouched); a new plan replaces the old one and forgets what it held; NULL stops recording, forgets and frees (as does
+ * wv_destroy).  WV_E_INVALID_ARGUMENT for a box that leaves the mesh, a zero stride or a zero period.  One domain only: a slab of a
+ * chain (ghost planes, or a communicator of more than one rank) answers WV_E_STATE -- every rank would hold a part of the box and
+ * the chain would have to agree on the cuts; nobody needs that yet.
+ * wv_fetch_snapshots: snapshots [first, first + n) as float[n][nz][ny][nx], their steps in steps[n] (may be NULL);
+ * WV_E_INVALID_ARGUMENT for one that was dropped or is not taken yet.  wv_snapshot_count: *taken = snapshots taken since the plan
+ * was set, *first_held = the oldest still held (either may be NULL). */
+typedef struct wv_snapshot_plan {
+    int32_t x0, y0, z0;  /* first node of the box */
+    int32_t nx, ny, nz;  /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;  /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step; /* snapshots at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;     /* >= 1 */
+    uint32_t keep;       /* snapshots held on the host; older ones are dropped.  0 = all */
+    uint32_t reserved;
+} wv_snapshot_plan;
+int wv_set_snapshots(wv_engine* e, const wv_snapshot_plan* plan);
+int wv_snapshot_count(wv_engine* e, uint64_t* taken, uint64_t* first_held);
+int wv_fetch_snapshots(wv_engine* e, uint64_t first, uint64_t n, float* dst /* [n][nz][ny][nx] */, uint64_t* steps /* [n] */);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */
@@ -283,7 +327,9 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *                            waits (every fourth); both reset by wv_kernel_time
  *   WV_QUERY_HALO_EXCHANGES, WV_QUERY_HALO_BYTES_SENT   exchanges issued and bytes handed to neighbours since creation
  *   WV_QUERY_EARLY_PASSES    two-step passes of a slab that ran both exchanges under the march (wv_tuning::slab_early)
- *   WV_QUERY_TRIPLE_PASSES   three-step passes taken since creation (wv_tuning::triple) */
+ *   WV_QUERY_TRIPLE_PASSES   three-step passes taken since creation (wv_tuning::triple)
+ *   WV_QUERY_SNAPSHOT_NS, WV_QUERY_SNAPSHOT_BYTES, WV_QUERY_SNAPSHOTS_TAKEN   since wv_set_snapshots: total time of the capture kernels
+ *                            that ran with kernel timing on, bytes captured, snapshots taken */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -297,7 +343,8 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
         * the passes whose parts were timed (every eighth timed pass): their third boundary launch and their third-level fix-up list
         * (WV_QUERY_BOUNDARY1_NS / 2_NS count the first two boundary launches of either kind of pass) */
        WV_QUERY_TRIPLE_MARCH_NS = 16, WV_QUERY_TRIPLE_MARCH_TIMED = 17, WV_QUERY_BOUNDARY3_NS = 18, WV_QUERY_FIXUP3_NS = 19,
-       WV_QUERY_TRIPLE_PARTS_TIMED = 20 };
+       WV_QUERY_TRIPLE_PARTS_TIMED = 20,
+       WV_QUERY_SNAPSHOT_NS = 21, WV_QUERY_SNAPSHOT_BYTES = 22, WV_QUERY_SNAPSHOTS_TAKEN = 23 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

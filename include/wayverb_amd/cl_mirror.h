@@ -32,6 +32,15 @@
 // mirroring 4.3 GB per step for nobody would cost it a factor of 400 -- but it holds NaN, not zeros, and the first
 // such run says so on stderr: a visualiser that does read it shows nothing and the log says which line is missing,
 // instead of a silent field of zeros.
+//
+// A DECLARED CADENCE -- `waveguide::cl_mirror_cadence() = k;` (k > 0; default 0 = everything above, untouched) -- is the cheap way to
+// feed a visualiser that takes every k-th step (the reference's application draws far fewer frames than the waveguide takes steps):
+// `canonical` has the engine record `cl_mirror_planes()` itself every k steps while it runs (wv_set_snapshots: captured on the device
+// behind the pass that produced the step, copied on a stream of its own) and runs ahead in whole batches with NO rollbacks.  Before
+// the callback of a step s = 0 (mod k) that step's snapshot is written into the buffer, straight from the fetched floats (with the hard
+// source's sample of that step in its node, as the callback of the reference's loop finds it) -- the chosen planes cross once, as
+// floats; at other steps the buffer keeps the last mirrored field.  The predicate is not consulted.
+// last_run_stats().fields_mirrored counts the refreshes; rollbacks stays 0.
 #pragma once
 
 #include <cstdio>
@@ -67,6 +76,12 @@ inline mirror_planes& cl_mirror_planes() {
     static mirror_planes p;
     return p;
 }
+/// k > 0: the buffer follows the field every k-th step (steps 0, k, 2k, ...) through a snapshot plan of the engine, and the run never
+/// comes back for a step (above).  0 (default): the predicate decides, step by step.
+inline size_t& cl_mirror_cadence() {
+    static size_t k = 0;
+    return k;
+}
 
 namespace detail {
 
@@ -82,7 +97,7 @@ public:
               nodes_{nodes} {
         // zeros until somebody wants the field (make_zeroed_buffer is what the reference's own field starts as, waveguide.h:47-56) --
         // NaN when nobody has said whether anybody will (an empty predicate): a reader then sees that it is not looking at a field
-        const bool unset = !cl_mirror_wanted();
+        const bool unset = !cl_mirror_wanted() && cl_mirror_cadence() == 0;
         const cl_float fill = unset ? std::numeric_limits<cl_float>::quiet_NaN() : cl_float{0};
         if (unset) {
             static bool warned = false;
@@ -131,6 +146,50 @@ public:
         callback(queue_, static_cast<const cl::Buffer&>(buffer_), step, steps);
     }
 
+    // ---- a declared cadence (cl_mirror_cadence() = k > 0) --------------------------------------------------------------------
+    static size_t cadence() { return cl_mirror_cadence(); }
+    /// Sets the engine's snapshot plan: planes cl_mirror_planes() of an nx * ny * nz mesh, whole, every k steps from step 0.  The
+    /// callbacks of a batch of up to `max_batch` steps fire after it: the host keeps the snapshots of one batch and the one before.
+    /// `source_node`, `samples`: `canonical`'s hard source.  A snapshot is the field after s completed steps; what the callback of step
+    /// s is handed (waveguide.h:80-121) is that field with the source's sample of step s already forced into its node, so the sample
+    /// is put there when the snapshot goes into the buffer (a float either way: the buffer holds exactly what an every-step mirror does).
+    void begin_cadence(int nx, int ny, int nz, size_t max_batch, size_t source_node, const std::vector<float>* samples) {
+        source_node_ = source_node;
+        samples_ = samples;
+        cadence_ = cl_mirror_cadence();
+        const mirror_planes want = cl_mirror_planes();
+        z0_ = want.z_count < 0 ? 0 : std::min(std::max(want.z_begin, 0), nz);
+        zn_ = want.z_count < 0 ? nz : std::min(want.z_count, nz - z0_);
+        if (zn_ <= 0 || cadence_ == 0) {
+            cadence_ = 0;
+            return;
+        }
+        wv_snapshot_plan plan{};
+        plan.x0 = 0, plan.y0 = 0, plan.z0 = z0_;
+        plan.nx = nx, plan.ny = ny, plan.nz = zn_;
+        plan.sx = plan.sy = plan.sz = 1;
+        plan.first_step = 0;
+        plan.period = cadence_;
+        plan.keep = (uint32_t)(max_batch / cadence_ + 2);
+        check(wv_set_snapshots(engine_, &plan));
+        staging_.assign((size_t)zn_ * plane_nodes_, 0.0f);
+    }
+    template <typename Callback>
+    void invoke_cadenced(Callback& callback, size_t step, size_t steps) {
+        if (cadence_ && step % cadence_ == 0) {
+            uint64_t of_step = 0;
+            check(wv_fetch_snapshots(engine_, step / cadence_, 1, staging_.data(), &of_step));
+            if (of_step != step) throw engine_error("wayverb_amd: the snapshot fetched for the cl::Buffer mirror is of another step");
+            const size_t first = (size_t)z0_ * plane_nodes_;
+            if (samples_ && step < samples_->size() && source_node_ >= first && source_node_ - first < staging_.size())
+                staging_[source_node_ - first] = (*samples_)[step];
+            queue_.enqueueWriteBuffer(buffer_, CL_TRUE, sizeof(cl_float) * (size_t)z0_ * plane_nodes_, sizeof(cl_float) * staging_.size(),
+                                      staging_.data());
+            ++last_run_stats().fields_mirrored;
+        }
+        callback(queue_, static_cast<const cl::Buffer&>(buffer_), step, steps);
+    }
+
     ~cl_mirror_bridge() {
         if (registered_) (void)wv_host_unregister(staging_.data());
     }
@@ -146,6 +205,10 @@ private:
     size_t nodes_;
     std::vector<float> staging_;
     bool registered_ = false;
+    size_t cadence_ = 0;  // the cadence this run was set up with (0: none)
+    int z0_ = 0, zn_ = 0;
+    size_t source_node_ = 0;
+    const std::vector<float>* samples_ = nullptr;  // canonical's hard source: one sample per step
 };
 
 // any context with a `.context` member that a cl::CommandQueue can be built from

@@ -736,16 +736,22 @@ template <typename OnBatch>
 void call_on_batch(OnBatch& f, wv_engine*, size_t first, size_t n, const std::vector<double>& s, long) {
     f(first, n, s);
 }
+struct no_engine_hook final {
+    void operator()(wv_engine*) const {}
+};
 }  // namespace detail
 
-template <typename Context, typename Mesh, typename It, typename OnBatch>
+/// `on_engine(wv_engine*)`: called once, when the engine stands ready (source and receivers set) and before its first step --
+/// where a caller sets what the run is to record besides the receivers (a snapshot plan: wv_set_snapshots).
+template <typename Context, typename Mesh, typename It, typename OnBatch, typename OnEngine = detail::no_engine_hook>
 size_t run_device(const Context& cc, const Mesh& mesh, source_kind kind, size_t source_node, It begin, It end,
                   const std::vector<uint64_t>& receivers, OnBatch&& on_batch, const std::atomic_bool& keep_going,
-                  size_t batch = 256) {
+                  size_t batch = 256, OnEngine&& on_engine = OnEngine{}) {
     auto engine = detail::make_engine(cc, mesh, default_precision());
     std::vector<double> signal(begin, end);
     detail::check(wv_set_source(engine.get(), (int)kind, source_node, signal.data(), signal.size()));
     detail::check(wv_set_receivers(engine.get(), receivers.data(), (uint32_t)receivers.size()));
+    on_engine(engine.get());
     size_t done_total = 0;
     std::vector<double> samples;
     run_stats& stats = last_run_stats();
@@ -831,6 +837,13 @@ public:
     void invoke(Callback& callback, size_t step, size_t steps) {
         callback(queue_, static_cast<const buffer&>(current_), step, steps);
     }
+    // a declared cadence is the cl::Buffer mirror's (cl_mirror.h, cl_mirror_cadence()): a handle shows the step's own field whenever it is read
+    static size_t cadence() { return 0; }
+    void begin_cadence(int, int, int, size_t, size_t, const std::vector<float>*) {}
+    template <typename Callback>
+    void invoke_cadenced(Callback& callback, size_t step, size_t steps) {
+        invoke(callback, step, steps);
+    }
 
 private:
     queue queue_;
@@ -864,6 +877,13 @@ template <typename Bridge, typename Callback>
 void fire(Bridge&, Callback& callback, size_t step, size_t steps, std::false_type) {
     callback(step, steps);
 }
+// (a declared cadence serves callbacks that see the field; for the others this is never reached and must merely compile)
+template <typename Bridge, typename Callback>
+void fire_cadenced(Bridge& bridge, Callback& callback, size_t step, size_t steps, std::true_type) {
+    bridge.invoke_cadenced(callback, step, steps);
+}
+template <typename Bridge, typename Callback>
+void fire_cadenced(Bridge&, Callback&, size_t, size_t, std::false_type) {}
 
 /// The device-resident run of `run_device`, AHEAD of per-step observers that may look at the field.
 ///
@@ -1096,7 +1116,30 @@ std::experimental::optional<band> canonical_impl(const Context& cc, const Mesh& 
         ret.directional.emplace_back(dr.accumulate((float)row[0], nb));
     };
     size_t steps = 0;
-    if (sees_field) {
+    // the bridge's field follows the run at a DECLARED cadence (cl_mirror.h, cl_mirror_cadence() = k > 0): the engine records the chosen
+    // planes itself every k steps (wv_set_snapshots) and the run goes ahead in whole batches -- no checkpoints, no rollbacks; before the
+    // callback of a step s = 0 (mod k) the bridge writes that step's snapshot into its buffer, at other steps the buffer keeps the last one.
+    // (A snapshot is the field after s completed steps; the callback's field is that with the hard source's sample of step s already
+    // in its node -- waveguide.h:80-121, SURVEY.md Appendix D Q1 / Q2 -- so the bridge is told the node and the samples and puts it there.)
+    const size_t cadence = sees_field ? bridge_t::cadence() : 0;
+    constexpr size_t cadence_batch = 256;
+    if (cadence) {
+        const auto& dims = mesh.get_descriptor().dimensions;
+        const size_t source_index = compute_mesh_index(source);
+        steps = run_device(
+                cc, mesh, source_kind::hard, source_index, input.begin(), input.end(), nodes,
+                [&](size_t first, size_t n, const std::vector<double>& s, wv_engine*) {
+                    for (size_t i = 0; i < n; ++i) {
+                        record(s.data() + i * 7);
+                        fire_cadenced(*bridge, callback, first + i, ideal_steps, std::integral_constant<bool, sees_field>{});
+                    }
+                },
+                keep_going, cadence_batch,
+                [&](wv_engine* e) {
+                    bridge.reset(callback_bridge_for<Context>::make(cc, e, num_nodes, plane_nodes, &guard));
+                    bridge->begin_cadence((int)dims.x, (int)dims.y, (int)dims.z, cadence_batch, source_index, &input);
+                });
+    } else if (sees_field) {
         steps = run_device_observed(
                 cc, mesh, source_kind::hard, compute_mesh_index(source), input.begin(), input.end(), nodes, guard,
                 [&](wv_engine* e) { bridge.reset(callback_bridge_for<Context>::make(cc, e, num_nodes, plane_nodes, &guard)); },

@@ -1,0 +1,162 @@
+// snapshot_plan_test.cpp -- the snapshot planning of wayverb_amd/csrc/snapshot_plan.h on the CPU (tests/test_snapshot_plan.py builds and
+// runs this).  Every expectation below is derived by hand from the contract in include/wayverb_amd.h, none recorded from the code.
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "snapshot_plan.h"
+
+static int g_failures = 0;
+#define CHECK(cond)                                                         \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
+            ++g_failures;                                                   \
+        }                                                                   \
+    } while (0)
+
+using namespace wv;
+
+// A stand-in for wv_run's loop: batches of at most `ring` steps, never past the next snapshot step; a snapshot is taken whenever the
+// step count stands on one (before the first batch too).  Returns the snapshot steps and checks that no batch is empty or steps over one.
+static std::vector<uint64_t> drive(uint64_t first, uint64_t period, uint64_t set_at, uint64_t run_steps, uint64_t ring,
+                                   std::vector<uint64_t>* batches = nullptr) {
+    std::vector<uint64_t> taken;
+    uint64_t done = set_at, next = snapshot_next_step(first, period, set_at);
+    const uint64_t end = set_at + run_steps;
+    if (next == done) {
+        taken.push_back(done);
+        next = snapshot_next_step(first, period, done + 1);
+    }
+    while (done < end) {
+        const uint64_t want = ring < end - done ? ring : end - done;
+        const uint64_t batch = snapshot_batch_limit(want, done, next);
+        CHECK(batch >= 1 && batch <= want);
+        CHECK(done + batch <= next);
+        if (batches) batches->push_back(batch);
+        done += batch;
+        if (done == next) {
+            taken.push_back(done);
+            next = snapshot_next_step(first, period, done + 1);
+        }
+    }
+    return taken;
+}
+
+int main() {
+    // ---- the next snapshot step from a step count
+    CHECK(snapshot_next_step(0, 1, 0) == 0);
+    CHECK(snapshot_next_step(0, 1, 17) == 17);
+    CHECK(snapshot_next_step(5, 3, 0) == 5);    // nothing before first_step
+    CHECK(snapshot_next_step(5, 3, 5) == 5);    // the first step is included when equal to the current count
+    CHECK(snapshot_next_step(5, 3, 6) == 8);
+    CHECK(snapshot_next_step(5, 3, 8) == 8);
+    CHECK(snapshot_next_step(5, 3, 9) == 11);
+    CHECK(snapshot_next_step(0, 64, 1) == 64);
+    CHECK(snapshot_next_step(0, 64, 64) == 64);
+    CHECK(snapshot_next_step(0, 64, 65) == 128);
+    CHECK(snapshot_next_step(10, 7, 100) == 101);  // 10 + 13 * 7
+    CHECK(snapshot_next_step(0, 0, 3) == kNoSnapshotStep);
+    CHECK(snapshot_next_step(kNoSnapshotStep - 2, 5, kNoSnapshotStep - 1) == kNoSnapshotStep);  // the next one does not fit in 64 bits
+    CHECK(snapshot_next_step(1, kNoSnapshotStep, 2) == kNoSnapshotStep);
+    CHECK(snapshot_is_step(5, 3, 0, 8) && !snapshot_is_step(5, 3, 0, 9) && !snapshot_is_step(5, 3, 9, 8) && snapshot_is_step(5, 3, 8, 8));
+
+    // ---- how far a batch may go
+    CHECK(snapshot_batch_limit(1024, 0, 64) == 64);
+    CHECK(snapshot_batch_limit(10, 0, 64) == 10);
+    CHECK(snapshot_batch_limit(1024, 60, 64) == 4);
+    CHECK(snapshot_batch_limit(1024, 63, 64) == 1);
+    CHECK(snapshot_batch_limit(1024, 64, 64) == 1024);  // due before the batch: the engine takes it first and asks again
+    CHECK(snapshot_batch_limit(1024, 0, kNoSnapshotStep) == 1024);
+    CHECK(snapshot_batch_limit(0, 3, 7) == 0);
+
+    // ---- batch cuts land exactly on snapshot steps: periods 1, 2, 3, 7, 64, batches longer and shorter than the period
+    for (uint64_t period : {1ull, 2ull, 3ull, 7ull, 64ull}) {
+        for (uint64_t ring : {1ull, 2ull, 5ull, 16ull, 1024ull}) {
+            for (uint64_t first : {0ull, 4ull}) {
+                for (uint64_t set_at : {0ull, 4ull, 9ull}) {
+                    const uint64_t steps = 200;
+                    const std::vector<uint64_t> got = drive(first, period, set_at, steps, ring);
+                    // by hand: every first + j * period in [set_at, set_at + steps]
+                    std::vector<uint64_t> want;
+                    for (uint64_t s = first; s <= set_at + steps; s += period)
+                        if (s >= set_at) want.push_back(s);
+                    CHECK(got == want);
+                }
+            }
+        }
+    }
+    {   // period 7 under a ring of 1024 from step 0, 30 steps: snapshot at 0 before the first batch, batches 7 7 7 7 2
+        std::vector<uint64_t> batches;
+        const std::vector<uint64_t> got = drive(0, 7, 0, 30, 1024, &batches);
+        CHECK((got == std::vector<uint64_t>{0, 7, 14, 21, 28}));
+        CHECK((batches == std::vector<uint64_t>{7, 7, 7, 7, 2}));
+    }
+    {   // period 64 under batches of 16: four batches per snapshot
+        std::vector<uint64_t> batches;
+        const std::vector<uint64_t> got = drive(64, 64, 0, 128, 16, &batches);
+        CHECK((got == std::vector<uint64_t>{64, 128}));
+        CHECK(batches.size() == 8);
+        for (uint64_t b : batches) CHECK(b == 16);
+    }
+    {   // a plan set at step 9 with first_step 4, period 3: 10 (not 4, 7: before the plan was set), 13, 16; batches 1 3 3 1
+        std::vector<uint64_t> batches;
+        const std::vector<uint64_t> got = drive(4, 3, 9, 8, 1024, &batches);
+        CHECK((got == std::vector<uint64_t>{10, 13, 16}));
+        CHECK((batches == std::vector<uint64_t>{1, 3, 3, 1}));
+    }
+
+    // ---- box validation at every mesh face (mesh 10 x 8 x 6)
+    auto box = [](int x0, int y0, int z0, int nx, int ny, int nz, int sx = 1, int sy = 1, int sz = 1) {
+        SnapshotBox b;
+        b.x0 = x0, b.y0 = y0, b.z0 = z0, b.nx = nx, b.ny = ny, b.nz = nz, b.sx = sx, b.sy = sy, b.sz = sz;
+        return b;
+    };
+    CHECK(snapshot_box_valid(box(0, 0, 0, 10, 8, 6), 10, 8, 6));          // the whole mesh: touches all six faces
+    CHECK(!snapshot_box_valid(box(0, 0, 0, 11, 8, 6), 10, 8, 6));         // one past +x
+    CHECK(!snapshot_box_valid(box(0, 0, 0, 10, 9, 6), 10, 8, 6));         // +y
+    CHECK(!snapshot_box_valid(box(0, 0, 0, 10, 8, 7), 10, 8, 6));         // +z
+    CHECK(!snapshot_box_valid(box(-1, 0, 0, 3, 3, 3), 10, 8, 6));         // -x
+    CHECK(!snapshot_box_valid(box(0, -1, 0, 3, 3, 3), 10, 8, 6));         // -y
+    CHECK(!snapshot_box_valid(box(0, 0, -1, 3, 3, 3), 10, 8, 6));         // -z
+    CHECK(snapshot_box_valid(box(9, 7, 5, 1, 1, 1), 10, 8, 6));           // the far corner node
+    CHECK(!snapshot_box_valid(box(10, 0, 0, 1, 1, 1), 10, 8, 6));
+    CHECK(!snapshot_box_valid(box(0, 8, 0, 1, 1, 1), 10, 8, 6));
+    CHECK(!snapshot_box_valid(box(0, 0, 6, 1, 1, 1), 10, 8, 6));
+    CHECK(snapshot_box_valid(box(0, 0, 0, 4, 3, 2, 3, 3, 3), 10, 8, 6));  // last nodes 9, 6, 3
+    CHECK(!snapshot_box_valid(box(1, 0, 0, 4, 3, 2, 3, 3, 3), 10, 8, 6)); // last x node 10
+    CHECK(!snapshot_box_valid(box(0, 2, 0, 4, 3, 2, 3, 3, 3), 10, 8, 6)); // last y node 8
+    CHECK(!snapshot_box_valid(box(0, 0, 3, 4, 3, 2, 3, 3, 3), 10, 8, 6)); // last z node 6
+    CHECK(!snapshot_box_valid(box(0, 0, 0, 0, 1, 1), 10, 8, 6));          // nothing taken
+    CHECK(!snapshot_box_valid(box(0, 0, 0, 1, 1, 1, 0, 1, 1), 10, 8, 6)); // zero stride
+    CHECK(!snapshot_box_valid(box(0, 0, 0, 1, 1, 1, 1, 1, -2), 10, 8, 6));
+    CHECK(!snapshot_box_valid(box(0, 0, 0, 2, 1, 1, 2147483647, 1, 1), 10, 8, 6));  // (no 32-bit overflow in the far node)
+    CHECK(snapshot_box_valid(box(0, 0, 0, 1, 1, 1, 2147483647, 1, 1), 10, 8, 6));
+
+    // ---- output shapes: strides that do and do not divide the box
+    CHECK(snapshot_axis_count(12, 1) == 12);
+    CHECK(snapshot_axis_count(12, 2) == 6);
+    CHECK(snapshot_axis_count(12, 3) == 4);
+    CHECK(snapshot_axis_count(12, 4) == 3);
+    CHECK(snapshot_axis_count(12, 5) == 3);   // nodes 0, 5, 10
+    CHECK(snapshot_axis_count(13, 4) == 4);   // nodes 0, 4, 8, 12
+    CHECK(snapshot_axis_count(1, 9) == 1);
+    CHECK(snapshot_axis_count(0, 2) == 0 && snapshot_axis_count(5, 0) == 0);
+    for (int extent = 1; extent <= 40; ++extent)
+        for (int s = 1; s <= 9; ++s) {
+            const int n = (int)snapshot_axis_count(extent, s);
+            CHECK(snapshot_axis_valid(0, n, s, extent));       // what is taken lies inside
+            CHECK(!snapshot_axis_valid(0, n + 1, s, extent));  // and one more would not
+        }
+    CHECK(snapshot_elements(box(0, 0, 0, 4, 3, 2, 3, 3, 3)) == 24 && snapshot_bytes(box(0, 0, 0, 4, 3, 2, 3, 3, 3)) == 96);
+    CHECK(snapshot_bytes(box(0, 0, 7, 512, 512, 1)) == (1u << 20));            // a 512^2 plane: 1 MiB
+    CHECK(snapshot_bytes(box(0, 0, 0, 2048, 2048, 2048)) == (32ull << 30));  // no 32-bit overflow
+    CHECK(snapshot_elements(box(0, 0, 0, 0, 3, 2)) == 0);
+
+    if (g_failures) {
+        std::printf("%d check(s) failed\n", g_failures);
+        return 1;
+    }
+    std::printf("SNAPSHOT PLAN OK\n");
+    return 0;
+}

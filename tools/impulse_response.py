@@ -38,6 +38,9 @@ def main():
     ap.add_argument("--pointing", type=float, nargs=3, default=[0.0, 0.0, 1.0])
     ap.add_argument("--precision", default="f64", choices=["f32", "f64"])
     ap.add_argument("--out", default="ir.wav")
+    ap.add_argument("--snapshots", help="z=<plane>,every=<k>: record plane z of the field every k steps while the run goes on "
+                                        "(Engine.set_snapshots; single-band runs)")
+    ap.add_argument("--snapshot-out", default="snapshots", help="directory the snapshots go to, one step_<n>.npy (float32[ny, nx]) each")
     args = ap.parse_args()
 
     bands = None
@@ -69,6 +72,18 @@ def main():
         table[name] = vals * 8 if len(vals) == 1 else vals
     absorptions = way_absorptions if args.way else [table.get(n, [0.05] * 8) for n in names]
 
+    snapshots = None
+    if args.snapshots:
+        if bands:
+            ap.error("--snapshots: single-band runs only")
+        want = dict(item.split("=") for item in args.snapshots.split(","))
+        if sorted(want) != ["every", "z"]:
+            ap.error("--snapshots takes z=<plane>,every=<k>")
+        plane, every = int(want["z"]), int(want["every"])
+
+        def snapshots(mesh):
+            return dict(box=((0, 0, plane), (None, None, 1)), period=every)
+
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
     if bands:   # multiple_band_constant_spacing: one run per band with flat per-band walls
@@ -79,10 +94,17 @@ def main():
                                       args.seconds, args.precision)
         audio = P.postprocess(bands, method, args.pointing, args.mic_shape or 0.0, env.acoustic_impedance, args.rate)
     else:
-        audio, bands, vm = W.impulse_response(v, t, absorptions, args.source, args.receiver, args.cutoff,
-                                              args.usable_portion, args.seconds, args.rate, method=method,
-                                              pointing=args.pointing, shape=args.mic_shape or 0.0,
-                                              precision=args.precision)
+        audio_etc = W.impulse_response(v, t, absorptions, args.source, args.receiver, args.cutoff,
+                                       args.usable_portion, args.seconds, args.rate, method=method,
+                                       pointing=args.pointing, shape=args.mic_shape or 0.0,
+                                       precision=args.precision, snapshots=snapshots)
+        if snapshots is not None:
+            fields, steps = audio_etc[3]
+            os.makedirs(args.snapshot_out, exist_ok=True)
+            for field, step in zip(fields, steps):
+                np.save(os.path.join(args.snapshot_out, "step_%06d.npy" % int(step)), field[0])
+            print("wrote %d snapshots of plane z=%d to %s" % (len(steps), plane, args.snapshot_out))
+        audio, bands, vm = audio_etc[:3]
     dt = time.perf_counter() - t0
     mesh = vm.mesh
     print("mesh %dx%dx%d (%d nodes, spacing %.4f m), %d steps at %.1f Hz, %d samples at %.0f Hz, %.2f s wall"

@@ -13,6 +13,7 @@
 #include "engine_triple.hip.h"
 #include "engine_batch.hip.h"
 #include "engine_io.hip.h"
+#include "engine_snapshot.hip.h"
 #include "engine_slab.hip.h"
 
 namespace {
@@ -188,6 +189,18 @@ int wv_rollback(wv_engine* e) {
 int wv_drop_checkpoint(wv_engine* e) {
     WV_NEED(e);
     return e->checkpoint(2);
+}
+int wv_set_snapshots(wv_engine* e, const wv_snapshot_plan* plan) {
+    WV_NEED(e);
+    return e->set_snapshots(plan);
+}
+int wv_snapshot_count(wv_engine* e, uint64_t* taken, uint64_t* first_held) {
+    WV_NEED(e);
+    return e->snapshot_count(taken, first_held);
+}
+int wv_fetch_snapshots(wv_engine* e, uint64_t first, uint64_t n, float* dst, uint64_t* steps) {
+    WV_NEED(e);
+    return e->fetch_snapshots(first, n, dst, steps);
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

@@ -15,16 +15,20 @@
 //   engine_batch.hip.h   wv_step / wv_run: batches of steps, flag words, kernel timing
 //   engine_io.hip.h      everything a caller reads or writes: values, fields, planes, filter memories, source,
 //                        receivers
+//   engine_snapshot.hip.h  field snapshots taken on the device while a run goes on (wv_set_snapshots): plan, ring, capture, copy stream, held log
+//   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
 #pragma once
 #include "engine_base.h"
 #include "march_plan.h"
+#include "snapshot_plan.h"
 
 #include "boundary_kernels.hip.h"
 #include "pair_kernels.hip.h"
 #include "stream_kernels.hip.h"
 #include "plane_kernels.hip.h"
+#include "snapshot_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
 namespace wv {
@@ -147,6 +151,11 @@ public:
     int set_coefficients(const wv_coefficients_canonical* c, uint32_t n) override;
     int device_buffer(int buffer_id, void** p) override;
     int checkpoint(int op) override;
+    // ---- engine_snapshot.hip.h
+    int set_snapshots(const wv_snapshot_plan* plan) override;
+    int snapshot_count(uint64_t* taken, uint64_t* first_held) override;
+    int fetch_snapshots(uint64_t first, uint64_t n, float* dst, uint64_t* steps) override;
+    bool snapshots_active() const override { return snap_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -346,7 +355,48 @@ private:
         size_t recv_log_size = 0;
         uint32_t n_recv = 0;
         int outside_dirty = 0;
+        uint64_t snap_generation = 0, snap_taken = 0, snap_next = 0;  // the snapshot plan's position (engine_snapshot.hip.h)
     } ckpt_;
+    // field snapshots (engine_snapshot.hip.h): a ring of device slots the capture kernel fills on the compute stream, each copied to its
+    // page-locked twin on a stream of its own, and the log of the snapshots the host holds
+    static constexpr int kSnapSlots = 4;
+    struct Snapshots {
+        bool active = false, wide = false;
+        wv_snapshot_plan plan{};
+        wv::SnapshotBox box;
+        uint64_t generation = 0;        // bumped by every wv_set_snapshots (a checkpoint remembers which plan it saw)
+        uint64_t set_at = 0;            // step count when the plan was set
+        uint64_t next = wv::kNoSnapshotStep;  // the next snapshot step not yet captured
+        uint64_t batch_end = wv::kNoSnapshotStep;  // the snapshot step at which the batch being planned ends at the latest
+        uint64_t taken = 0;             // snapshots that reached the held log since the plan was set
+        uint64_t first_taken_step = 0;  // the step of snapshot 0
+        uint64_t bytes = 0;             // bytes captured
+        double kernel_ms = 0;           // capture kernels' time (kernel timing on)
+        uint64_t elems = 0;             // floats per snapshot
+        int slots = 0, head = 0;        // ring size (2 .. kSnapSlots), the slot the next capture takes
+        size_t committed = 0;           // pending captures that are of committed steps (those of earlier batches)
+        float* dev[kSnapSlots] = {nullptr, nullptr, nullptr, nullptr};
+        float* host[kSnapSlots] = {nullptr, nullptr, nullptr, nullptr};
+        hipEvent_t begun[kSnapSlots] = {nullptr, nullptr, nullptr, nullptr};     // before the capture kernel (kernel timing)
+        hipEvent_t captured[kSnapSlots] = {nullptr, nullptr, nullptr, nullptr};  // behind it: hands the slot to the copy stream
+        hipEvent_t copied[kSnapSlots] = {nullptr, nullptr, nullptr, nullptr};    // the slot is on the host and may be filled again
+        bool used[kSnapSlots] = {false, false, false, false}, timed[kSnapSlots] = {false, false, false, false};
+        hipStream_t copy_stream = nullptr;
+        struct Pending {
+            int slot;
+            uint64_t step;
+        };
+        std::deque<Pending> pending;    // captures enqueued, oldest first, not yet in the log
+        std::vector<std::vector<float>> spare;  // memory of dropped snapshots, for the next ones
+        std::deque<std::pair<uint64_t, std::vector<float>>> held;  // (step, floats), oldest first: snapshots taken - held.size() .. taken - 1
+    } snap_;
+    static void snapshot_release(Snapshots& s);
+    int snapshot_capture(uint64_t step);
+    int snapshot_harvest(bool wait, size_t limit = ~size_t{0});
+    void snapshot_discard_after(uint64_t last_good_step);
+    int snapshot_plan_batch();
+    int snapshot_begin_run();
+    void snapshot_rollback(uint64_t to_step);
 };
 
 }  // namespace wv

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <limits>
 #include <memory>
 #include <string>
@@ -86,6 +87,10 @@ struct wv_engine {
     virtual int set_coefficients(const wv_coefficients_canonical* c, uint32_t n) = 0;
     virtual int device_buffer(int buffer, void** p) = 0;
     virtual int checkpoint(int op) = 0;  // 0 save, 1 restore, 2 drop (wv_checkpoint / wv_rollback / wv_drop_checkpoint)
+    virtual int set_snapshots(const wv_snapshot_plan* plan) = 0;
+    virtual int snapshot_count(uint64_t* taken, uint64_t* first_held) = 0;
+    virtual int fetch_snapshots(uint64_t first, uint64_t n, float* dst, uint64_t* steps) = 0;
+    virtual bool snapshots_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;
     virtual int set_source(int kind, uint64_t node, const double* signal, uint64_t n) = 0;

@@ -143,6 +143,9 @@ uint64_t Engine<Real>::plan_batch(uint64_t remaining) {
         const uint64_t left = signal_len_ - std::min(signal_len_, signal_pos_);
         batch = std::min(batch, left);
     }
+    // a snapshot step is the end of a pass, and a batch holds no more captures than the ring has free slots (snapshot_plan.h;
+    // snapshot_plan_batch has set where this batch must end at the latest)
+    if (snap_.active) batch = wv::snapshot_batch_limit(batch, steps_done, snap_.batch_end);
     batch_can_fuse_ = !comm_ && io_nodes_plain() && opt_.tuning.fuse_pre_post != 0;
     (void)whole_step_ready();  // (looks at the class map once per source / receiver set: here, not inside a capture)
     batch_source_live_ = source_kind_ != WV_SOURCE_NONE;
@@ -234,7 +237,17 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
     int32_t flag = 0;
     const bool chain = comm_ && !comm_->is_local();  // (a one-rank communicator agrees with itself: the loopback test runs this)
     std::string cerr;
+    // a snapshot of the step the engine stands at is taken before the first batch (engine_snapshot.hip.h)
+    if (snap_.active) {
+        const int rc = snapshot_begin_run();
+        if (rc) return rc;
+    }
     while (completed < n_steps && flag == 0) {
+        // where this batch ends: it may hold captures for half the snapshot ring
+        if (snap_.active) {
+            const int rc = snapshot_plan_batch();
+            if (rc) return rc;
+        }
         uint64_t batch = plan_batch(n_steps - completed);
         int eligible = 0, rc = batch_pair_eligible(&eligible);
         if (rc) return rc;
@@ -303,10 +316,18 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
                     batch_flags_reset_ = true;
                 }
             }
-            auto triple_at = [&](uint64_t i) { return triples && i >= (uint64_t)singles_first && i + 3 <= batch; };
-            auto pair_at = [&](uint64_t i) { return pairs && !triple_at(i) && i >= (uint64_t)singles_first && i + 2 <= batch; };
+            // A snapshot step inside the batch ends a SEGMENT: no pass reaches across it (a pass holds the steps inside it in no whole
+            // field) and nothing of the step behind it rides in the launch before it (the capture must see the step as wv_read_planes
+            // would); the capture is enqueued between the two passes.  Without a plan the one segment is the batch.
+            uint64_t seg_end = batch;
+            auto next_segment = [&] {
+                seg_end = (snap_.active && snap_.next > steps_done && snap_.next - steps_done < batch) ? snap_.next - steps_done : batch;
+            };
+            next_segment();
+            auto triple_at = [&](uint64_t i) { return triples && i >= (uint64_t)singles_first && i + 3 <= seg_end; };
+            auto pair_at = [&](uint64_t i) { return pairs && !triple_at(i) && i >= (uint64_t)singles_first && i + 2 <= seg_end; };
             // (a three-step pass serves its own first step's source / receiver work unless the launch before it has: as a single step would)
-            auto kind_at = [&](uint64_t i) { return i >= batch ? 0 : (pair_at(i) ? 2 : 1); };
+            auto kind_at = [&](uint64_t i) { return i >= seg_end ? 0 : (pair_at(i) ? 2 : 1); };
             for (uint64_t i = 0; i < batch;) {
                 if (triple_at(i)) {
                     if (comm_) {
@@ -324,12 +345,26 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
                     if ((rc = enqueue_batch_step(i, batch, kind_at(i + 1)))) return rc;
                     i += 1;
                 }
+                if (i == seg_end && i < batch) {  // (the capture at the batch's end follows below, for every form)
+                    if ((rc = snapshot_capture(snap_.next))) return rc;
+                    next_segment();
+                }
             }
         }
+        // the batch ends on a snapshot step: the capture goes directly behind the pass (or the replayed graph) that produced it
+        if (snap_.active && steps_done + batch == snap_.next && (rc = snapshot_capture(snap_.next))) return rc;
+        // captures of EARLIER batches whose copies have landed go into the held log now, while this batch keeps the device busy
+        if (snap_.active && (rc = snapshot_harvest(false, snap_.committed))) return rc;
         if ((rc = collect_batch(batch))) return rc;
         uint64_t good = 0;
         if ((rc = commit_batch(batch, flags_host_, &good, &flag))) return rc;
+        if (snap_.active && good < batch) snapshot_discard_after(steps_done);  // (a flag stopped the run before those steps)
         completed += good;
+    }
+    // on return every snapshot of a completed step can be fetched
+    if (snap_.active) {
+        const int rc = snapshot_harvest(true);
+        if (rc) return rc;
     }
     if (done) *done = completed;
     if (flag_out) *flag_out = flag;
@@ -401,6 +436,9 @@ int Engine<Real>::query(int what, uint64_t* value) {
         case WV_QUERY_TRIPLE_PARTS_TIMED: *value = std::min(part_n_[2], part_n_[3]); return WV_OK;
         case WV_QUERY_TRIPLE_MARCH_NS: *value = (uint64_t)(part_ms_[4] * 1e6 + 0.5); return WV_OK;
         case WV_QUERY_TRIPLE_MARCH_TIMED: *value = part_n_[4]; return WV_OK;
+        case WV_QUERY_SNAPSHOT_NS: *value = (uint64_t)(snap_.kernel_ms * 1e6 + 0.5); return WV_OK;
+        case WV_QUERY_SNAPSHOT_BYTES: *value = snap_.bytes; return WV_OK;
+        case WV_QUERY_SNAPSHOTS_TAKEN: *value = snap_.taken; return WV_OK;
         default: return fail(WV_E_INVALID_ARGUMENT, "unknown query");
     }
 }

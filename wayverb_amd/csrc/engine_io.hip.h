@@ -378,6 +378,9 @@ int Engine<Real>::checkpoint(int op) {
         ckpt_.recv_log_size = recv_log_.size();
         ckpt_.n_recv = n_recv_;
         ckpt_.outside_dirty = outside_dirty_;
+        ckpt_.snap_generation = snap_.generation;
+        ckpt_.snap_taken = snap_.taken;
+        ckpt_.snap_next = snap_.next;
         ckpt_.valid = true;
         return WV_OK;
     }
@@ -393,6 +396,7 @@ int Engine<Real>::checkpoint(int op) {
     steps_done = ckpt_.steps_done;
     signal_pos_ = ckpt_.signal_pos;
     recv_log_.resize(ckpt_.recv_log_size);
+    if (snap_.active) snapshot_rollback(ckpt_.steps_done);  // the snapshots of the abandoned steps go; the re-run takes them again
     outside_dirty_ = std::max(outside_dirty_, ckpt_.outside_dirty);  // (steps taken since may have cleaned the outside nodes: the copies have not)
     xw_valid_ = false;  // the x-facing walls' compact copies hold the abandoned steps' values
     pre_post_done_ = pair_mid_done_ = pair_list_done_ = false;

@@ -542,6 +542,7 @@ void Engine<Real>::release() {
     }
     comm_.reset();
     if (stream_) (void)hipStreamSynchronize(stream_);
+    snapshot_release(snap_);
     for (auto& e : events_) (void)hipEventDestroy(e);
     events_.clear();
     for (auto& e : halo_events_)

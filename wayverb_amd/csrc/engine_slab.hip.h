@@ -101,6 +101,10 @@ inline int group_run(wv_engine* const* engines, int32_t n, uint64_t n_steps, uin
     if (!engines || n < 1) return fail(WV_E_INVALID_ARGUMENT, "no engines");
     for (int i = 0; i < n; ++i)
         if (!engines[i]) return fail(WV_E_INVALID_ARGUMENT, "null engine");
+    // (snapshots are taken by wv_run on one domain: a group would cut its batches at the plan's steps and capture nothing)
+    for (int k = 0; k < n; ++k)
+        if (engines[k]->snapshots_active())
+            return fail(WV_E_STATE, "wv_run_group takes no snapshots: an engine with a snapshot plan is stepped with wv_run (wv_set_snapshots(e, NULL) stops the plan)");
     // lockstep needs the slabs in the same state: the same field buffer in the same role after the same number of steps
     // (exchanges address the neighbour's buffer by index)
     for (int k = 1; k < n; ++k)

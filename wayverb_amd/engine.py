@@ -34,7 +34,7 @@ EXPORTS = [
     "wv_frequency_domain_filter", "wv_postprocess_waveguide", "wv_hrtf_attenuation", "wv_hrtf_ear_position",
     "wv_attenuate_hrtf", "wv_multiband_filter_and_mixdown", "wv_postprocess_waveguide_hrtf", "wv_scene_mesh_create", "wv_scene_mesh_fetch",
     "wv_scene_mesh_create_engine", "wv_scene_mesh_destroy", "wv_checkpoint", "wv_rollback", "wv_drop_checkpoint", "wv_host_register", "wv_host_unregister",
-    "wv_compressed_waveguide_run", "wv_make_transparent",
+    "wv_compressed_waveguide_run", "wv_make_transparent", "wv_set_snapshots", "wv_snapshot_count", "wv_fetch_snapshots",
 ]
 
 
@@ -62,6 +62,13 @@ class WvOptions(C.Structure):
                 ("ghost_lo", C.c_int32), ("ghost_hi", C.c_int32), ("flag_interval", C.c_int32),
                 ("stream_variant", C.c_int32), ("all_tiles", C.c_int32), ("nodes_on_device", C.c_int32), ("comm_timeout_s", C.c_int32), ("transport", C.c_int32), ("reserved_", C.c_int32 * 5),
                 ("tuning", WvTuning)]
+
+
+class WvSnapshotPlan(C.Structure):
+    """wv_snapshot_plan (include/wayverb_amd.h): a box of the mesh, a stride per axis, a cadence in steps."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("sx", C.c_int32), ("sy", C.c_int32), ("sz", C.c_int32), ("first_step", C.c_uint64), ("period", C.c_uint64),
+                ("keep", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 # Tuning applied to every engine this module creates unless the call says otherwise: {field of wv_tuning: value}, plus
@@ -163,6 +170,9 @@ def load_library():
     lib.wv_comm_init_local.argtypes = [C.POINTER(C.c_void_p), C.c_int32]
     lib.wv_run_group.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     lib.wv_make_box_nodes.argtypes = [C.c_int32] * 7 + [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.wv_set_snapshots.argtypes = [C.c_void_p, C.POINTER(WvSnapshotPlan)]
+    lib.wv_snapshot_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.wv_fetch_snapshots.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -332,6 +342,7 @@ class Engine:
         _check(self.lib.wv_create(C.byref(wm), C.byref(opt), C.byref(handle)))
         self.h = handle
         self.n_recv = 0
+        self.snapshot_shape = None
 
     @classmethod
     def from_handle(cls, handle, mesh, precision):
@@ -343,6 +354,7 @@ class Engine:
         eng.dtype = np.float32 if precision == "f32" else np.float64
         eng.h = handle
         eng.n_recv = 0
+        eng.snapshot_shape = None
         return eng
 
     def close(self):
@@ -457,6 +469,54 @@ class Engine:
             _check(self.lib.wv_fetch_receivers(self.h, first, n, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # ---- field snapshots taken on the device while wv_run goes on ---------------------------------
+    def set_snapshots(self, box="mesh", stride=1, first_step=0, period=1, keep=0):
+        """wv_set_snapshots.  `box` = ((x0, y0, z0), (ex, ey, ez)): first node and extent in NODES OF THE MESH ("mesh": the whole mesh;
+        an extent of None: up to the mesh's far face); `stride` = s or (sx, sy, sz): every s-th node of the box is taken, the first
+        included, so an axis yields ceil(extent / s) nodes.  Snapshots at steps first_step + j * period; the host holds the last
+        `keep` (0: all).  A snapshot of step s is the field after s completed steps -- what read_planes returns at step_count() == s;
+        the source's sample of step s is not in it yet (the loop puts it into its node after the snapshot is taken, before the
+        update).  set_snapshots(None) stops recording and forgets what is held.  Returns the shape
+        (nz, ny, nx) of one snapshot."""
+        if box is None:
+            _check(self.lib.wv_set_snapshots(self.h, None))
+            self.snapshot_shape = None
+            return None
+        dims = self.mesh.dims
+        origin, extent = ((0, 0, 0), None) if isinstance(box, str) and box == "mesh" else box
+        extent = tuple(extent) if extent is not None else (None, None, None)
+        stride = (stride,) * 3 if np.isscalar(stride) else tuple(stride)
+        plan = WvSnapshotPlan()
+        taken = []
+        for axis in range(3):
+            ext = dims[axis] - origin[axis] if extent[axis] is None else extent[axis]
+            s = int(stride[axis])
+            taken.append((int(ext) + s - 1) // s if s >= 1 and ext >= 1 else 0)   # (a bad stride or extent is the library's to refuse)
+        plan.x0, plan.y0, plan.z0 = (int(v) for v in origin)
+        plan.nx, plan.ny, plan.nz = taken
+        plan.sx, plan.sy, plan.sz = (int(v) for v in stride)
+        plan.first_step, plan.period, plan.keep = int(first_step), int(period), int(keep)
+        _check(self.lib.wv_set_snapshots(self.h, C.byref(plan)))
+        self.snapshot_shape = (taken[2], taken[1], taken[0])
+        return self.snapshot_shape
+
+    def snapshot_count(self):
+        """wv_snapshot_count: (snapshots taken since the plan was set, index of the oldest one still held)."""
+        taken, first = C.c_uint64(), C.c_uint64()
+        _check(self.lib.wv_snapshot_count(self.h, C.byref(taken), C.byref(first)))
+        return taken.value, first.value
+
+    def fetch_snapshots(self, first=None, n=None):
+        """wv_fetch_snapshots: snapshots [first, first + n) as (float32[n, nz, ny, nx], steps uint64[n]); by default all that are held."""
+        if first is None or n is None:
+            taken, first_held = self.snapshot_count()
+            first = first_held if first is None else first
+            n = taken - first if n is None else n
+        out = np.empty((n,) + tuple(self.snapshot_shape or (0, 0, 0)), dtype=np.float32)   # (no plan: the library says so)
+        steps = np.empty(n, dtype=np.uint64)
+        _check(self.lib.wv_fetch_snapshots(self.h, int(first), int(n), out.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p)))
+        return out, steps
+
     def step_count(self):
         s = C.c_uint64()
         _check(self.lib.wv_step_count(self.h, C.byref(s)))
@@ -485,6 +545,7 @@ class Engine:
     QUERY_WHOLE_STEPS = 14
     QUERY_TRIPLE_PASSES = 15
     QUERY_TRIPLE_MARCH_NS, QUERY_TRIPLE_MARCH_TIMED, QUERY_BOUNDARY3_NS, QUERY_FIXUP3_NS, QUERY_TRIPLE_PARTS_TIMED = 16, 17, 18, 19, 20
+    QUERY_SNAPSHOT_NS, QUERY_SNAPSHOT_BYTES, QUERY_SNAPSHOTS_TAKEN = 21, 22, 23
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

@@ -108,13 +108,20 @@ def compute_voxels_and_mesh(vertices, triangles, surface_absorptions, anchor, sa
 
 
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
-              device=-1, keep_going=lambda: True, slabs=1, devices=None):
+              device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None):
     """canonical (single band): hard source at `source`, directional receiver at `receiver`, for
     ceil(sample_rate * simulation_time) steps.  Returns [(directional records, sample_rate,
     (0, cutoff))] -- the bandpass_band list waveguide::postprocess takes -- or None when stopped early.
     `precision`: "f32" is the reference's pressure type; "f64" the fp64 engine.
     `slabs` > 1: the mesh is cut into that many z-slabs, on the GPUs in `devices` (BASELINE configs[4], "1 -> 8
-    GPUs"; engine.run_fast_slabs) -- same records, bit for bit."""
+    GPUs"; engine.run_fast_slabs) -- same records, bit for bit.
+    `snapshots`: keyword arguments of Engine.set_snapshots (box, stride, first_step, period, keep) -- the engine records that part
+    of the field on the device while the run goes on (what the reference's visualiser takes from the per-step callback,
+    src/combined/src/engine.cpp:158-169); the return value is then (bands, (float32[n, nz, ny, nx], steps[n])), or None when stopped
+    early.  A snapshot of step s is the field after s completed steps: the hard source's sample of step s, which the reference's
+    callback finds in the source node, is not in it yet (the C++ mirror, cl_mirror_cadence(), puts it there).  One domain only."""
+    if snapshots is not None and slabs > 1:
+        raise ValueError("snapshots are taken on one domain only (slabs=1)")
     mesh = vm.mesh
     sample_rate = compute_sample_rate(mesh.spacing, environment.speed_of_sound)
 
@@ -139,14 +146,18 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     else:
         eng = E.Engine(mesh, precision=precision, device=device)
         try:
+            if snapshots is not None:
+                eng.set_snapshots(**snapshots)
             done, traces = E.run_fast(eng, E.SOURCE_HARD, mesh_index(source), signal, [receiver_index] + list(neighbours),
                                       keep_going=keep_going)
+            taken = eng.fetch_snapshots() if snapshots is not None else None
         finally:
             eng.close()
     if done != ideal_steps:
         return None
     directional = P.directional_receiver(traces, mesh.spacing, sample_rate, environment.ambient_density)
-    return [(directional, sample_rate, (0.0, float(cutoff)))]
+    bands = [(directional, sample_rate, (0.0, float(cutoff)))]
+    return bands if snapshots is None else (bands, taken)
 
 
 def band_edges_hz(bands=8, lo=20.0, hi=20000.0):
@@ -183,11 +194,21 @@ def canonical_multiband(vm, source, receiver, environment, bands, cutoff, usable
 
 def impulse_response(vertices, triangles, surface_absorptions, source, receiver, cutoff=200.0, usable_portion=0.6,
                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
-                     pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1):
-    """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio."""
+                     pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None):
+    """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio.
+    `snapshots`: a function mesh -> keyword arguments of Engine.set_snapshots (the mesh's size is not known before it is built),
+    or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member."""
     environment = environment or Environment()
     vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
-    bands = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device)
+    if snapshots is None:
+        bands = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device)
+        taken = None
+    else:
+        plan = snapshots(vm.mesh) if callable(snapshots) else snapshots
+        both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, snapshots=plan)
+        if both is None:
+            raise RuntimeError("the waveguide run was stopped early")
+        bands, taken = both
     audio = P.postprocess(bands, method, pointing, shape, environment.acoustic_impedance, output_sample_rate)
-    return audio, bands, vm
+    return (audio, bands, vm) if snapshots is None else (audio, bands, vm, taken)
