@@ -256,6 +256,30 @@ int wv_run(wv_engine* e, uint64_t n_steps, uint64_t* steps_done, int32_t* flag);
 /* Receiver samples of steps [first, first+n) as double[n][num_receivers]; steps driven by wv_step / wv_swap
  * record nothing (their rows are NaN). */
 int wv_fetch_receivers(wv_engine* e, uint64_t first, uint64_t n, double* dst);
+/* R directional receivers (postprocessor::directional_receiver, src/waveguide/src/postprocessor/directional_receiver.cpp:10-69)
+ * recorded AND integrated on the device: one run of the mesh serves every listener in the room (the reference's application runs the
+ * whole mesh once per source-receiver pair, src/combined/src/threaded_engine.cpp:155-162).  nodes[i] is the centre node of receiver
+ * i; its six neighbours are compute_neighbors' (nx, px, ny, py, nz, pz).  Internally the 7 * n columns (per receiver the centre, then
+ * ports 0..5) are recorded as wv_set_receivers records them; at the end of every batch of wv_run a kernel integrates them, one lane per
+ * receiver, with the arithmetic of directional_receiver::operator() operation for operation, and only the {intensity, pressure}
+ * records (16 B per receiver and step where the raw columns are 56) come to the host.  The records of n receivers are bit-identical
+ * to those of n runs with one receiver each.
+ *   - a centre with a neighbour off the grid: WV_E_INVALID_ARGUMENT, "Can't place directional_receiver at this node as it is adjacent
+ *     to a boundary." (directional_receiver.cpp:21-27); the engine keeps what it had (everything is allocated before anything changes)
+ *   - records of completed steps are always fetchable; after a run that stopped on a flag the velocities are as meaningless as the fields
+ *   - steps taken by wv_step / wv_swap record NaN rows and leave the velocities alone
+ *   - wv_checkpoint copies the velocities and the log's length aside, wv_rollback puts both back
+ *   - wv_set_receivers, or wv_set_directional_receivers(e, NULL, 0, ...), leaves the mode; in it wv_fetch_receivers answers WV_E_STATE
+ *     (and wv_fetch_directional answers WV_E_STATE outside it)
+ *   - a slab of a chain (ghost planes, or a communicator of more than one rank) answers WV_E_STATE: a receiver next to a cut has a
+ *     neighbour in a ghost plane, and nothing pins the reading of ghost planes by receivers in every form of pass.  Chains record the
+ *     7 * n columns with wv_set_receivers and integrate them with wv_directional_accumulate (below): the same records, bit for bit.
+ * wv_fetch_directional: records of steps [first, first + n) as wv_directional_output[n][R] (the struct is declared with the host-side
+ * post-processing below). */
+struct wv_directional_output;
+int wv_set_directional_receivers(wv_engine* e, const uint64_t* nodes, uint32_t n, double spacing, double sample_rate,
+                                 double ambient_density);
+int wv_fetch_directional(wv_engine* e, uint64_t first, uint64_t n, struct wv_directional_output* dst /* [n][R] */);
 /* Number of loop iterations completed since creation. */
 int wv_step_count(wv_engine* e, uint64_t* steps);
 
@@ -329,7 +353,10 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *   WV_QUERY_EARLY_PASSES    two-step passes of a slab that ran both exchanges under the march (wv_tuning::slab_early)
  *   WV_QUERY_TRIPLE_PASSES   three-step passes taken since creation (wv_tuning::triple)
  *   WV_QUERY_SNAPSHOT_NS, WV_QUERY_SNAPSHOT_BYTES, WV_QUERY_SNAPSHOTS_TAKEN   since wv_set_snapshots: total time of the capture kernels
- *                            that ran with kernel timing on, bytes captured, snapshots taken */
+ *                            that ran with kernel timing on, bytes captured, snapshots taken
+ *   WV_QUERY_WIDE_GATHERS    steps whose receivers (more than 64 columns) were gathered by a launch of their own, one lane per
+ *                            column, since creation (receiver_kernels.hip.h); 0 for ever with 64 columns or fewer
+ *   WV_QUERY_DIRECTIONAL_LAUNCHES   launches of the directional receivers' integrator since creation (one per batch of wv_run) */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -344,7 +371,8 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
         * (WV_QUERY_BOUNDARY1_NS / 2_NS count the first two boundary launches of either kind of pass) */
        WV_QUERY_TRIPLE_MARCH_NS = 16, WV_QUERY_TRIPLE_MARCH_TIMED = 17, WV_QUERY_BOUNDARY3_NS = 18, WV_QUERY_FIXUP3_NS = 19,
        WV_QUERY_TRIPLE_PARTS_TIMED = 20,
-       WV_QUERY_SNAPSHOT_NS = 21, WV_QUERY_SNAPSHOT_BYTES = 22, WV_QUERY_SNAPSHOTS_TAKEN = 23 };
+       WV_QUERY_SNAPSHOT_NS = 21, WV_QUERY_SNAPSHOT_BYTES = 22, WV_QUERY_SNAPSHOTS_TAKEN = 23,
+       WV_QUERY_WIDE_GATHERS = 24, WV_QUERY_DIRECTIONAL_LAUNCHES = 25 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);
@@ -522,6 +550,12 @@ typedef struct wv_directional_output {
     float intensity[3];
     float pressure;
 } wv_directional_output;
+/* The integrator of wv_set_directional_receivers on the host, for columns that come from somewhere else (a chain of slabs records
+ * columns): p7[n][7] = the centre and its neighbours (nx, px, ny, py, nz, pz) per step, as wv_fetch_receivers delivers them;
+ * velocity[3] is read and advanced (zeros before the first call), so a trace may be fed in pieces; out[n] receives the records.
+ * directional_receiver.cpp:29-67: float pressure differences, a double velocity. */
+int wv_directional_accumulate(const double* p7 /* [n][7] */, uint64_t n, double spacing, double sample_rate, double ambient_density,
+                              double velocity[3] /* in, out */, wv_directional_output* out /* [n] */);
 /* bandpass_band (src/waveguide/include/waveguide/bandpass_band.h:11-20) */
 typedef struct wv_waveguide_band {
     const wv_directional_output* directional;

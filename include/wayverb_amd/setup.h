@@ -252,6 +252,29 @@ std::experimental::optional<std::vector<bandpass_band>> canonical(
     return ret;
 }
 
+/// The same for many receivers: one run per band, ALL receivers in each (detail::canonical_many_impl).  ret[r] is what the overload
+/// above returns for receivers[r] alone: its bands in order.  `progress(step, steps)`: progress only.
+template <typename Context, typename Vec3, typename Receivers, typename Environment, typename Progress>
+std::experimental::optional<std::vector<std::vector<bandpass_band>>> canonical_many(
+        const Context& cc, voxels_and_mesh voxelised, const Vec3& source, const Receivers& receivers,
+        const Environment& environment, const multiple_band_constant_spacing_parameters& sim_params,
+        double simulation_time, const std::atomic_bool& keep_going, Progress&& progress) {
+    const auto edges = band_edges_hz();
+    std::vector<std::vector<bandpass_band>> ret;
+    for (size_t band = 0; band != sim_params.bands; ++band) {
+        set_flat_coefficients_for_band(voxelised, band);
+        if (auto rendered = detail::canonical_many_impl(cc, voxelised.mesh, simulation_time, source, receivers, environment,
+                                                        keep_going, progress)) {
+            if (ret.empty()) ret.resize(rendered->size());
+            for (size_t r = 0; r < rendered->size(); ++r)
+                ret[r].push_back(bandpass_band{std::move((*rendered)[r]), util::make_range(edges[band], edges[band + 1])});
+        } else {
+            return std::experimental::nullopt;
+        }
+    }
+    return ret;
+}
+
 // ---- receiver traces -> audio ------------------------------------------------------------------------
 namespace detail {
 inline std::vector<wv_directional_output> to_abi(const band& b) {

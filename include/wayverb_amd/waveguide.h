@@ -1165,6 +1165,95 @@ std::experimental::optional<band> canonical_impl(const Context& cc, const Mesh& 
     if (steps != ideal_steps) return std::experimental::nullopt;
     return ret;
 }
+
+/// canonical.h:29-88 for MANY receivers out of ONE run of the mesh: the reference's application runs the whole mesh once per
+/// source-receiver pair (src/combined/src/threaded_engine.cpp:155-162) although a run costs the same however many points listen.
+/// `receivers` is any range of positions; the result holds one `band` per receiver, in order, each bit-identical to what
+/// `canonical_impl` returns for that receiver alone; nullopt when cancelled.  The input is the hard source with the calibrated impulse,
+/// the receivers are recorded and integrated on the device (wv_set_directional_receivers), in batches bounded as run_device's are.
+/// Errors are canonical_impl's, per receiver ("Source/receiver node position appears to be outside mesh.", "Can't place
+/// directional_receiver at this node as it is adjacent to a boundary.").
+/// `progress(step, ideal_steps)` fires once per completed step, in order.  It is PROGRESS ONLY: there is no field handle, so the
+/// speculate / rollback machinery of run_device_observed is not involved -- a caller that must see the field runs `canonical`.
+template <typename Context, typename Mesh, typename Vec3, typename Receivers, typename Environment, typename Progress>
+std::experimental::optional<std::vector<band>> canonical_many_impl(const Context& cc, const Mesh& mesh, double simulation_time,
+                                                                   const Vec3& source, const Receivers& receivers,
+                                                                   const Environment& environment, const std::atomic_bool& keep_going,
+                                                                   Progress&& progress, size_t batch = 256) {
+    const auto sample_rate = compute_sample_rate(mesh.get_descriptor(), environment.speed_of_sound);
+    const size_t num_nodes = mesh.get_structure().get_condensed_nodes().size();
+    const auto compute_mesh_index = [&](const Vec3& pt) {
+        const auto ret = compute_index(mesh.get_descriptor(), pt);
+        if (ret >= num_nodes || !(mesh.get_structure().get_condensed_nodes()[ret].boundary_type & WV_ID_INSIDE))
+            throw std::runtime_error{"Source/receiver node position appears to be outside mesh."};
+        return ret;
+    };
+    const size_t ideal_steps = (size_t)std::ceil(sample_rate * simulation_time);
+    std::vector<double> signal(ideal_steps, 0.0);
+    if (!signal.empty())
+        signal.front() = (double)(float)rectilinear_calibration_factor(mesh.get_descriptor().spacing, environment.acoustic_impedance);
+    const double ambient_density = environment.acoustic_impedance / environment.speed_of_sound;
+    std::vector<uint64_t> centres;
+    for (const auto& receiver : receivers) {
+        const size_t index = compute_mesh_index(receiver);
+        // (the constructor throws for a node next to the mesh's edge, as it does in canonical_impl)
+        const postprocessor::directional_receiver dr{mesh.get_descriptor(), sample_rate, ambient_density, index};
+        centres.push_back(dr.get_output_node());
+    }
+    const size_t source_index = compute_mesh_index(source);
+    std::vector<band> ret(centres.size(), band{{}, sample_rate});
+    if (centres.empty()) return ret;
+    for (auto& b : ret) b.directional.reserve(ideal_steps);
+
+    auto engine = make_engine(cc, mesh, default_precision());
+    wv_engine* e = engine.get();
+    check(wv_set_source(e, WV_SOURCE_HARD, source_index, signal.data(), signal.size()));
+    check(wv_set_directional_receivers(e, centres.data(), (uint32_t)centres.size(), (double)mesh.get_descriptor().spacing, sample_rate,
+                                       ambient_density));
+    run_stats& stats = last_run_stats();
+    stats = run_stats{};
+    const double t0 = seconds_now();
+    size_t done_total = 0;
+    struct at_exit final {  // (also when a flag or the callback throws)
+        run_stats& stats;
+        wv_engine* e;
+        const size_t& done_total;
+        double t0;
+        ~at_exit() {
+            uint64_t passes = 0;
+            if (wv_query(e, WV_QUERY_PASSES, &passes) == WV_OK) stats.passes = passes;
+            stats.steps = done_total;
+            stats.seconds = seconds_now() - t0;
+        }
+    } finish{stats, e, done_total, t0};
+    std::vector<wv_directional_output> records;
+    double step_seconds = 0;  // of the batch before (the first batch is a short one that finds out)
+    while (done_total < ideal_steps && keep_going) {
+        const uint64_t want = std::min<uint64_t>(std::min<uint64_t>(batch, steps_within_budget(step_seconds, 8)), ideal_steps - done_total);
+        uint64_t done = 0;
+        int32_t flag = 0;
+        const double t_batch = seconds_now();
+        check(wv_run(e, want, &done, &flag));
+        if (done) {
+            step_seconds = (seconds_now() - t_batch) / (double)done;
+            ++stats.batches;
+            records.resize((size_t)done * centres.size());
+            check(wv_fetch_directional(e, done_total, done, records.data()));
+            for (size_t i = 0; i < (size_t)done; ++i) {
+                for (size_t r = 0; r < centres.size(); ++r) {
+                    const wv_directional_output& o = records[i * centres.size() + r];
+                    ret[r].directional.push_back({vec3{o.intensity[0], o.intensity[1], o.intensity[2]}, o.pressure});
+                }
+                progress(done_total + i, ideal_steps);
+            }
+        }
+        done_total += (size_t)done;
+        throw_for_flag(flag);
+        if (done < want) break;
+    }
+    if (done_total != ideal_steps) return std::experimental::nullopt;
+    return ret;
+}
 }  // namespace detail
 
 /// canonical.h:100-127 for an already-built mesh.
@@ -1192,6 +1281,28 @@ auto canonical(const Context& cc, VoxelsAndMesh voxelised, const Vec3& source, c
         return std::vector<bandpass_band>{bandpass_band{std::move(*ret), util::make_range(0.0, sim_params.cutoff)}};
     }
     return std::experimental::nullopt;
+}
+
+/// canonical for many receivers out of one run of an already-built mesh (or of anything with a `.mesh` member): one bandpass_band
+/// per receiver, in the receivers' order, each what `canonical` returns for that receiver alone, bit for bit.
+/// `progress(step, steps)`: progress only, see detail::canonical_many_impl.
+template <typename Context, typename Vec3, typename Receivers, typename Environment, typename Progress>
+std::experimental::optional<std::vector<bandpass_band>> canonical_many(
+        const Context& cc, const mesh& mesh, const Vec3& source, const Receivers& receivers, const Environment& environment,
+        const single_band_parameters& sim_params, double simulation_time, const std::atomic_bool& keep_going, Progress&& progress) {
+    if (auto ret = detail::canonical_many_impl(cc, mesh, simulation_time, source, receivers, environment, keep_going, progress)) {
+        std::vector<bandpass_band> out;
+        for (auto& b : *ret) out.push_back(bandpass_band{std::move(b), util::make_range(0.0, sim_params.cutoff)});
+        return out;
+    }
+    return std::experimental::nullopt;
+}
+template <typename Context, typename VoxelsAndMesh, typename Vec3, typename Receivers, typename Environment, typename Progress>
+auto canonical_many(const Context& cc, VoxelsAndMesh voxelised, const Vec3& source, const Receivers& receivers,
+                    const Environment& environment, const single_band_parameters& sim_params, double simulation_time,
+                    const std::atomic_bool& keep_going, Progress&& progress)
+        -> decltype((void)voxelised.mesh, std::experimental::optional<std::vector<bandpass_band>>{}) {
+    return canonical_many(cc, voxelised.mesh, source, receivers, environment, sim_params, simulation_time, keep_going, progress);
 }
 
 }  // namespace waveguide

@@ -5,6 +5,8 @@ single-band waveguide at `--cutoff`, microphone or omni capsule, WAV out.
 
     python tools/impulse_response.py --out ir.wav                       # built-in hall
     python tools/impulse_response.py --way demo/evaluation/receivers/concert.way   # a wayverb project bundle
+    python tools/impulse_response.py --receiver 8 20 1.2 --receiver 4 12 1.2 --receiver 14 25 1.2 --out ir.wav
+                                                                        # three listeners, ONE run of the mesh: ir_0.wav ir_1.wav ir_2.wav
     python tools/impulse_response.py --obj concert.obj --source 0 0 0 --receiver 0 1.47 -20.06 \
         --material DefaultMaterial=0.05 --material FrontColor=0.30,0.30,0.45,0.65,0.56,0.59,0.71,0.71
 """
@@ -22,6 +24,17 @@ from wayverb_amd import scene as S  # noqa: E402
 from wayverb_amd import simulation as W  # noqa: E402
 
 
+def write_wav(path, audio, rate):
+    peak = float(np.abs(audio).max()) or 1.0
+    pcm = np.clip(audio / peak * 32767.0, -32768, 32767).astype("<i2")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(rate))
+        w.writeframes(pcm.tobytes())
+    return peak
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--obj")
@@ -29,7 +42,9 @@ def main():
                                     "source / receiver / capsule and the waveguide parameters come from it")
     ap.add_argument("--material", action="append", default=[], help="name=a  or  name=a1,...,a8 (band absorptions)")
     ap.add_argument("--source", type=float, nargs=3, default=[9.0, 3.0, 1.5])
-    ap.add_argument("--receiver", type=float, nargs=3, default=[8.0, 20.0, 1.2])
+    ap.add_argument("--receiver", type=float, nargs=3, action="append", default=None,
+                    help="may be given several times: every receiver listens to the same run of the mesh (the mesh is anchored at "
+                         "the first, the others snap to their nearest node), and --out gets _<i> suffixes (default: 8 20 1.2)")
     ap.add_argument("--cutoff", type=float, default=200.0)
     ap.add_argument("--usable-portion", type=float, default=0.6)
     ap.add_argument("--seconds", type=float, default=2.0)
@@ -49,7 +64,7 @@ def main():
         cfg, v, t, way_absorptions = wayfile.read_way(args.way)
         names = None
         args.source = cfg["sources"][0]["position"]
-        args.receiver = cfg["receivers"][0]["position"]
+        args.receiver = [cfg["receivers"][0]["position"]]
         wg = cfg["waveguide"]
         params = wg["single"] if wg["mode"] == "single" else wg["multiple"]
         args.cutoff, args.usable_portion = params["cutoff"], params["usable_portion"]
@@ -84,8 +99,26 @@ def main():
         def snapshots(mesh):
             return dict(box=((0, 0, plane), (None, None, 1)), period=every)
 
+    receivers = args.receiver or [[8.0, 20.0, 1.2]]
+    args.receiver = receivers[0]
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
+    if len(receivers) > 1:
+        if bands or snapshots is not None:
+            ap.error("several --receiver: single-band runs without --snapshots")
+        audios, per, positions, vm = W.impulse_responses(v, t, absorptions, args.source, receivers, args.cutoff, args.usable_portion,
+                                                         args.seconds, args.rate, method=method, pointing=args.pointing,
+                                                         shape=args.mic_shape or 0.0, precision=args.precision)
+        dt = time.perf_counter() - t0
+        mesh = vm.mesh
+        print("mesh %dx%dx%d (%d nodes, spacing %.4f m), %d steps at %.1f Hz for %d receivers in one run, %.2f s wall"
+              % (mesh.dims + (mesh.num_nodes, mesh.spacing, per[0][0][0].shape[0], per[0][0][1], len(receivers), dt)))
+        stem, ext = os.path.splitext(args.out)
+        for i, (audio, pos) in enumerate(zip(audios, positions)):
+            name = "%s_%d%s" % (stem, i, ext)
+            peak = write_wav(name, audio, args.rate)
+            print("wrote %s: receiver at node position (%.3f, %.3f, %.3f) (normalised, peak was %.3e)" % ((name,) + tuple(pos) + (peak,)))
+        return
     if bands:   # multiple_band_constant_spacing: one run per band with flat per-band walls
         env = W.Environment()
         vm = W.compute_voxels_and_mesh(v, t, absorptions, args.receiver,
@@ -109,13 +142,7 @@ def main():
     mesh = vm.mesh
     print("mesh %dx%dx%d (%d nodes, spacing %.4f m), %d steps at %.1f Hz, %d samples at %.0f Hz, %.2f s wall"
           % (mesh.dims + (mesh.num_nodes, mesh.spacing, bands[0][0].shape[0], bands[0][1], audio.shape[0], args.rate, dt)))
-    peak = float(np.abs(audio).max()) or 1.0
-    pcm = np.clip(audio / peak * 32767.0, -32768, 32767).astype("<i2")
-    with wave.open(args.out, "wb") as w:
-        w.setnchannels(1)
-        w.setsampwidth(2)
-        w.setframerate(int(args.rate))
-        w.writeframes(pcm.tobytes())
+    peak = write_wav(args.out, audio, args.rate)
     print("wrote %s (normalised, peak was %.3e)" % (args.out, peak))
 
 

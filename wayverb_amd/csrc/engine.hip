@@ -14,6 +14,7 @@
 #include "engine_batch.hip.h"
 #include "engine_io.hip.h"
 #include "engine_snapshot.hip.h"
+#include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
 namespace {
@@ -225,6 +226,15 @@ int wv_run(wv_engine* e, uint64_t n_steps, uint64_t* done, int32_t* flag) {
 int wv_fetch_receivers(wv_engine* e, uint64_t first, uint64_t n, double* dst) {
     WV_NEED(e);
     return e->fetch_receivers(first, n, dst);
+}
+int wv_set_directional_receivers(wv_engine* e, const uint64_t* nodes, uint32_t n, double spacing, double sample_rate,
+                                 double ambient_density) {
+    WV_NEED(e);
+    return e->set_directional_receivers(nodes, n, spacing, sample_rate, ambient_density);
+}
+int wv_fetch_directional(wv_engine* e, uint64_t first, uint64_t n, wv_directional_output* dst) {
+    WV_NEED(e);
+    return e->fetch_directional(first, n, dst);
 }
 int wv_step_count(wv_engine* e, uint64_t* steps) {
     WV_NEED(e);

@@ -17,6 +17,7 @@
 //                        receivers
 //   engine_snapshot.hip.h  field snapshots taken on the device while a run goes on (wv_set_snapshots): plan, ring, capture, copy stream, held log
 //   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape
+//   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
 #pragma once
@@ -29,9 +30,15 @@
 #include "stream_kernels.hip.h"
 #include "plane_kernels.hip.h"
 #include "snapshot_kernels.hip.h"
+#include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
 namespace wv {
+
+// (engine_directional.hip.h, engine_slab.hip.h)
+constexpr const char* kDirectionalOnSlab =
+        "directional receivers on the device: not on a slab of a chain (a receiver next to a cut has a neighbour in a ghost plane); "
+        "record the 7 columns per receiver with wv_set_receivers and integrate them with wv_directional_accumulate";
 
 template <typename Real>
 class Engine final : public wv_engine {
@@ -129,6 +136,7 @@ public:
     // ---- engine_io.hip.h
     int set_source(int kind, uint64_t node, const double* signal, uint64_t n) override;
     int set_receivers(const uint64_t* nodes, uint32_t n) override;
+    int set_columns(const uint64_t* nodes, uint32_t n);  // what wv_set_receivers does to the recorded columns, in either mode
     bool io_nodes_plain();
     bool io_nodes(std::vector<uint64_t>* stored);
     bool io_nodes_unfaced();
@@ -151,6 +159,9 @@ public:
     int set_coefficients(const wv_coefficients_canonical* c, uint32_t n) override;
     int device_buffer(int buffer_id, void** p) override;
     int checkpoint(int op) override;
+    // ---- engine_directional.hip.h
+    int set_directional_receivers(const uint64_t* nodes, uint32_t n, double spacing, double sample_rate, double ambient_density) override;
+    int fetch_directional(uint64_t first, uint64_t n, wv_directional_output* dst) override;
     // ---- engine_snapshot.hip.h
     int set_snapshots(const wv_snapshot_plan* plan) override;
     int snapshot_count(uint64_t* taken, uint64_t* first_held) override;
@@ -344,6 +355,23 @@ private:
     uint64_t recv_first_step_ = 0;
     Real* recv_stage_ = nullptr;  // pinned, kRing rows: a copy into pageable memory would make hipMemcpyAsync wait for the stream on the host
     std::vector<double> recv_log_;
+    uint64_t wide_gathers_ = 0;        // steps whose receivers took the wide gather (WV_QUERY_WIDE_GATHERS)
+    uint64_t graph_wide_gathers_ = 0;  // ... by one replay of the captured batch
+    // directional receivers on the device (engine_directional.hip.h): the 7 * n columns are recv_nodes_ / recv_out_ as ever; at the end of
+    // a batch the integrator turns the batch's rows into records, and those travel instead of the rows
+    struct Directional {
+        bool active = false;
+        uint32_t n = 0;
+        double spacing = 0, k = 0;                 // k = ambient_density * sample_rate
+        double* velocity = nullptr;                // device [n][3]
+        wv::DirectionalRecord* dev = nullptr;      // device [kRing][n]
+        wv_directional_output* host = nullptr;     // page-locked [kRing][n]
+        std::vector<wv_directional_output> log;    // records of the completed steps since the receivers were set
+        uint64_t generation = 0;                   // bumped whenever the mode is entered or left (a checkpoint remembers which set it saw)
+        uint64_t launches = 0;                     // WV_QUERY_DIRECTIONAL_LAUNCHES
+    } dir_;
+    void directional_release();
+    int directional_enqueue(uint64_t batch);
     std::unique_ptr<wv::SlabComm> comm_;
     // wv_checkpoint / wv_rollback (engine_io.hip.h): device copies of the two live fields and the filter memories, and the
     // host-side position that goes with them
@@ -356,6 +384,10 @@ private:
         uint32_t n_recv = 0;
         int outside_dirty = 0;
         uint64_t snap_generation = 0, snap_taken = 0, snap_next = 0;  // the snapshot plan's position (engine_snapshot.hip.h)
+        double* dir_velocity = nullptr;  // the directional receivers' velocities (engine_directional.hip.h), their log's length, which set
+        uint32_t dir_n = 0;              // (receivers the copy has room for)
+        size_t dir_log_size = 0;
+        uint64_t dir_generation = 0;
     } ckpt_;
     // field snapshots (engine_snapshot.hip.h): a ring of device slots the capture kernel fills on the compute stream, each copied to its
     // page-locked twin on a stream of its own, and the log of the snapshots the host holds

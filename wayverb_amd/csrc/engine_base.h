@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -97,6 +98,8 @@ struct wv_engine {
     virtual int set_receivers(const uint64_t* nodes, uint32_t n) = 0;
     virtual int run(uint64_t n_steps, uint64_t* done, int32_t* flag) = 0;
     virtual int fetch_receivers(uint64_t first, uint64_t n, double* dst) = 0;
+    virtual int set_directional_receivers(const uint64_t* nodes, uint32_t n, double spacing, double sample_rate, double ambient_density) = 0;
+    virtual int fetch_directional(uint64_t first, uint64_t n, wv_directional_output* dst) = 0;
     virtual int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) = 0;
     virtual int synchronize() = 0;
     virtual int query(int what, uint64_t* value) = 0;

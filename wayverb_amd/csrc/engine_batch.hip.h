@@ -127,7 +127,13 @@ int Engine<Real>::swap() {
     ++steps_done;
     // a step driven from outside (wv_step / wv_swap) records no receiver samples: its row of the log is NaN,
     // so that wv_fetch_receivers keeps addressing rows by step
-    if (n_recv_) recv_log_.insert(recv_log_.end(), n_recv_, std::numeric_limits<double>::quiet_NaN());
+    // (directional receivers: a NaN record per receiver, and the velocities stay as they are)
+    if (dir_.active) {
+        const float nan = std::numeric_limits<float>::quiet_NaN();
+        dir_.log.insert(dir_.log.end(), dir_.n, wv_directional_output{{nan, nan, nan}, nan});
+    } else if (n_recv_) {
+        recv_log_.insert(recv_log_.end(), n_recv_, std::numeric_limits<double>::quiet_NaN());
+    }
     return WV_OK;
 }
 
@@ -187,7 +193,11 @@ int Engine<Real>::collect_batch(uint64_t batch) {
     if (comm_ && !comm_->join_halo(stream_, &cerr)) return fail(WV_E_COMM, cerr);
     if (comm_ && !comm_->or_flags(stream_, flags_, (int)batch, &cerr)) return fail(WV_E_COMM, cerr);
     WV_HIP(hipMemcpyAsync(flags_host_, flags_, batch * sizeof(int), hipMemcpyDeviceToHost, stream_));
-    if (n_recv_) {
+    if (dir_.active) {
+        // the batch's rows become records on the device, and the records travel instead of the rows
+        const int rc = directional_enqueue(batch);
+        if (rc) return rc;
+    } else if (n_recv_) {
         WV_HIP(hipMemcpyAsync(recv_stage_, recv_out_, (size_t)batch * n_recv_ * sizeof(Real), hipMemcpyDeviceToHost, stream_));
     }
     if (comm_ && !comm_->is_local()) {
@@ -215,7 +225,9 @@ int Engine<Real>::commit_batch(uint64_t batch, const int* flags, uint64_t* good_
             break;
         }
     }
-    if (n_recv_)
+    if (dir_.active)
+        dir_.log.insert(dir_.log.end(), dir_.host, dir_.host + (size_t)good * dir_.n);
+    else if (n_recv_)
         for (size_t i = 0; i < (size_t)good * n_recv_; ++i) recv_log_.push_back((double)recv_stage_[i]);
     steps_done += good;
     signal_pos_ += good;
@@ -439,6 +451,8 @@ int Engine<Real>::query(int what, uint64_t* value) {
         case WV_QUERY_SNAPSHOT_NS: *value = (uint64_t)(snap_.kernel_ms * 1e6 + 0.5); return WV_OK;
         case WV_QUERY_SNAPSHOT_BYTES: *value = snap_.bytes; return WV_OK;
         case WV_QUERY_SNAPSHOTS_TAKEN: *value = snap_.taken; return WV_OK;
+        case WV_QUERY_WIDE_GATHERS: *value = wide_gathers_; return WV_OK;
+        case WV_QUERY_DIRECTIONAL_LAUNCHES: *value = dir_.launches; return WV_OK;
         default: return fail(WV_E_INVALID_ARGUMENT, "unknown query");
     }
 }

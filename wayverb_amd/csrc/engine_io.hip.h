@@ -45,6 +45,13 @@ int Engine<Real>::set_source(int kind, uint64_t node, const double* signal, uint
 
 template <typename Real>
 int Engine<Real>::set_receivers(const uint64_t* nodes, uint32_t n) {
+    const int rc = set_columns(nodes, n);
+    if (rc == WV_OK) directional_release();  // plain columns again (engine_directional.hip.h)
+    return rc;
+}
+
+template <typename Real>
+int Engine<Real>::set_columns(const uint64_t* nodes, uint32_t n) {
     DeviceGuard guard(device_);
     // validate and build the new device buffers first; the engine's state changes only when
     // nothing can fail any more (a failed call leaves the engine without receivers)
@@ -163,6 +170,7 @@ bool Engine<Real>::io_nodes_clear_of_x_walls() {
 
 template <typename Real>
 int Engine<Real>::fetch_receivers(uint64_t first, uint64_t n, double* dst) {
+    if (dir_.active) return fail(WV_E_STATE, "wv_fetch_receivers: the receivers are directional receivers (wv_fetch_directional has their records)");
     if (first < recv_first_step_) return fail(WV_E_INVALID_ARGUMENT, "steps before wv_set_receivers are not recorded");
     const uint64_t off = first - recv_first_step_;
     if ((off + n) * n_recv_ > recv_log_.size()) return fail(WV_E_INVALID_ARGUMENT, "steps not recorded yet");
@@ -343,6 +351,7 @@ int Engine<Real>::checkpoint(int op) {
             f = nullptr;
         }
         if (ckpt_.fmem) (void)hipFree(ckpt_.fmem);
+        if (ckpt_.dir_velocity) (void)hipFree(ckpt_.dir_velocity);
         ckpt_ = Checkpoint{};
         return WV_OK;
     }
@@ -369,9 +378,24 @@ int Engine<Real>::checkpoint(int op) {
                 return fail(WV_E_HIP, std::string("wv_checkpoint: no room for a copy of the filter memories: ") + hipGetErrorString(rc));
             }
         }
+        if (dir_.active && (!ckpt_.dir_velocity || ckpt_.dir_n < dir_.n)) {
+            if (ckpt_.dir_velocity) (void)hipFree(ckpt_.dir_velocity);
+            ckpt_.dir_velocity = nullptr;
+            const hipError_t rc = hipMalloc((void**)&ckpt_.dir_velocity, (size_t)dir_.n * 3 * sizeof(double));
+            if (rc != hipSuccess) {
+                ckpt_.dir_velocity = nullptr;
+                (void)hipGetLastError();
+                return fail(WV_E_HIP, std::string("wv_checkpoint: no room for a copy of the directional receivers' velocities: ") + hipGetErrorString(rc));
+            }
+            ckpt_.dir_n = dir_.n;
+        }
         WV_HIP(hipMemcpyAsync(ckpt_.field[0], field_[cur_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.field[1], field_[prv_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.fmem, fmem_, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
+        if (dir_.active)
+            WV_HIP(hipMemcpyAsync(ckpt_.dir_velocity, dir_.velocity, (size_t)dir_.n * 3 * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+        ckpt_.dir_log_size = dir_.log.size();
+        ckpt_.dir_generation = dir_.generation;
         ckpt_.steps_done = steps_done;
         ckpt_.signal_pos = signal_pos_;
         ckpt_.recv_first_step = recv_first_step_;
@@ -386,13 +410,18 @@ int Engine<Real>::checkpoint(int op) {
     }
     if (op != 1) return fail(WV_E_INVALID_ARGUMENT, "unknown checkpoint operation");
     if (!ckpt_.valid) return fail(WV_E_STATE, "wv_rollback: no checkpoint has been taken");
-    if (ckpt_.recv_first_step != recv_first_step_ || ckpt_.n_recv != n_recv_ || recv_log_.size() < ckpt_.recv_log_size)
+    if (ckpt_.recv_first_step != recv_first_step_ || ckpt_.n_recv != n_recv_ || recv_log_.size() < ckpt_.recv_log_size ||
+        ckpt_.dir_generation != dir_.generation || dir_.log.size() < ckpt_.dir_log_size)
         return fail(WV_E_STATE, "wv_rollback: the receivers were changed after the checkpoint");
     if (signal_pos_ < ckpt_.signal_pos)
         return fail(WV_E_STATE, "wv_rollback: the source was changed after the checkpoint");
     WV_HIP(hipMemcpyAsync(field_[cur_], ckpt_.field[0], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(field_[prv_], ckpt_.field[1], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(fmem_, ckpt_.fmem, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
+    if (dir_.active) {
+        WV_HIP(hipMemcpyAsync(dir_.velocity, ckpt_.dir_velocity, (size_t)dir_.n * 3 * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+        dir_.log.resize(ckpt_.dir_log_size);
+    }
     steps_done = ckpt_.steps_done;
     signal_pos_ = ckpt_.signal_pos;
     recv_log_.resize(ckpt_.recv_log_size);

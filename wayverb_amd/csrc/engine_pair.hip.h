@@ -530,6 +530,17 @@ void Engine<Real>::launch_pre_post(Real* field, int slot, uint64_t signal_pos, b
 
 template <typename Real>
 void Engine<Real>::launch_pre_post(const wv::PrePostArgs<Real>& pp) {
+    if (pp.n_recv > 64) {
+        // a receiver array: its columns are gathered one lane each by a launch of their own (receiver_kernels.hip.h), FIRST -- it reads
+        // cur[source_node] as `pre` finds it, the store of the sample is in the launch behind it (a store inside a gather of several
+        // workgroups would race with a soft source's read) --, and the one wave keeps the flag words, the source store and the list
+        hipLaunchKernelGGL(wv::receiver_gather_kernel<Real>, dim3((pp.n_recv + 255u) / 256u), dim3(256), 0, stream_, pp);
+        wv::PrePostArgs<Real> rest = pp;
+        rest.n_recv = 0;
+        hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, rest);
+        ++wide_gathers_;
+        return;
+    }
     hipLaunchKernelGGL(wv::pre_post_kernel<Real>, dim3(1), dim3(64), 0, stream_, pp);
 }
 
@@ -540,6 +551,8 @@ template <typename Real>
 int Engine<Real>::launch_boundary_with_io(int part, Real* prev, const Real* cur, int* flag, int z0, int z1, Real* out, bool fix_inner, bool levels,
                                           int xw3, const wv::PrePostArgs<Real>& io, IoRide ride) {
     int rc;
+    // (more than 64 columns never ride in a boundary launch: batch_can_fuse_ and io_nodes_unfaced() are false for them, engine_io.hip.h)
+    assert(!(ride == IoRide::carried && io.n_recv > 64));
     const int token = begin_part_timing(part);
     if ((rc = launch_boundary(prev, cur, flag, z0, z1, ride == IoRide::carried ? &io : nullptr, out, fix_inner, levels, nullptr, xw3))) return rc;
     if (ride == IoRide::behind) launch_pre_post(io);

@@ -428,6 +428,7 @@ int Engine<Real>::enqueue_step(int slot, bool with_pre_post, uint64_t signal_pos
             // the next step's `current` is this step's `prev`
             wv::PrePostArgs<Real> nx = pre_post_args(prev, slot + 1, true, signal_pos + 1, source_live);
             if (fuse_next == 2) nx.flag2 = flags_ + slot + 2;  // a two-step pass follows: both its flag words
+            assert(nx.n_recv <= 64);  // (fuse_next comes from batch_can_fuse_, which more than 64 columns never get: io_nodes)
             if ((rc = launch_boundary(prev, cur, flag, z_begin_, z_end_, &nx))) return rc;
             pre_post_done_ = true;
         } else if ((rc = launch_boundary(prev, cur, flag, z_begin_, z_end_))) {
@@ -464,7 +465,7 @@ int Engine<Real>::replay_batch(uint64_t batch, bool source_live, bool can_fuse) 
         (void)io_nodes_plain();
         (void)whole_step_ready();
         const int cur_before = cur_, prv_before = prv_;
-        const uint64_t whole_before = whole_steps_;
+        const uint64_t whole_before = whole_steps_, wide_before = wide_gathers_;
         hipGraph_t graph = nullptr;
         WV_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
         graph_capturing_ = true;
@@ -479,6 +480,8 @@ int Engine<Real>::replay_batch(uint64_t batch, bool source_live, bool can_fuse) 
         prv_ = prv_before;
         graph_whole_steps_ = whole_steps_ - whole_before;  // (counted per replay, not per capture)
         whole_steps_ = whole_before;
+        graph_wide_gathers_ = wide_gathers_ - wide_before;
+        wide_gathers_ = wide_before;
         if (rc != WV_OK) {
             if (graph) (void)hipGraphDestroy(graph);
             return rc;
@@ -492,6 +495,7 @@ int Engine<Real>::replay_batch(uint64_t batch, bool source_live, bool can_fuse) 
     WV_HIP(hipMemcpyAsync(signal_base_dev_, &signal_pos_, sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
     WV_HIP(hipGraphLaunch(graph_exec_, stream_));
     whole_steps_ += graph_whole_steps_;
+    wide_gathers_ += graph_wide_gathers_;
     // batch is even: the fields are back in their roles
     // A replay runs no host code of enqueue_step: what that clears per step has to be cleared here -- the fields have moved
     // on without the x-facing walls' compact copies (a two-step pass after this must refill them), and every plane has

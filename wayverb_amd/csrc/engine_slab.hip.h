@@ -11,6 +11,7 @@ template <typename Real>
 int Engine<Real>::comm_init(const void* id, int rank, int nranks) {
     DeviceGuard guard(device_);
     if (comm_) return fail(WV_E_STATE, "communicator already initialised");
+    if (dir_.active && nranks > 1) return fail(WV_E_STATE, wv::kDirectionalOnSlab);
     std::unique_ptr<wv::SlabComm> c(new wv::SlabComm());
     std::string err;
     if (!c->init(id, rank, nranks, device_, comm_stream_, opt_.ghost_lo != 0, opt_.ghost_hi != 0, &err))
@@ -51,6 +52,7 @@ template <typename Real>
 int Engine<Real>::comm_init_local(int rank, int nranks) {
     DeviceGuard guard(device_);
     if (comm_) return fail(WV_E_STATE, "communicator already initialised");
+    if (dir_.active && nranks > 1) return fail(WV_E_STATE, wv::kDirectionalOnSlab);
     std::unique_ptr<wv::SlabComm> c(new wv::SlabComm());
     std::string err;
     if (!c->init_local(rank, nranks, device_, comm_stream_, opt_.ghost_lo != 0, opt_.ghost_hi != 0, &err))

@@ -333,6 +333,38 @@ extern "C" int wv_attenuate(int32_t method, const float pointing[3], float shape
     return WV_OK;
 }
 
+// postprocessor::directional_receiver::operator() (directional_receiver.cpp:29-67) on recorded columns: the host twin of
+// directional_accumulate_kernel (receiver_kernels.hip.h), operation for operation, for columns that come from a chain of slabs.
+extern "C" int wv_directional_accumulate(const double* p7, uint64_t n, double spacing, double sample_rate, double ambient_density,
+                                         double velocity[3], wv_directional_output* out) {
+    if ((n && (!p7 || !out)) || !velocity) return wv::fail_with(WV_E_INVALID_ARGUMENT, "bad argument");
+    if (!(spacing > 0) || !(sample_rate > 0) || !(ambient_density > 0))
+        return wv::fail_with(WV_E_INVALID_ARGUMENT, "wv_directional_accumulate: spacing, sample rate and ambient density must be positive");
+    const double k = ambient_density * sample_rate;
+    double vx = velocity[0], vy = velocity[1], vz = velocity[2];
+    for (uint64_t s = 0; s < n; ++s) {
+        const double* row = p7 + s * 7;
+        const float pressure = (float)row[0];
+        float surrounding[6];
+        for (int i = 0; i < 6; ++i) surrounding[i] = (float)((double)((float)row[1 + i] - pressure) / spacing);
+        const double mx = (double)(surrounding[1] - surrounding[0]) * 0.5;
+        const double my = (double)(surrounding[3] - surrounding[2]) * 0.5;
+        const double mz = (double)(surrounding[5] - surrounding[4]) * 0.5;
+        vx -= mx / k;
+        vy -= my / k;
+        vz -= mz / k;
+        const double p = (double)pressure;
+        out[s].intensity[0] = (float)(vx * p);
+        out[s].intensity[1] = (float)(vy * p);
+        out[s].intensity[2] = (float)(vz * p);
+        out[s].pressure = pressure;
+    }
+    velocity[0] = vx;
+    velocity[1] = vy;
+    velocity[2] = vz;
+    return WV_OK;
+}
+
 extern "C" int wv_adjust_sampling_rate(const float* in, uint64_t n, double in_sample_rate, double out_sample_rate,
                                        float* out, uint64_t capacity, uint64_t* n_out) {
     if ((n && !in) || !n_out) return wv::fail_with(WV_E_INVALID_ARGUMENT, "bad argument");

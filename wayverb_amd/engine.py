@@ -20,6 +20,7 @@ BUF_CURRENT = 0
 BUF_PREVIOUS = 1
 SOURCE_NONE, SOURCE_HARD, SOURCE_SOFT = 0, 1, 2
 NO_NODE = 0xFFFFFFFFFFFFFFFF
+DIRECTIONAL_OUTPUT_DTYPE = np.dtype([("intensity", "<f4", (3,)), ("pressure", "<f4")])   # wv_directional_output
 UNIQUE_ID_BYTES = 128
 
 EXPORTS = [
@@ -35,6 +36,7 @@ EXPORTS = [
     "wv_attenuate_hrtf", "wv_multiband_filter_and_mixdown", "wv_postprocess_waveguide_hrtf", "wv_scene_mesh_create", "wv_scene_mesh_fetch",
     "wv_scene_mesh_create_engine", "wv_scene_mesh_destroy", "wv_checkpoint", "wv_rollback", "wv_drop_checkpoint", "wv_host_register", "wv_host_unregister",
     "wv_compressed_waveguide_run", "wv_make_transparent", "wv_set_snapshots", "wv_snapshot_count", "wv_fetch_snapshots",
+    "wv_set_directional_receivers", "wv_fetch_directional", "wv_directional_accumulate",
 ]
 
 
@@ -173,6 +175,9 @@ def load_library():
     lib.wv_set_snapshots.argtypes = [C.c_void_p, C.POINTER(WvSnapshotPlan)]
     lib.wv_snapshot_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.wv_fetch_snapshots.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.wv_set_directional_receivers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_double]
+    lib.wv_fetch_directional.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    lib.wv_directional_accumulate.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -342,6 +347,7 @@ class Engine:
         _check(self.lib.wv_create(C.byref(wm), C.byref(opt), C.byref(handle)))
         self.h = handle
         self.n_recv = 0
+        self.n_directional = 0
         self.snapshot_shape = None
 
     @classmethod
@@ -354,6 +360,7 @@ class Engine:
         eng.dtype = np.float32 if precision == "f32" else np.float64
         eng.h = handle
         eng.n_recv = 0
+        eng.n_directional = 0
         eng.snapshot_shape = None
         return eng
 
@@ -452,9 +459,25 @@ class Engine:
 
     def set_receivers(self, nodes):
         nodes = np.ascontiguousarray(nodes, dtype=np.uint64)
+        _check(self.lib.wv_set_receivers(self.h, nodes.ctypes.data_as(C.c_void_p) if nodes.shape[0] else None,
+                                         nodes.shape[0]))
         self.n_recv = nodes.shape[0]
-        _check(self.lib.wv_set_receivers(self.h, nodes.ctypes.data_as(C.c_void_p) if self.n_recv else None,
-                                         self.n_recv))
+        self.n_directional = 0
+
+    def set_directional_receivers(self, nodes, spacing, sample_rate, ambient_density):
+        """wv_set_directional_receivers: `nodes` are the centre nodes of R directional receivers, recorded and integrated on the
+        device; fetch_directional has their records.  An empty list leaves the mode (as set_receivers does)."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint64)
+        _check(self.lib.wv_set_directional_receivers(self.h, nodes.ctypes.data_as(C.c_void_p) if nodes.shape[0] else None,
+                                                     nodes.shape[0], float(spacing), float(sample_rate), float(ambient_density)))
+        self.n_directional = nodes.shape[0]
+        self.n_recv = 7 * nodes.shape[0]
+
+    def fetch_directional(self, first, n):
+        """wv_fetch_directional: records of steps [first, first + n) as postprocess.directional_output_dtype[n, R]."""
+        out = np.zeros((n, self.n_directional), dtype=DIRECTIONAL_OUTPUT_DTYPE)
+        _check(self.lib.wv_fetch_directional(self.h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def run_steps(self, n_steps):
         """wv_run: returns (steps_done, flag)."""
@@ -546,6 +569,7 @@ class Engine:
     QUERY_TRIPLE_PASSES = 15
     QUERY_TRIPLE_MARCH_NS, QUERY_TRIPLE_MARCH_TIMED, QUERY_BOUNDARY3_NS, QUERY_FIXUP3_NS, QUERY_TRIPLE_PARTS_TIMED = 16, 17, 18, 19, 20
     QUERY_SNAPSHOT_NS, QUERY_SNAPSHOT_BYTES, QUERY_SNAPSHOTS_TAKEN = 21, 22, 23
+    QUERY_WIDE_GATHERS, QUERY_DIRECTIONAL_LAUNCHES = 24, 25
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

@@ -43,6 +43,22 @@ def directional_receiver(p7, spacing, sample_rate, ambient_density):
     return out
 
 
+def directional_accumulate(p7, spacing, sample_rate, ambient_density, velocity=None):
+    """wv_directional_accumulate: the integrator of directional_receiver above in the library (the host twin of the kernel behind
+    Engine.set_directional_receivers), for columns that come from a chain of slabs.  `velocity` float64[3] is read and advanced in
+    place, so a trace may be fed in pieces; None starts from rest.  Returns directional_output_dtype[steps]."""
+    lib = load_library()
+    p7 = np.ascontiguousarray(p7, dtype=np.float64)
+    assert p7.ndim == 2 and p7.shape[1] == 7
+    if velocity is None:
+        velocity = np.zeros(3)
+    assert velocity.dtype == np.float64 and velocity.shape == (3,) and velocity.flags.c_contiguous
+    out = np.zeros(p7.shape[0], dtype=directional_output_dtype)
+    _check(lib.wv_directional_accumulate(_p(p7), p7.shape[0], float(spacing), float(sample_rate), float(ambient_density),
+                                         _p(velocity), _p(out)))
+    return out
+
+
 def attenuate(directional, method=ATTENUATOR_NULL, pointing=(0.0, 0.0, 1.0), shape=0.0, acoustic_impedance=400.0):
     lib = load_library()
     lib.wv_attenuate.argtypes = [C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p]

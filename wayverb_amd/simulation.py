@@ -160,6 +160,67 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     return bands if snapshots is None else (bands, taken)
 
 
+def canonical_many(vm, source, receivers, environment, cutoff, usable_portion, simulation_time, precision="f64",
+                   device=-1, keep_going=lambda: True, slabs=1, devices=None, chunk=1024):
+    """canonical for MANY receivers out of ONE run of the mesh (the reference's application runs the whole mesh once per
+    source-receiver pair, src/combined/src/threaded_engine.cpp:155-162; a run costs the same however many points listen): a list,
+    one entry per receiver, of what canonical() returns for that receiver, bit for bit -- or None when stopped early.
+    One domain: the receivers are recorded and integrated on the device (Engine.set_directional_receivers).  `slabs` > 1: the chain
+    records the 7 columns of every receiver (engine.run_fast_slabs) and the library's host integrator turns them into the same
+    records (postprocess.directional_accumulate)."""
+    mesh = vm.mesh
+    sample_rate = compute_sample_rate(mesh.spacing, environment.speed_of_sound)
+
+    def mesh_index(pt):
+        idx = vm.compute_index(pt)
+        if idx >= mesh.num_nodes or not (mesh.nodes["boundary_type"][idx] & M.ID_INSIDE):
+            raise RuntimeError("Source/receiver node position appears to be outside mesh.")
+        return idx
+
+    ideal_steps = int(math.ceil(sample_rate * simulation_time))
+    signal = np.zeros(ideal_steps, dtype=np.float64)
+    if ideal_steps:
+        signal[0] = np.float32(M.rectilinear_calibration_factor(mesh.spacing, environment.acoustic_impedance))
+    centres, columns = [], []
+    for receiver in receivers:
+        idx = mesh_index(receiver)
+        neighbours = mesh.compute_neighbors(idx)
+        if any(n == 0xFFFFFFFF for n in neighbours):
+            raise RuntimeError("Can't place directional_receiver at this node as it is adjacent to a boundary.")
+        centres.append(idx)
+        columns += [idx] + list(neighbours)
+    source_index = mesh_index(source)
+    if not centres:
+        return []
+    if slabs > 1:
+        done, traces = E.run_fast_slabs(mesh, slabs, E.SOURCE_HARD, source_index, signal, columns, precision=precision,
+                                        devices=devices or [device], keep_going=keep_going, chunk=chunk)
+        if done != ideal_steps:
+            return None
+        records = [P.directional_accumulate(traces[:, 7 * i:7 * i + 7], mesh.spacing, sample_rate, environment.ambient_density)
+                   for i in range(len(centres))]
+    else:
+        eng = E.Engine(mesh, precision=precision, device=device)
+        try:
+            eng.set_source(E.SOURCE_HARD, source_index, signal)
+            eng.set_directional_receivers(centres, mesh.spacing, sample_rate, environment.ambient_density)
+            first = eng.step_count()
+            done = 0
+            while done < ideal_steps and keep_going():
+                took, flag = eng.run_steps(min(chunk, ideal_steps - done))
+                done += took
+                E.raise_for_flag(flag)
+                if took == 0:
+                    break
+            if done != ideal_steps:
+                return None
+            got = eng.fetch_directional(first, done)
+        finally:
+            eng.close()
+        records = [np.ascontiguousarray(got[:, i]) for i in range(len(centres))]
+    return [[(r, sample_rate, (0.0, float(cutoff)))] for r in records]
+
+
 def band_edges_hz(bands=8, lo=20.0, hi=20000.0):
     """hrtf_band_params_hz().edges: band_edge_frequency(i, 8, {20, 20000})
     (src/frequency_domain/src/envelope.cpp:50-53, src/hrtf/lib/include/hrtf/multiband.h:22-25)"""
@@ -212,3 +273,33 @@ def impulse_response(vertices, triangles, surface_absorptions, source, receiver,
         bands, taken = both
     audio = P.postprocess(bands, method, pointing, shape, environment.acoustic_impedance, output_sample_rate)
     return (audio, bands, vm) if snapshots is None else (audio, bands, vm, taken)
+
+
+def impulse_responses(vertices, triangles, surface_absorptions, source, receivers, cutoff=200.0, usable_portion=0.6,
+                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
+                      pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, slabs=1, devices=None):
+    """impulse_response for several receivers out of one run of the mesh.  The mesh is anchored at the FIRST receiver (as the
+    reference anchors it at its only one, engine.cpp:98-103): a node coincides with it; the others snap to their nearest node, as the
+    source does (compute_index).  `method`, `pointing`, `shape` may be lists, one entry per receiver.
+    Returns (audio per receiver, bands per receiver, the node positions used float32[R, 3], vm)."""
+    environment = environment or Environment()
+    receivers = [tuple(r) for r in receivers]
+    if not receivers:
+        raise ValueError("no receivers")
+    vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receivers[0],
+                                 compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
+    per = canonical_many(vm, source, receivers, environment, cutoff, usable_portion, simulation_time, precision, device,
+                         slabs=slabs, devices=devices)
+    if per is None:
+        raise RuntimeError("the waveguide run was stopped early")
+
+    def of(value, i, scalar):
+        return value[i] if isinstance(value, (list, tuple)) and not scalar(value) else value
+
+    is_vec = lambda v: len(v) == 3 and all(np.isscalar(c) for c in v)   # noqa: E731  (one pointing, not a list of them)
+    never = lambda v: False   # noqa: E731
+    audio = [P.postprocess(bands, of(method, i, never), of(pointing, i, is_vec), of(shape, i, never),
+                           environment.acoustic_impedance, output_sample_rate) for i, bands in enumerate(per)]
+    positions = np.stack([vm.min_corner + np.asarray(vm.compute_locator(r), dtype=np.float32) * np.float32(vm.mesh.spacing)
+                          for r in receivers])
+    return audio, per, positions, vm
