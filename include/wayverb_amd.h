@@ -327,6 +327,58 @@ int wv_set_snapshots(wv_engine* e, const wv_snapshot_plan* plan);
 int wv_snapshot_count(wv_engine* e, uint64_t* taken, uint64_t* first_held);
 int wv_fetch_snapshots(wv_engine* e, uint64_t first, uint64_t n, float* dst /* [n][nz][ny][nx] */, uint64_t* steps /* [n] */);
 
+/* ---- field spectra: a box of the field Fourier-transformed on the device ------------------------- */
+/* What the room does at a given frequency everywhere at once -- mode shapes, steady-state pressure maps, the transfer function from
+ * the source to every node of a plane -- is the Fourier transform over time of a box of the field.  With snapshots alone every
+ * capture crosses the link and the host array grows with the run; a spectrum plan has the engine capture the box as a snapshot
+ * plan would (the same box / stride semantics, the same cadence) and accumulate, per node taken and per frequency, a running
+ * discrete Fourier sum ON THE DEVICE.  Nothing crosses the link until the caller fetches the K complex fields.
+ *
+ * Definition.  p_j is the float a snapshot of plan step n_j holds for the node: the field after exactly n_j completed steps, a
+ * double rounded to nearest (the snapshot block above, unchanged).  f_k is in cycles per step, 0 <= f_k <= 0.5.  The twiddles come
+ * from one exported function, which the engine itself uses on the host (the device evaluates no trigonometric function):
+ *     wv_spectrum_twiddle(f, step, &c, &s):   x = f * (double)step;  x -= floor(x);  c = cos(2 pi x);  s = sin(2 pi x)   (libm, double)
+ * and the sums run in capture order j = 0, 1, ..., in double, the product rounded, then the sum rounded:
+ *     re[k] = re[k] + (double)p_j * c(j, k)          im[k] = im[k] - (double)p_j * s(j, k)
+ * so X_k = sum_j p_j e^(-2 pi i f_k n_j), and a loop over the snapshots in the same order that evaluates `a + p * c` on float64
+ * arrays reproduces the sums BIT FOR BIT.  No window is applied: a caller who wants one changes the cadence or post-processes.
+ *
+ *   - 1 <= n_freqs <= 64; a frequency outside [0, 0.5], a NaN, a box that leaves the mesh, a zero stride or a zero period:
+ *     WV_E_INVALID_ARGUMENT
+ *   - everything (the stage of 16 captures, 64 bytes per node; the sums, 16 n_freqs bytes per node) is allocated when the plan is
+ *     set: with no room the call answers WV_E_HIP and leaves the engine and any earlier plan untouched.  A new plan replaces the old
+ *     one and forgets its sums; a NULL plan stops, forgets and frees (as does wv_destroy)
+ *   - one domain only: a slab of a chain answers WV_E_STATE (the snapshot plan's reason)
+ *   - a spectrum plan and a snapshot plan are EXCLUSIVE: both decide where passes end; setting one while the other is active answers
+ *     WV_E_STATE
+ *   - after a run that stopped on a flag at step f (an overflow, or keep_going cleared) the sums hold exactly the captures of steps
+ *     <= f, and wv_spectrum_count says how many: a capture of a step that was never committed is never folded in
+ *   - wv_step / wv_swap capture nothing; plan steps they pass are passed, as for snapshots
+ *   - wv_checkpoint copies the sums and the count aside (the copy is allocated by the first checkpoint taken under a plan: WV_E_HIP,
+ *     engine untouched, when there is no room); wv_rollback puts both back, and the re-run reproduces them bitwise.  A plan set
+ *     AFTER the checkpoint makes wv_rollback answer WV_E_STATE, as a changed source does
+ *   - wv_fetch_spectrum may be called any time outside wv_run; it folds what is staged and leaves the plan running, so fetching
+ *     twice during a long run gives two consistent partial sums
+ *   - with no plan nothing is launched, allocated or waited for; with one the fields, receiver rows and flags are bit-identical to
+ *     a run without
+ *
+ * wv_spectrum_count: *captures = captures of completed steps since the plan was set, *last_step = the step of the last of them
+ * (either may be NULL).  wv_fetch_spectrum: the sums as complex128 [n_freqs][nz][ny][nx] (re, im interleaved), *captures (may be
+ * NULL) = how many captures they hold. */
+typedef struct wv_spectrum_plan {
+    int32_t x0, y0, z0;  /* first node of the box */
+    int32_t nx, ny, nz;  /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;  /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step; /* captures at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;     /* >= 1 */
+    uint32_t n_freqs;    /* K, 1 .. 64 */
+    uint32_t reserved;
+} wv_spectrum_plan;
+int wv_set_spectrum(wv_engine* e, const wv_spectrum_plan* plan, const double* cycles_per_step /* [n_freqs] */);
+int wv_spectrum_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
+int wv_fetch_spectrum(wv_engine* e, double* dst /* [n_freqs][nz][ny][nx][2]: complex128 */, uint64_t* captures);
+void wv_spectrum_twiddle(double cycles_per_step, uint64_t step, double* c, double* s);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */
@@ -356,7 +408,12 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *                            that ran with kernel timing on, bytes captured, snapshots taken
  *   WV_QUERY_WIDE_GATHERS    steps whose receivers (more than 64 columns) were gathered by a launch of their own, one lane per
  *                            column, since creation (receiver_kernels.hip.h); 0 for ever with 64 columns or fewer
- *   WV_QUERY_DIRECTIONAL_LAUNCHES   launches of the directional receivers' integrator since creation (one per batch of wv_run) */
+ *   WV_QUERY_DIRECTIONAL_LAUNCHES   launches of the directional receivers' integrator since creation (one per batch of wv_run)
+ *   WV_QUERY_SPECTRUM_CAPTURES, WV_QUERY_SPECTRUM_FOLDS, WV_QUERY_SPECTRUM_NS   since wv_set_spectrum: captures of completed steps,
+ *                            launches of the fold kernel (one per 16 captures at the most, plus those a fetch or a checkpoint asked
+ *                            for), total time of the fold kernels that ran with kernel timing on.  (The capture kernel's time under
+ *                            a spectrum plan is in neither this nor WV_QUERY_SNAPSHOT_NS: it is the snapshot plan's capture, whose
+ *                            time DESIGN.md 4.7 has) */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -372,7 +429,8 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
        WV_QUERY_TRIPLE_MARCH_NS = 16, WV_QUERY_TRIPLE_MARCH_TIMED = 17, WV_QUERY_BOUNDARY3_NS = 18, WV_QUERY_FIXUP3_NS = 19,
        WV_QUERY_TRIPLE_PARTS_TIMED = 20,
        WV_QUERY_SNAPSHOT_NS = 21, WV_QUERY_SNAPSHOT_BYTES = 22, WV_QUERY_SNAPSHOTS_TAKEN = 23,
-       WV_QUERY_WIDE_GATHERS = 24, WV_QUERY_DIRECTIONAL_LAUNCHES = 25 };
+       WV_QUERY_WIDE_GATHERS = 24, WV_QUERY_DIRECTIONAL_LAUNCHES = 25,
+       WV_QUERY_SPECTRUM_CAPTURES = 26, WV_QUERY_SPECTRUM_FOLDS = 27, WV_QUERY_SPECTRUM_NS = 28 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

@@ -56,6 +56,11 @@ def main():
     ap.add_argument("--snapshots", help="z=<plane>,every=<k>: record plane z of the field every k steps while the run goes on "
                                         "(Engine.set_snapshots; single-band runs)")
     ap.add_argument("--snapshot-out", default="snapshots", help="directory the snapshots go to, one step_<n>.npy (float32[ny, nx]) each")
+    ap.add_argument("--spectrum", help="HZ[,HZ...]: Fourier-transform one horizontal plane of the field at these frequencies on the "
+                                       "device while the run goes on (Engine.set_spectrum; single-band runs)")
+    ap.add_argument("--spectrum-plane", default=None, help="z=<metres>: the height of that plane (default: the receiver's)")
+    ap.add_argument("--spectrum-out", default="spectrum.npz", help="the complex maps go here: spectrum complex128[K, ny, nx], freqs_hz, "
+                                                                   "captures, plane (node index), z (metres of that plane)")
     args = ap.parse_args()
 
     bands = None
@@ -101,11 +106,29 @@ def main():
 
     receivers = args.receiver or [[8.0, 20.0, 1.2]]
     args.receiver = receivers[0]
+    spectrum = None
+    if args.spectrum:
+        if bands or snapshots is not None:
+            ap.error("--spectrum: single-band runs without --snapshots")
+        freqs_hz = [float(x) for x in args.spectrum.split(",")]
+        height = args.receiver[2]
+        if args.spectrum_plane:
+            if not args.spectrum_plane.startswith("z="):
+                ap.error("--spectrum-plane takes z=<metres>")
+            height = float(args.spectrum_plane[2:])
+        spectrum_plane = {}
+
+        def spectrum(mesh):
+            plane = int(round((height - mesh.min_corner[2]) / mesh.spacing))
+            if not 0 <= plane < mesh.dims[2]:
+                ap.error("--spectrum-plane: z=%g m is outside the mesh" % height)
+            spectrum_plane.update(plane=plane, z=mesh.min_corner[2] + plane * mesh.spacing)
+            return dict(freqs_hz=freqs_hz, box=((0, 0, plane), (None, None, 1)))
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
     if len(receivers) > 1:
-        if bands or snapshots is not None:
-            ap.error("several --receiver: single-band runs without --snapshots")
+        if bands or snapshots is not None or spectrum is not None:
+            ap.error("several --receiver: single-band runs without --snapshots or --spectrum")
         audios, per, positions, vm = W.impulse_responses(v, t, absorptions, args.source, receivers, args.cutoff, args.usable_portion,
                                                          args.seconds, args.rate, method=method, pointing=args.pointing,
                                                          shape=args.mic_shape or 0.0, precision=args.precision)
@@ -130,7 +153,12 @@ def main():
         audio_etc = W.impulse_response(v, t, absorptions, args.source, args.receiver, args.cutoff,
                                        args.usable_portion, args.seconds, args.rate, method=method,
                                        pointing=args.pointing, shape=args.mic_shape or 0.0,
-                                       precision=args.precision, snapshots=snapshots)
+                                       precision=args.precision, snapshots=snapshots, spectrum=spectrum)
+        if spectrum is not None:
+            maps, captures = audio_etc[3]
+            np.savez(args.spectrum_out, spectrum=maps[:, 0], freqs_hz=np.array(freqs_hz), captures=captures,
+                     plane=spectrum_plane["plane"], z=spectrum_plane["z"])
+            print("wrote %d complex maps of plane z=%d (%d captures) to %s" % (maps.shape[0], spectrum_plane["plane"], captures, args.spectrum_out))
         if snapshots is not None:
             fields, steps = audio_etc[3]
             os.makedirs(args.snapshot_out, exist_ok=True)

@@ -14,6 +14,7 @@
 #include "engine_batch.hip.h"
 #include "engine_io.hip.h"
 #include "engine_snapshot.hip.h"
+#include "engine_spectrum.hip.h"
 #include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
@@ -202,6 +203,24 @@ int wv_snapshot_count(wv_engine* e, uint64_t* taken, uint64_t* first_held) {
 int wv_fetch_snapshots(wv_engine* e, uint64_t first, uint64_t n, float* dst, uint64_t* steps) {
     WV_NEED(e);
     return e->fetch_snapshots(first, n, dst, steps);
+}
+int wv_set_spectrum(wv_engine* e, const wv_spectrum_plan* plan, const double* cycles_per_step) {
+    WV_NEED(e);
+    return e->set_spectrum(plan, cycles_per_step);
+}
+int wv_spectrum_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
+    WV_NEED(e);
+    return e->spectrum_count(captures, last_step);
+}
+int wv_fetch_spectrum(wv_engine* e, double* dst, uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_spectrum(dst, captures);
+}
+void wv_spectrum_twiddle(double cycles_per_step, uint64_t step, double* c, double* s) {
+    double cc = 1.0, ss = 0.0;
+    wv::spectrum_twiddle(cycles_per_step, step, &cc, &ss);
+    if (c) *c = cc;
+    if (s) *s = ss;
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

@@ -17,6 +17,8 @@
 //                        receivers
 //   engine_snapshot.hip.h  field snapshots taken on the device while a run goes on (wv_set_snapshots): plan, ring, capture, copy stream, held log
 //   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape
+//   engine_spectrum.hip.h  field spectra accumulated on the device while a run goes on (wv_set_spectrum): plan, stage, fold, fetch
+//   spectrum_plan.h      (host only, no HIP) free slots of the stage, when a fold is due, which captures survive a stop, sizes
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -24,12 +26,14 @@
 #include "engine_base.h"
 #include "march_plan.h"
 #include "snapshot_plan.h"
+#include "spectrum_plan.h"
 
 #include "boundary_kernels.hip.h"
 #include "pair_kernels.hip.h"
 #include "stream_kernels.hip.h"
 #include "plane_kernels.hip.h"
 #include "snapshot_kernels.hip.h"
+#include "spectrum_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -167,6 +171,11 @@ public:
     int snapshot_count(uint64_t* taken, uint64_t* first_held) override;
     int fetch_snapshots(uint64_t first, uint64_t n, float* dst, uint64_t* steps) override;
     bool snapshots_active() const override { return snap_.active; }
+    // ---- engine_spectrum.hip.h
+    int set_spectrum(const wv_spectrum_plan* plan, const double* cycles_per_step) override;
+    int spectrum_count(uint64_t* captures, uint64_t* last_step) override;
+    int fetch_spectrum(double* dst, uint64_t* captures) override;
+    bool spectrum_active() const override { return spec_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -388,6 +397,9 @@ private:
         uint32_t dir_n = 0;              // (receivers the copy has room for)
         size_t dir_log_size = 0;
         uint64_t dir_generation = 0;
+        double* spec_acc = nullptr;  // the spectrum plan's sums (engine_spectrum.hip.h), allocated by the first checkpoint under a plan
+        size_t spec_bytes = 0;
+        uint64_t spec_generation = 0, spec_captures = 0, spec_last_step = 0, spec_next = 0;
     } ckpt_;
     // field snapshots (engine_snapshot.hip.h): a ring of device slots the capture kernel fills on the compute stream, each copied to its
     // page-locked twin on a stream of its own, and the log of the snapshots the host holds
@@ -423,12 +435,54 @@ private:
         std::deque<std::pair<uint64_t, std::vector<float>>> held;  // (step, floats), oldest first: snapshots taken - held.size() .. taken - 1
     } snap_;
     static void snapshot_release(Snapshots& s);
+    int launch_snapshot_gather(const wv::SnapshotBox& box, bool wide, float* dst);
     int snapshot_capture(uint64_t step);
     int snapshot_harvest(bool wait, size_t limit = ~size_t{0});
     void snapshot_discard_after(uint64_t last_good_step);
     int snapshot_plan_batch();
     int snapshot_begin_run();
     void snapshot_rollback(uint64_t to_step);
+    // field spectra (engine_spectrum.hip.h): the device-only stage the capture kernel fills on the compute stream, the planar sums the
+    // fold kernel accumulates, two twiddle tables (page-locked, and their device copies) the host writes in turn
+    struct Spectrum {
+        bool active = false, gather_wide = false, fold_wide = false;
+        wv_spectrum_plan plan{};
+        wv::SnapshotBox box;
+        std::vector<double> freqs;      // cycles per step, [K]
+        uint64_t generation = 0;        // bumped by every wv_set_spectrum (a checkpoint remembers which plan it saw)
+        uint64_t next = wv::kNoSnapshotStep;       // the next plan step not yet captured
+        uint64_t batch_end = wv::kNoSnapshotStep;  // the plan step at which the batch being planned ends at the latest
+        uint64_t nodes = 0;             // B: nodes taken
+        float* stage = nullptr;         // [T][B]
+        double* acc = nullptr;          // [K][2][B]
+        double* tw_host[2] = {nullptr, nullptr};
+        double* tw_dev[2] = {nullptr, nullptr};
+        hipEvent_t begun[2] = {nullptr, nullptr};      // before the fold that uses the table (kernel timing)
+        hipEvent_t folded_ev[2] = {nullptr, nullptr};  // behind it: the host may write the table again
+        bool table_used[2] = {false, false}, timed[2] = {false, false};
+        int table = 0;                  // the table the next fold writes
+        std::vector<uint64_t> steps;    // the steps of the staged captures, slot by slot
+        int committed = 0;              // how many of them are of committed steps (all of them between batches)
+        uint64_t folded = 0;            // captures in the sums
+        uint64_t last_step = 0;         // the step of the last committed capture
+        uint64_t folds = 0;             // WV_QUERY_SPECTRUM_FOLDS
+        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
+    } spec_;
+    static void spectrum_release(Spectrum& s);
+    int spectrum_capture(uint64_t step);
+    int spectrum_drain_timing(int table);
+    void spectrum_drop_uncommitted();
+    int spectrum_fold();
+    void spectrum_commit(uint64_t last_good_step);
+    int spectrum_plan_batch();
+    int spectrum_begin_run();
+    int spectrum_checkpoint();
+    int spectrum_rollback();
+    // whichever plan is active decides where passes end (engine_batch.hip.h): the two exclude each other
+    bool capture_plan_active() const { return snap_.active || spec_.active; }
+    uint64_t capture_next() const { return snap_.active ? snap_.next : spec_.active ? spec_.next : wv::kNoSnapshotStep; }
+    uint64_t capture_batch_end() const { return snap_.active ? snap_.batch_end : spec_.active ? spec_.batch_end : wv::kNoSnapshotStep; }
+    int capture_step(uint64_t step) { return snap_.active ? snapshot_capture(step) : spectrum_capture(step); }
 };
 
 }  // namespace wv

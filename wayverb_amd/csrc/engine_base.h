@@ -92,6 +92,10 @@ struct wv_engine {
     virtual int snapshot_count(uint64_t* taken, uint64_t* first_held) = 0;
     virtual int fetch_snapshots(uint64_t first, uint64_t n, float* dst, uint64_t* steps) = 0;
     virtual bool snapshots_active() const = 0;
+    virtual int set_spectrum(const wv_spectrum_plan* plan, const double* cycles_per_step) = 0;
+    virtual int spectrum_count(uint64_t* captures, uint64_t* last_step) = 0;
+    virtual int fetch_spectrum(double* dst, uint64_t* captures) = 0;
+    virtual bool spectrum_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;
     virtual int set_source(int kind, uint64_t node, const double* signal, uint64_t n) = 0;

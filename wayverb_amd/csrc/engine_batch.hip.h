@@ -151,7 +151,8 @@ uint64_t Engine<Real>::plan_batch(uint64_t remaining) {
     }
     // a snapshot step is the end of a pass, and a batch holds no more captures than the ring has free slots (snapshot_plan.h;
     // snapshot_plan_batch has set where this batch must end at the latest)
-    if (snap_.active) batch = wv::snapshot_batch_limit(batch, steps_done, snap_.batch_end);
+    // (a spectrum plan's captures are a snapshot plan's, and cut the batches the same way: whichever plan is active)
+    if (capture_plan_active()) batch = wv::snapshot_batch_limit(batch, steps_done, capture_batch_end());
     batch_can_fuse_ = !comm_ && io_nodes_plain() && opt_.tuning.fuse_pre_post != 0;
     (void)whole_step_ready();  // (looks at the class map once per source / receiver set: here, not inside a capture)
     batch_source_live_ = source_kind_ != WV_SOURCE_NONE;
@@ -253,11 +254,17 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
     if (snap_.active) {
         const int rc = snapshot_begin_run();
         if (rc) return rc;
+    } else if (spec_.active) {  // (engine_spectrum.hip.h)
+        const int rc = spectrum_begin_run();
+        if (rc) return rc;
     }
     while (completed < n_steps && flag == 0) {
         // where this batch ends: it may hold captures for half the snapshot ring
         if (snap_.active) {
             const int rc = snapshot_plan_batch();
+            if (rc) return rc;
+        } else if (spec_.active) {  // ... or as many captures as the spectrum's stage has free slots, folded first when it has none
+            const int rc = spectrum_plan_batch();
             if (rc) return rc;
         }
         uint64_t batch = plan_batch(n_steps - completed);
@@ -333,7 +340,8 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
             // would); the capture is enqueued between the two passes.  Without a plan the one segment is the batch.
             uint64_t seg_end = batch;
             auto next_segment = [&] {
-                seg_end = (snap_.active && snap_.next > steps_done && snap_.next - steps_done < batch) ? snap_.next - steps_done : batch;
+                const uint64_t next = capture_next();
+                seg_end = (capture_plan_active() && next > steps_done && next - steps_done < batch) ? next - steps_done : batch;
             };
             next_segment();
             auto triple_at = [&](uint64_t i) { return triples && i >= (uint64_t)singles_first && i + 3 <= seg_end; };
@@ -358,19 +366,20 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
                     i += 1;
                 }
                 if (i == seg_end && i < batch) {  // (the capture at the batch's end follows below, for every form)
-                    if ((rc = snapshot_capture(snap_.next))) return rc;
+                    if ((rc = capture_step(capture_next()))) return rc;
                     next_segment();
                 }
             }
         }
         // the batch ends on a snapshot step: the capture goes directly behind the pass (or the replayed graph) that produced it
-        if (snap_.active && steps_done + batch == snap_.next && (rc = snapshot_capture(snap_.next))) return rc;
+        if (capture_plan_active() && steps_done + batch == capture_next() && (rc = capture_step(capture_next()))) return rc;
         // captures of EARLIER batches whose copies have landed go into the held log now, while this batch keeps the device busy
         if (snap_.active && (rc = snapshot_harvest(false, snap_.committed))) return rc;
         if ((rc = collect_batch(batch))) return rc;
         uint64_t good = 0;
         if ((rc = commit_batch(batch, flags_host_, &good, &flag))) return rc;
         if (snap_.active && good < batch) snapshot_discard_after(steps_done);  // (a flag stopped the run before those steps)
+        if (spec_.active) spectrum_commit(steps_done);  // the batch's captures of completed steps stay staged, the others are dropped
         completed += good;
     }
     // on return every snapshot of a completed step can be fetched
@@ -453,6 +462,17 @@ int Engine<Real>::query(int what, uint64_t* value) {
         case WV_QUERY_SNAPSHOTS_TAKEN: *value = snap_.taken; return WV_OK;
         case WV_QUERY_WIDE_GATHERS: *value = wide_gathers_; return WV_OK;
         case WV_QUERY_DIRECTIONAL_LAUNCHES: *value = dir_.launches; return WV_OK;
+        case WV_QUERY_SPECTRUM_CAPTURES: *value = spec_.folded + (uint64_t)spec_.committed; return WV_OK;
+        case WV_QUERY_SPECTRUM_FOLDS: *value = spec_.folds; return WV_OK;
+        case WV_QUERY_SPECTRUM_NS: {
+            DeviceGuard guard(device_);
+            for (int b = 0; b < 2; ++b) {
+                const int rc = spectrum_drain_timing(b);
+                if (rc) return rc;
+            }
+            *value = (uint64_t)(spec_.kernel_ms * 1e6 + 0.5);
+            return WV_OK;
+        }
         default: return fail(WV_E_INVALID_ARGUMENT, "unknown query");
     }
 }

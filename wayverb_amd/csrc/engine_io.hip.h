@@ -352,6 +352,7 @@ int Engine<Real>::checkpoint(int op) {
         }
         if (ckpt_.fmem) (void)hipFree(ckpt_.fmem);
         if (ckpt_.dir_velocity) (void)hipFree(ckpt_.dir_velocity);
+        if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
         ckpt_ = Checkpoint{};
         return WV_OK;
     }
@@ -389,6 +390,12 @@ int Engine<Real>::checkpoint(int op) {
             }
             ckpt_.dir_n = dir_.n;
         }
+        // the spectrum plan's sums and count (engine_spectrum.hip.h): their copy is allocated by the first checkpoint under the plan
+        if (spec_.active) {
+            const int rc = spectrum_checkpoint();
+            if (rc) return rc;
+        }
+        ckpt_.spec_generation = spec_.generation;
         WV_HIP(hipMemcpyAsync(ckpt_.field[0], field_[cur_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.field[1], field_[prv_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.fmem, fmem_, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
@@ -415,9 +422,15 @@ int Engine<Real>::checkpoint(int op) {
         return fail(WV_E_STATE, "wv_rollback: the receivers were changed after the checkpoint");
     if (signal_pos_ < ckpt_.signal_pos)
         return fail(WV_E_STATE, "wv_rollback: the source was changed after the checkpoint");
+    if (spec_.active && ckpt_.spec_generation != spec_.generation)
+        return fail(WV_E_STATE, "wv_rollback: the spectrum plan was set after the checkpoint (its sums have no copy to go back to)");
     WV_HIP(hipMemcpyAsync(field_[cur_], ckpt_.field[0], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(field_[prv_], ckpt_.field[1], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(fmem_, ckpt_.fmem, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
+    if (spec_.active) {  // sums and count back; what is staged is of abandoned steps
+        const int rc = spectrum_rollback();
+        if (rc) return rc;
+    }
     if (dir_.active) {
         WV_HIP(hipMemcpyAsync(dir_.velocity, ckpt_.dir_velocity, (size_t)dir_.n * 3 * sizeof(double), hipMemcpyDeviceToDevice, stream_));
         dir_.log.resize(ckpt_.dir_log_size);

@@ -543,6 +543,8 @@ void Engine<Real>::release() {
     comm_.reset();
     if (stream_) (void)hipStreamSynchronize(stream_);
     snapshot_release(snap_);
+    spectrum_release(spec_);
+    if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
     for (auto& e : events_) (void)hipEventDestroy(e);
     events_.clear();
     for (auto& e : halo_events_)

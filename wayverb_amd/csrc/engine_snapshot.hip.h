@@ -47,6 +47,8 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
     // scope (as for wv_checkpoint), refused rather than half done.
     if (opt_.ghost_lo || opt_.ghost_hi || (comm_ && comm_->nranks() > 1))
         return fail(WV_E_STATE, "wv_set_snapshots: not on a slab of a chain (one domain only)");
+    // (a spectrum plan cuts the passes at its own steps: one consumer of capture steps at a time, engine_spectrum.hip.h)
+    if (spec_.active) return fail(WV_E_STATE, "wv_set_snapshots: a spectrum plan is active (wv_set_spectrum(e, NULL, NULL) stops it); the two plans exclude each other");
     wv::SnapshotBox box;
     box.x0 = plan->x0, box.y0 = plan->y0, box.z0 = plan->z0;
     box.nx = plan->nx, box.ny = plan->ny, box.nz = plan->nz;
@@ -95,6 +97,30 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
     return WV_OK;
 }
 
+// snapshot_gather_kernel on the compute stream: `box` of the field `current` -> the dense floats at `dst` (`wide`: four nodes per
+// lane, snapshot_kernels.hip.h).  The one launch site of the kernel: a snapshot plan's captures and a spectrum plan's
+// (engine_spectrum.hip.h) are the same launch.
+template <typename Real>
+int Engine<Real>::launch_snapshot_gather(const wv::SnapshotBox& box, bool wide, float* dst) {
+    wv::SnapshotArgs<Real> a{};
+    a.field = field_[cur_];
+    a.dst = dst;
+    a.pitch = pitch_;
+    a.mesh_ny = ny_;
+    a.x0 = box.x0, a.y0 = box.y0, a.z0 = box.z0;
+    a.nx = box.nx, a.ny = box.ny, a.nz = box.nz;
+    a.sx = box.sx, a.sy = box.sy, a.sz = box.sz;
+    // grid: x over the items of a dense plane, y over the planes (both with a stride loop behind them)
+    const uint64_t items = (wide ? (uint64_t)box.nx / 4 : (uint64_t)box.nx) * (uint64_t)box.ny;
+    const dim3 grid((unsigned)std::min<uint64_t>((items + 255) / 256, 1u << 14), (unsigned)std::min(box.nz, 1024));
+    if (wide)
+        hipLaunchKernelGGL((wv::snapshot_gather_kernel<Real, true>), grid, dim3(256), 0, stream_, a);
+    else
+        hipLaunchKernelGGL((wv::snapshot_gather_kernel<Real, false>), grid, dim3(256), 0, stream_, a);
+    WV_HIP(hipGetLastError());
+    return WV_OK;
+}
+
 // The capture of `step`, which the field `current` holds once everything enqueued on the compute stream so far has run.
 template <typename Real>
 int Engine<Real>::snapshot_capture(uint64_t step) {
@@ -104,24 +130,10 @@ int Engine<Real>::snapshot_capture(uint64_t step) {
     if ((int)s.pending.size() >= s.slots) return fail(WV_E_STATE, "wv_run: the snapshot ring is full");
     // the slot's previous copy must have left it: a stream wait, never a host wait
     if (s.used[slot]) WV_HIP(hipStreamWaitEvent(stream_, s.copied[slot], 0));
-    wv::SnapshotArgs<Real> a{};
-    a.field = field_[cur_];
-    a.dst = s.dev[slot];
-    a.pitch = pitch_;
-    a.mesh_ny = ny_;
-    a.x0 = s.box.x0, a.y0 = s.box.y0, a.z0 = s.box.z0;
-    a.nx = s.box.nx, a.ny = s.box.ny, a.nz = s.box.nz;
-    a.sx = s.box.sx, a.sy = s.box.sy, a.sz = s.box.sz;
-    // grid: x over the items of a dense plane, y over the planes (both with a stride loop behind them)
-    const uint64_t items = (s.wide ? (uint64_t)s.box.nx / 4 : (uint64_t)s.box.nx) * (uint64_t)s.box.ny;
-    const dim3 grid((unsigned)std::min<uint64_t>((items + 255) / 256, 1u << 14), (unsigned)std::min(s.box.nz, 1024));
     s.timed[slot] = timing;
     if (timing) WV_HIP(hipEventRecord(s.begun[slot], stream_));
-    if (s.wide)
-        hipLaunchKernelGGL((wv::snapshot_gather_kernel<Real, true>), grid, dim3(256), 0, stream_, a);
-    else
-        hipLaunchKernelGGL((wv::snapshot_gather_kernel<Real, false>), grid, dim3(256), 0, stream_, a);
-    WV_HIP(hipGetLastError());
+    const int rc = launch_snapshot_gather(s.box, s.wide, s.dev[slot]);
+    if (rc) return rc;
     WV_HIP(hipEventRecord(s.captured[slot], stream_));
     WV_HIP(hipStreamWaitEvent(s.copy_stream, s.captured[slot], 0));
     WV_HIP(hipMemcpyAsync(s.host[slot], s.dev[slot], (size_t)s.elems * sizeof(float), hipMemcpyDeviceToHost, s.copy_stream));

@@ -37,6 +37,7 @@ EXPORTS = [
     "wv_scene_mesh_create_engine", "wv_scene_mesh_destroy", "wv_checkpoint", "wv_rollback", "wv_drop_checkpoint", "wv_host_register", "wv_host_unregister",
     "wv_compressed_waveguide_run", "wv_make_transparent", "wv_set_snapshots", "wv_snapshot_count", "wv_fetch_snapshots",
     "wv_set_directional_receivers", "wv_fetch_directional", "wv_directional_accumulate",
+    "wv_set_spectrum", "wv_spectrum_count", "wv_fetch_spectrum", "wv_spectrum_twiddle",
 ]
 
 
@@ -71,6 +72,13 @@ class WvSnapshotPlan(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
                 ("sx", C.c_int32), ("sy", C.c_int32), ("sz", C.c_int32), ("first_step", C.c_uint64), ("period", C.c_uint64),
                 ("keep", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WvSpectrumPlan(C.Structure):
+    """wv_spectrum_plan (include/wayverb_amd.h): the snapshot plan's box, strides and cadence, and the number of frequencies."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("sx", C.c_int32), ("sy", C.c_int32), ("sz", C.c_int32), ("first_step", C.c_uint64), ("period", C.c_uint64),
+                ("n_freqs", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 # Tuning applied to every engine this module creates unless the call says otherwise: {field of wv_tuning: value}, plus
@@ -175,6 +183,11 @@ def load_library():
     lib.wv_set_snapshots.argtypes = [C.c_void_p, C.POINTER(WvSnapshotPlan)]
     lib.wv_snapshot_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.wv_fetch_snapshots.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.wv_set_spectrum.argtypes = [C.c_void_p, C.POINTER(WvSpectrumPlan), C.c_void_p]
+    lib.wv_spectrum_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.wv_fetch_spectrum.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.wv_spectrum_twiddle.argtypes = [C.c_double, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.wv_spectrum_twiddle.restype = None
     lib.wv_set_directional_receivers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_double]
     lib.wv_fetch_directional.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.wv_directional_accumulate.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
@@ -185,6 +198,14 @@ def load_library():
 def _check(rc):
     if rc != WV_OK:
         raise WaveguideError("wayverb_amd error %d: %s" % (rc, load_library().wv_last_error().decode()))
+
+
+def spectrum_twiddle(cycles_per_step, step):
+    """wv_spectrum_twiddle: (cos, sin) of 2 pi frac(cycles_per_step * step), the very doubles the engine folds a capture of `step`
+    with at that frequency (Engine.set_spectrum)."""
+    c, s = C.c_double(), C.c_double()
+    load_library().wv_spectrum_twiddle(float(cycles_per_step), int(step), C.byref(c), C.byref(s))
+    return c.value, s.value
 
 
 def raise_for_flag(flag):
@@ -349,6 +370,7 @@ class Engine:
         self.n_recv = 0
         self.n_directional = 0
         self.snapshot_shape = None
+        self.spectrum_shape = None
 
     @classmethod
     def from_handle(cls, handle, mesh, precision):
@@ -362,6 +384,7 @@ class Engine:
         eng.n_recv = 0
         eng.n_directional = 0
         eng.snapshot_shape = None
+        eng.spectrum_shape = None
         return eng
 
     def close(self):
@@ -505,11 +528,19 @@ class Engine:
             _check(self.lib.wv_set_snapshots(self.h, None))
             self.snapshot_shape = None
             return None
+        plan = WvSnapshotPlan()
+        taken = self._fill_box(plan, box, stride)
+        plan.first_step, plan.period, plan.keep = int(first_step), int(period), int(keep)
+        _check(self.lib.wv_set_snapshots(self.h, C.byref(plan)))
+        self.snapshot_shape = (taken[2], taken[1], taken[0])
+        return self.snapshot_shape
+
+    def _fill_box(self, plan, box, stride):
+        """(origin, extent, stride) -> the plan's first node, nodes taken and strides; returns the nodes taken (x, y, z)."""
         dims = self.mesh.dims
         origin, extent = ((0, 0, 0), None) if isinstance(box, str) and box == "mesh" else box
         extent = tuple(extent) if extent is not None else (None, None, None)
         stride = (stride,) * 3 if np.isscalar(stride) else tuple(stride)
-        plan = WvSnapshotPlan()
         taken = []
         for axis in range(3):
             ext = dims[axis] - origin[axis] if extent[axis] is None else extent[axis]
@@ -518,10 +549,7 @@ class Engine:
         plan.x0, plan.y0, plan.z0 = (int(v) for v in origin)
         plan.nx, plan.ny, plan.nz = taken
         plan.sx, plan.sy, plan.sz = (int(v) for v in stride)
-        plan.first_step, plan.period, plan.keep = int(first_step), int(period), int(keep)
-        _check(self.lib.wv_set_snapshots(self.h, C.byref(plan)))
-        self.snapshot_shape = (taken[2], taken[1], taken[0])
-        return self.snapshot_shape
+        return taken
 
     def snapshot_count(self):
         """wv_snapshot_count: (snapshots taken since the plan was set, index of the oldest one still held)."""
@@ -539,6 +567,38 @@ class Engine:
         steps = np.empty(n, dtype=np.uint64)
         _check(self.lib.wv_fetch_snapshots(self.h, int(first), int(n), out.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p)))
         return out, steps
+
+    # ---- field spectra accumulated on the device while wv_run goes on -------------------------------
+    def set_spectrum(self, freqs, box="mesh", stride=1, first_step=0, period=1):
+        """wv_set_spectrum.  `freqs`: K frequencies in CYCLES PER STEP, 0 .. 0.5 (K <= 64); `box`, `stride`, `first_step`, `period` as
+        for set_snapshots.  At every plan step the engine captures the box as a snapshot would and adds it, on the device, to a running
+        Fourier sum per node and frequency: X_k = sum_j p_j exp(-2 pi i f_k n_j) over the captures j of steps n_j, in capture order, with
+        the twiddles spectrum_twiddle gives -- a NumPy loop over the snapshots of the same plan reproduces it bit for bit.  No window.
+        Excludes a snapshot plan.  set_spectrum(None) stops and forgets.  Returns the shape (K, nz, ny, nx)."""
+        if freqs is None:
+            _check(self.lib.wv_set_spectrum(self.h, None, None))
+            self.spectrum_shape = None
+            return None
+        f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        plan = WvSpectrumPlan()
+        taken = self._fill_box(plan, box, stride)
+        plan.first_step, plan.period, plan.n_freqs = int(first_step), int(period), f.shape[0]
+        _check(self.lib.wv_set_spectrum(self.h, C.byref(plan), f.ctypes.data_as(C.c_void_p)))
+        self.spectrum_shape = (f.shape[0], taken[2], taken[1], taken[0])
+        return self.spectrum_shape
+
+    def spectrum_count(self):
+        """wv_spectrum_count: (captures of completed steps since the plan was set, the step of the last of them)."""
+        captures, last = C.c_uint64(), C.c_uint64()
+        _check(self.lib.wv_spectrum_count(self.h, C.byref(captures), C.byref(last)))
+        return captures.value, last.value
+
+    def fetch_spectrum(self):
+        """wv_fetch_spectrum: (complex128[K, nz, ny, nx], captures in it).  The plan keeps running."""
+        out = np.zeros(tuple(self.spectrum_shape or (0, 0, 0, 0)), dtype=np.complex128)   # (no plan: the library says so)
+        captures = C.c_uint64()
+        _check(self.lib.wv_fetch_spectrum(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
+        return out, captures.value
 
     def step_count(self):
         s = C.c_uint64()
@@ -570,6 +630,7 @@ class Engine:
     QUERY_TRIPLE_MARCH_NS, QUERY_TRIPLE_MARCH_TIMED, QUERY_BOUNDARY3_NS, QUERY_FIXUP3_NS, QUERY_TRIPLE_PARTS_TIMED = 16, 17, 18, 19, 20
     QUERY_SNAPSHOT_NS, QUERY_SNAPSHOT_BYTES, QUERY_SNAPSHOTS_TAKEN = 21, 22, 23
     QUERY_WIDE_GATHERS, QUERY_DIRECTIONAL_LAUNCHES = 24, 25
+    QUERY_SPECTRUM_CAPTURES, QUERY_SPECTRUM_FOLDS, QUERY_SPECTRUM_NS = 26, 27, 28
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

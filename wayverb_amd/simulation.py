@@ -103,12 +103,12 @@ def compute_voxels_and_mesh(vertices, triangles, surface_absorptions, anchor, sa
     coeffs = np.zeros(absorptions.shape[0], dtype=M.coefficients_dtype)
     for i, a in enumerate(absorptions):
         coeffs[i] = F.surface_coefficients(a, speed_of_sound, float(spacing))   # mesh.cpp:126-138
-    mesh = M.Mesh(dims, nodes, coeffs, b[0], b[1], b[2], spacing=float(spacing))
+    mesh = M.Mesh(dims, nodes, coeffs, b[0], b[1], b[2], spacing=float(spacing), min_corner=tuple(float(c) for c in c0))
     return VoxelsAndMesh(vox, (c0, c1), side, vertices, triangles, mesh, c0, absorptions)
 
 
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
-              device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None):
+              device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None):
     """canonical (single band): hard source at `source`, directional receiver at `receiver`, for
     ceil(sample_rate * simulation_time) steps.  Returns [(directional records, sample_rate,
     (0, cutoff))] -- the bandpass_band list waveguide::postprocess takes -- or None when stopped early.
@@ -119,11 +119,20 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     of the field on the device while the run goes on (what the reference's visualiser takes from the per-step callback,
     src/combined/src/engine.cpp:158-169); the return value is then (bands, (float32[n, nz, ny, nx], steps[n])), or None when stopped
     early.  A snapshot of step s is the field after s completed steps: the hard source's sample of step s, which the reference's
-    callback finds in the source node, is not in it yet (the C++ mirror, cl_mirror_cadence(), puts it there).  One domain only."""
+    callback finds in the source node, is not in it yet (the C++ mirror, cl_mirror_cadence(), puts it there).  One domain only.
+    `spectrum`: dict(freqs_hz=[...], box=..., stride=..., first_step=..., period=...) -- the engine Fourier-transforms that part of
+    the field on the device at those frequencies while the run goes on (Engine.set_spectrum; Hz become cycles per step with the
+    run's sample rate); the return value is then (bands, (complex128[K, nz, ny, nx], captures)).  One domain only, and not together
+    with `snapshots`."""
     if snapshots is not None and slabs > 1:
         raise ValueError("snapshots are taken on one domain only (slabs=1)")
+    if spectrum is not None and slabs > 1:
+        raise ValueError("a spectrum is accumulated on one domain only (slabs=1)")
+    if spectrum is not None and snapshots is not None:
+        raise ValueError("a spectrum plan and a snapshot plan exclude each other")
     mesh = vm.mesh
     sample_rate = compute_sample_rate(mesh.spacing, environment.speed_of_sound)
+    spectrum_plan = spectrum_plan_arguments(spectrum, sample_rate) if spectrum is not None else None
 
     def mesh_index(pt):
         idx = vm.compute_index(pt)
@@ -148,16 +157,42 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
         try:
             if snapshots is not None:
                 eng.set_snapshots(**snapshots)
+            if spectrum_plan is not None:
+                eng.set_spectrum(**spectrum_plan)
             done, traces = E.run_fast(eng, E.SOURCE_HARD, mesh_index(source), signal, [receiver_index] + list(neighbours),
                                       keep_going=keep_going)
             taken = eng.fetch_snapshots() if snapshots is not None else None
+            if spectrum_plan is not None:
+                taken = eng.fetch_spectrum()
         finally:
             eng.close()
     if done != ideal_steps:
         return None
     directional = P.directional_receiver(traces, mesh.spacing, sample_rate, environment.ambient_density)
     bands = [(directional, sample_rate, (0.0, float(cutoff)))]
-    return bands if snapshots is None else (bands, taken)
+    return bands if snapshots is None and spectrum is None else (bands, taken)
+
+
+def spectrum_plan_arguments(spectrum, sample_rate):
+    """canonical's `spectrum` dict -> keyword arguments of Engine.set_spectrum: freqs_hz / sample_rate = cycles per step.  The field is
+    sampled every `period` steps, so a frequency above sample_rate / (2 * period) would fold back onto a lower one: refused."""
+    plan = dict(spectrum)
+    if "freqs_hz" not in plan:
+        raise ValueError("spectrum: freqs_hz=[...] is required")
+    freqs_hz = np.atleast_1d(np.asarray(plan.pop("freqs_hz"), dtype=np.float64))
+    period = int(plan.get("period", 1))
+    if period < 1:
+        raise ValueError("spectrum: period must be >= 1")
+    nyquist = float(sample_rate) / 2.0 / period
+    for f in freqs_hz:
+        if not np.isfinite(f):
+            raise ValueError("spectrum: %r is not a frequency" % float(f))
+        if not 0.0 <= f <= nyquist:
+            alias = abs(f - round(f * period / sample_rate) * sample_rate / period)
+            raise ValueError("spectrum: %.6g Hz is outside 0 .. %.6g Hz (half the sample rate %.6g Hz divided by period %d): "
+                             "sampled every %d steps it aliases to %.6g Hz" % (f, nyquist, sample_rate, period, period, alias))
+    plan["freqs"] = freqs_hz / float(sample_rate)
+    return plan
 
 
 def canonical_many(vm, source, receivers, environment, cutoff, usable_portion, simulation_time, precision="f64",
@@ -255,24 +290,29 @@ def canonical_multiband(vm, source, receiver, environment, bands, cutoff, usable
 
 def impulse_response(vertices, triangles, surface_absorptions, source, receiver, cutoff=200.0, usable_portion=0.6,
                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
-                     pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None):
+                     pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None):
     """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio.
     `snapshots`: a function mesh -> keyword arguments of Engine.set_snapshots (the mesh's size is not known before it is built),
-    or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member."""
+    or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member.
+    `spectrum`: a function mesh -> canonical's `spectrum` dict, or the dict; the fourth member is then (spectrum, captures)."""
     environment = environment or Environment()
     vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
-    if snapshots is None:
+    if spectrum is not None and snapshots is not None:
+        raise ValueError("a spectrum plan and a snapshot plan exclude each other")
+    if snapshots is None and spectrum is None:
         bands = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device)
         taken = None
     else:
-        plan = snapshots(vm.mesh) if callable(snapshots) else snapshots
-        both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, snapshots=plan)
+        which = "snapshots" if snapshots is not None else "spectrum"
+        plan = snapshots if snapshots is not None else spectrum
+        plan = plan(vm.mesh) if callable(plan) else plan
+        both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, **{which: plan})
         if both is None:
             raise RuntimeError("the waveguide run was stopped early")
         bands, taken = both
     audio = P.postprocess(bands, method, pointing, shape, environment.acoustic_impedance, output_sample_rate)
-    return (audio, bands, vm) if snapshots is None else (audio, bands, vm, taken)
+    return (audio, bands, vm) if taken is None else (audio, bands, vm, taken)
 
 
 def impulse_responses(vertices, triangles, surface_absorptions, source, receivers, cutoff=200.0, usable_portion=0.6,
