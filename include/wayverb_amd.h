@@ -379,6 +379,62 @@ int wv_spectrum_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
 int wv_fetch_spectrum(wv_engine* e, double* dst /* [n_freqs][nz][ny][nx][2]: complex128 */, uint64_t* captures);
 void wv_spectrum_twiddle(double cycles_per_step, uint64_t step, double* c, double* s);
 
+/* ---- energy decay maps: time-binned field energy folded on the device -------------------------- */
+/* How long sound lingers, and where -- the energy decay curve and the reverberation times (EDT, T20, T30) at every node of an
+ * audience plane, the level map under broadband excitation -- follows from the squared field summed over time.  The reference
+ * computes it for one receiver trace at a time (src/core/include/core/schroeder.h).  With snapshots alone every capture crosses the
+ * link and the host array grows with the run; a decay plan has the engine capture the box as a snapshot plan would (the same box /
+ * stride semantics, the same cadence) and accumulate, per node taken, the energy of the captures in n_bins TIME BINS ON THE DEVICE.
+ * Nothing crosses the link until the caller fetches the n_bins doubles per node.  The backward sums of the bins are the Schroeder
+ * integral exactly at the bin edges (only the order of summation differs from the per-sample curve): wayverb_amd/decay.py derives
+ * the decay curve and the decay times from them with the reference's own regression.
+ *
+ * Definition.  p_j is the float a snapshot of plan step n_j holds for the node: the field after exactly n_j completed steps, a
+ * double rounded to nearest (the snapshot block above, unchanged).  Capture j counts the committed captures since the plan was set
+ * (0, 1, ...) and goes to bin
+ *     b(j) = min(j / bin_captures, n_bins - 1)                      (integer division)
+ * so every bin holds bin_captures captures but the last, which is open-ended: the backward sums stay exact tail sums at every
+ * earlier edge however long the run.  The sums start at +0.0 and run in capture order, in double:
+ *     E[b(j)] = E[b(j)] + (double)p_j * (double)p_j
+ * The product of two converted floats is exact in double; the one rounding per capture is the sum's.  A loop over the snapshots of
+ * the same plan that evaluates `E[b] = E[b] + p * p` on float64 arrays therefore reproduces the bins BIT FOR BIT.
+ *
+ *   - 1 <= n_bins <= 4096 and bin_captures >= 1; otherwise, and for a box that leaves the mesh, a zero stride or a zero period:
+ *     WV_E_INVALID_ARGUMENT
+ *   - everything (the stage of 16 captures, 64 bytes per node; the bins, 8 n_bins bytes per node; two tables of 16 bin indices) is
+ *     allocated when the plan is set: with no room the call answers WV_E_HIP and leaves the engine and any earlier plan untouched.
+ *     A new plan replaces the old one and forgets its bins; a NULL plan stops, forgets and frees (as does wv_destroy)
+ *   - one domain only: a slab of a chain answers WV_E_STATE (the snapshot plan's reason), and wv_run_group refuses an engine with a
+ *     plan, as it does for the other plans
+ *   - a decay plan, a spectrum plan and a snapshot plan are EXCLUSIVE: each decides where passes end.  Each of the three setters
+ *     answers WV_E_STATE while another plan is active, and wv_last_error names the plan to stop
+ *   - after a run that stopped on a flag at step f (an overflow, or keep_going cleared) the bins hold exactly the captures of steps
+ *     <= f, and wv_decay_count says how many: a capture of a step that was never committed is never folded in
+ *   - wv_step / wv_swap capture nothing; plan steps they pass are passed, as for snapshots
+ *   - wv_checkpoint folds what is staged and copies the bins, the capture count and the next plan step aside (the copy is allocated
+ *     by the first checkpoint taken under a plan: WV_E_HIP, engine untouched, when there is no room); wv_rollback puts them back,
+ *     and the re-run reproduces the bins bitwise.  A plan set AFTER the checkpoint makes wv_rollback answer WV_E_STATE
+ *   - wv_fetch_decay may be called any time outside wv_run; it folds what is staged and leaves the plan running, so fetching
+ *     twice during a long run gives two consistent partial sums
+ *   - with no plan nothing is launched, allocated or waited for; with one the fields, receiver rows and flags are bit-identical to
+ *     a run without
+ *
+ * wv_decay_count: *captures = captures of completed steps since the plan was set, *last_step = the step of the last of them
+ * (either may be NULL).  wv_fetch_decay: the bins as float64 [n_bins][nz][ny][nx], *captures (may be NULL) = how many captures
+ * they hold. */
+typedef struct wv_decay_plan {
+    int32_t x0, y0, z0;    /* first node of the box */
+    int32_t nx, ny, nz;    /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;    /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step;   /* captures at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;       /* >= 1 */
+    uint32_t n_bins;       /* 1 .. 4096 */
+    uint32_t bin_captures; /* W >= 1: captures per bin (the last bin is open-ended) */
+} wv_decay_plan;
+int wv_set_decay(wv_engine* e, const wv_decay_plan* plan);
+int wv_decay_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
+int wv_fetch_decay(wv_engine* e, double* dst /* [n_bins][nz][ny][nx] */, uint64_t* captures);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */
@@ -413,7 +469,9 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *                            launches of the fold kernel (one per 16 captures at the most, plus those a fetch or a checkpoint asked
  *                            for), total time of the fold kernels that ran with kernel timing on.  (The capture kernel's time under
  *                            a spectrum plan is in neither this nor WV_QUERY_SNAPSHOT_NS: it is the snapshot plan's capture, whose
- *                            time DESIGN.md 4.7 has) */
+ *                            time DESIGN.md 4.7 has)
+ *   WV_QUERY_DECAY_CAPTURES, WV_QUERY_DECAY_FOLDS, WV_QUERY_DECAY_NS   the same three since wv_set_decay: captures of completed steps,
+ *                            launches of the decay plan's fold kernel, their total time with kernel timing on */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -430,7 +488,8 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
        WV_QUERY_TRIPLE_PARTS_TIMED = 20,
        WV_QUERY_SNAPSHOT_NS = 21, WV_QUERY_SNAPSHOT_BYTES = 22, WV_QUERY_SNAPSHOTS_TAKEN = 23,
        WV_QUERY_WIDE_GATHERS = 24, WV_QUERY_DIRECTIONAL_LAUNCHES = 25,
-       WV_QUERY_SPECTRUM_CAPTURES = 26, WV_QUERY_SPECTRUM_FOLDS = 27, WV_QUERY_SPECTRUM_NS = 28 };
+       WV_QUERY_SPECTRUM_CAPTURES = 26, WV_QUERY_SPECTRUM_FOLDS = 27, WV_QUERY_SPECTRUM_NS = 28,
+       WV_QUERY_DECAY_CAPTURES = 29, WV_QUERY_DECAY_FOLDS = 30, WV_QUERY_DECAY_NS = 31 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

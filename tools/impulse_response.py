@@ -61,6 +61,16 @@ def main():
     ap.add_argument("--spectrum-plane", default=None, help="z=<metres>: the height of that plane (default: the receiver's)")
     ap.add_argument("--spectrum-out", default="spectrum.npz", help="the complex maps go here: spectrum complex128[K, ny, nx], freqs_hz, "
                                                                    "captures, plane (node index), z (metres of that plane)")
+    ap.add_argument("--decay-map", nargs="?", const="", default=None, metavar="z=METRES",
+                    help="sum the squared field of one horizontal plane into time bins on the device while the run goes on "
+                         "(Engine.set_decay; single-band runs) and write EDT / T20 / T30 and level maps of it; z=<metres>: the height "
+                         "of that plane (default: the receiver's)")
+    ap.add_argument("--decay-bin-ms", type=float, default=10.0, help="the length of a time bin in milliseconds")
+    ap.add_argument("--decay-every", type=int, default=3, help="capture every k-th step (3 keeps every pass a three-step pass; the "
+                                                               "levels then lie 10 log10(k) dB low, the decay times do not change)")
+    ap.add_argument("--decay-out", default="decay.npz", help="the maps go here: bins float64[n_bins, ny, nx], edt_s / t20_s / t30_s and "
+                                                             "their _r, level_db, edc_db, sample_rate, bin_captures, period, captures, "
+                                                             "plane, origin (metres of the plane's first node), spacing")
     args = ap.parse_args()
 
     bands = None
@@ -124,11 +134,32 @@ def main():
                 ap.error("--spectrum-plane: z=%g m is outside the mesh" % height)
             spectrum_plane.update(plane=plane, z=mesh.min_corner[2] + plane * mesh.spacing)
             return dict(freqs_hz=freqs_hz, box=((0, 0, plane), (None, None, 1)))
+    decay = None
+    if args.decay_map is not None:
+        if bands or snapshots is not None or spectrum is not None:
+            ap.error("--decay-map: single-band runs without --snapshots or --spectrum")
+        if args.decay_map and not args.decay_map.startswith("z="):
+            ap.error("--decay-map takes z=<metres>")
+        if args.decay_every < 1 or not args.decay_bin_ms > 0:
+            ap.error("--decay-every must be >= 1 and --decay-bin-ms positive")
+        decay_height = float(args.decay_map[2:]) if args.decay_map else args.receiver[2]
+        decay_plane = {}
+
+        def decay(mesh, rate):
+            plane = int(round((decay_height - mesh.min_corner[2]) / mesh.spacing))
+            if not 0 <= plane < mesh.dims[2]:
+                ap.error("--decay-map: z=%g m is outside the mesh" % decay_height)
+            captures = int(np.ceil(rate * args.seconds)) // args.decay_every + 1
+            per_bin = max(1, int(round(args.decay_bin_ms * 1e-3 * rate / args.decay_every)))
+            n_bins = max(1, min(4096, -(-captures // per_bin)))
+            decay_plane.update(plane=plane, rate=rate, per_bin=per_bin,
+                               origin=np.asarray(mesh.min_corner, dtype=np.float64) + np.array([0.0, 0.0, plane * mesh.spacing]))
+            return dict(n_bins=n_bins, bin_captures=per_bin, box=((0, 0, plane), (None, None, 1)), period=args.decay_every)
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
     if len(receivers) > 1:
-        if bands or snapshots is not None or spectrum is not None:
-            ap.error("several --receiver: single-band runs without --snapshots or --spectrum")
+        if bands or snapshots is not None or spectrum is not None or decay is not None:
+            ap.error("several --receiver: single-band runs without --snapshots, --spectrum or --decay-map")
         audios, per, positions, vm = W.impulse_responses(v, t, absorptions, args.source, receivers, args.cutoff, args.usable_portion,
                                                          args.seconds, args.rate, method=method, pointing=args.pointing,
                                                          shape=args.mic_shape or 0.0, precision=args.precision)
@@ -153,7 +184,18 @@ def main():
         audio_etc = W.impulse_response(v, t, absorptions, args.source, args.receiver, args.cutoff,
                                        args.usable_portion, args.seconds, args.rate, method=method,
                                        pointing=args.pointing, shape=args.mic_shape or 0.0,
-                                       precision=args.precision, snapshots=snapshots, spectrum=spectrum)
+                                       precision=args.precision, snapshots=snapshots, spectrum=spectrum, decay=decay)
+        if decay is not None:
+            from wayverb_amd import decay as D
+            bins, captures = audio_etc[3]
+            maps = D.decay_maps(bins[:, 0], decay_plane["per_bin"], args.decay_every, decay_plane["rate"])
+            np.savez(args.decay_out, bins=bins[:, 0], sample_rate=decay_plane["rate"], bin_captures=decay_plane["per_bin"],
+                     period=args.decay_every, captures=captures, plane=decay_plane["plane"], origin=decay_plane["origin"],
+                     spacing=audio_etc[2].mesh.spacing, **maps)
+            t30 = maps["t30_s"][np.isfinite(maps["t30_s"])]
+            print("wrote decay maps of plane z=%d (%d bins of %d captures, %d captures; median T30 %s) to %s"
+                  % (decay_plane["plane"], bins.shape[0], decay_plane["per_bin"], captures,
+                     "%.3f s" % np.median(t30) if t30.size else "not defined", args.decay_out))
         if spectrum is not None:
             maps, captures = audio_etc[3]
             np.savez(args.spectrum_out, spectrum=maps[:, 0], freqs_hz=np.array(freqs_hz), captures=captures,

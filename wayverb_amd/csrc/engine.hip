@@ -15,6 +15,7 @@
 #include "engine_io.hip.h"
 #include "engine_snapshot.hip.h"
 #include "engine_spectrum.hip.h"
+#include "engine_decay.hip.h"
 #include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
@@ -221,6 +222,18 @@ void wv_spectrum_twiddle(double cycles_per_step, uint64_t step, double* c, doubl
     wv::spectrum_twiddle(cycles_per_step, step, &cc, &ss);
     if (c) *c = cc;
     if (s) *s = ss;
+}
+int wv_set_decay(wv_engine* e, const wv_decay_plan* plan) {
+    WV_NEED(e);
+    return e->set_decay(plan);
+}
+int wv_decay_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
+    WV_NEED(e);
+    return e->decay_count(captures, last_step);
+}
+int wv_fetch_decay(wv_engine* e, double* dst, uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_decay(dst, captures);
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

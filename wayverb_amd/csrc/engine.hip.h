@@ -19,6 +19,9 @@
 //   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape
 //   engine_spectrum.hip.h  field spectra accumulated on the device while a run goes on (wv_set_spectrum): plan, stage, fold, fetch
 //   spectrum_plan.h      (host only, no HIP) free slots of the stage, when a fold is due, which captures survive a stop, sizes
+//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the spectrum and the decay plan
+//   engine_decay.hip.h   time-binned field energy accumulated on the device while a run goes on (wv_set_decay): plan, stage, fold, fetch
+//   decay_plan.h         (host only, no HIP) the bin of a capture, sizes, the fold's traffic model
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -27,6 +30,8 @@
 #include "march_plan.h"
 #include "snapshot_plan.h"
 #include "spectrum_plan.h"
+#include "decay_plan.h"
+#include "capture_stage.h"
 
 #include "boundary_kernels.hip.h"
 #include "pair_kernels.hip.h"
@@ -34,6 +39,7 @@
 #include "plane_kernels.hip.h"
 #include "snapshot_kernels.hip.h"
 #include "spectrum_kernels.hip.h"
+#include "decay_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -176,6 +182,11 @@ public:
     int spectrum_count(uint64_t* captures, uint64_t* last_step) override;
     int fetch_spectrum(double* dst, uint64_t* captures) override;
     bool spectrum_active() const override { return spec_.active; }
+    // ---- engine_decay.hip.h
+    int set_decay(const wv_decay_plan* plan) override;
+    int decay_count(uint64_t* captures, uint64_t* last_step) override;
+    int fetch_decay(double* dst, uint64_t* captures) override;
+    bool decay_active() const override { return decay_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -400,6 +411,9 @@ private:
         double* spec_acc = nullptr;  // the spectrum plan's sums (engine_spectrum.hip.h), allocated by the first checkpoint under a plan
         size_t spec_bytes = 0;
         uint64_t spec_generation = 0, spec_captures = 0, spec_last_step = 0, spec_next = 0;
+        double* decay_bins = nullptr;  // the decay plan's bins (engine_decay.hip.h), allocated by the first checkpoint under a plan
+        size_t decay_bytes = 0;
+        uint64_t decay_generation = 0, decay_captures = 0, decay_last_step = 0, decay_next = 0;
     } ckpt_;
     // field snapshots (engine_snapshot.hip.h): a ring of device slots the capture kernel fills on the compute stream, each copied to its
     // page-locked twin on a stream of its own, and the log of the snapshots the host holds
@@ -450,8 +464,7 @@ private:
         wv::SnapshotBox box;
         std::vector<double> freqs;      // cycles per step, [K]
         uint64_t generation = 0;        // bumped by every wv_set_spectrum (a checkpoint remembers which plan it saw)
-        uint64_t next = wv::kNoSnapshotStep;       // the next plan step not yet captured
-        uint64_t batch_end = wv::kNoSnapshotStep;  // the plan step at which the batch being planned ends at the latest
+        wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
         uint64_t nodes = 0;             // B: nodes taken
         float* stage = nullptr;         // [T][B]
         double* acc = nullptr;          // [K][2][B]
@@ -461,28 +474,53 @@ private:
         hipEvent_t folded_ev[2] = {nullptr, nullptr};  // behind it: the host may write the table again
         bool table_used[2] = {false, false}, timed[2] = {false, false};
         int table = 0;                  // the table the next fold writes
-        std::vector<uint64_t> steps;    // the steps of the staged captures, slot by slot
-        int committed = 0;              // how many of them are of committed steps (all of them between batches)
-        uint64_t folded = 0;            // captures in the sums
-        uint64_t last_step = 0;         // the step of the last committed capture
         uint64_t folds = 0;             // WV_QUERY_SPECTRUM_FOLDS
         double kernel_ms = 0;           // fold kernels' time (kernel timing on)
     } spec_;
     static void spectrum_release(Spectrum& s);
     int spectrum_capture(uint64_t step);
     int spectrum_drain_timing(int table);
-    void spectrum_drop_uncommitted();
     int spectrum_fold();
-    void spectrum_commit(uint64_t last_good_step);
     int spectrum_plan_batch();
     int spectrum_begin_run();
     int spectrum_checkpoint();
     int spectrum_rollback();
-    // whichever plan is active decides where passes end (engine_batch.hip.h): the two exclude each other
-    bool capture_plan_active() const { return snap_.active || spec_.active; }
-    uint64_t capture_next() const { return snap_.active ? snap_.next : spec_.active ? spec_.next : wv::kNoSnapshotStep; }
-    uint64_t capture_batch_end() const { return snap_.active ? snap_.batch_end : spec_.active ? spec_.batch_end : wv::kNoSnapshotStep; }
-    int capture_step(uint64_t step) { return snap_.active ? snapshot_capture(step) : spectrum_capture(step); }
+    // energy decay maps (engine_decay.hip.h): the device-only stage the capture kernel fills on the compute stream, the time-binned
+    // energies the fold kernel accumulates, two tables of the staged captures' bins (page-locked, and their device copies) the host
+    // writes in turn
+    struct Decay {
+        bool active = false, gather_wide = false, fold_wide = false;
+        wv_decay_plan plan{};
+        wv::SnapshotBox box;
+        uint64_t generation = 0;        // bumped by every wv_set_decay (a checkpoint remembers which plan it saw)
+        wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
+        uint64_t nodes = 0;             // B: nodes taken
+        float* stage = nullptr;         // [T][B]
+        double* bins = nullptr;         // [n_bins][B]
+        int32_t* table_host[2] = {nullptr, nullptr};
+        int32_t* table_dev[2] = {nullptr, nullptr};
+        hipEvent_t begun[2] = {nullptr, nullptr};      // before the fold that uses the table (kernel timing)
+        hipEvent_t folded_ev[2] = {nullptr, nullptr};  // behind it: the host may write the table again
+        bool table_used[2] = {false, false}, timed[2] = {false, false};
+        int table = 0;                  // the table the next fold writes
+        uint64_t folds = 0;             // WV_QUERY_DECAY_FOLDS
+        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
+    } decay_;
+    static void decay_release(Decay& d);
+    int decay_capture(uint64_t step);
+    int decay_drain_timing(int table);
+    int decay_fold();
+    int decay_plan_batch();
+    int decay_begin_run();
+    int decay_checkpoint();
+    int decay_rollback();
+    // whichever plan is active decides where passes end (engine_batch.hip.h): the three exclude each other
+    bool capture_plan_active() const { return snap_.active || spec_.active || decay_.active; }
+    uint64_t capture_next() const { return snap_.active ? snap_.next : spec_.active ? spec_.st.next : decay_.active ? decay_.st.next : wv::kNoSnapshotStep; }
+    uint64_t capture_batch_end() const {
+        return snap_.active ? snap_.batch_end : spec_.active ? spec_.st.batch_end : decay_.active ? decay_.st.batch_end : wv::kNoSnapshotStep;
+    }
+    int capture_step(uint64_t step) { return snap_.active ? snapshot_capture(step) : spec_.active ? spectrum_capture(step) : decay_capture(step); }
 };
 
 }  // namespace wv

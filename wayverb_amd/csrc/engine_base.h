@@ -96,6 +96,10 @@ struct wv_engine {
     virtual int spectrum_count(uint64_t* captures, uint64_t* last_step) = 0;
     virtual int fetch_spectrum(double* dst, uint64_t* captures) = 0;
     virtual bool spectrum_active() const = 0;
+    virtual int set_decay(const wv_decay_plan* plan) = 0;
+    virtual int decay_count(uint64_t* captures, uint64_t* last_step) = 0;
+    virtual int fetch_decay(double* dst, uint64_t* captures) = 0;
+    virtual bool decay_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;
     virtual int set_source(int kind, uint64_t node, const double* signal, uint64_t n) = 0;

@@ -151,7 +151,7 @@ uint64_t Engine<Real>::plan_batch(uint64_t remaining) {
     }
     // a snapshot step is the end of a pass, and a batch holds no more captures than the ring has free slots (snapshot_plan.h;
     // snapshot_plan_batch has set where this batch must end at the latest)
-    // (a spectrum plan's captures are a snapshot plan's, and cut the batches the same way: whichever plan is active)
+    // (a spectrum plan's and a decay plan's captures are a snapshot plan's, and cut the batches the same way: whichever plan is active)
     if (capture_plan_active()) batch = wv::snapshot_batch_limit(batch, steps_done, capture_batch_end());
     batch_can_fuse_ = !comm_ && io_nodes_plain() && opt_.tuning.fuse_pre_post != 0;
     (void)whole_step_ready();  // (looks at the class map once per source / receiver set: here, not inside a capture)
@@ -257,6 +257,9 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
     } else if (spec_.active) {  // (engine_spectrum.hip.h)
         const int rc = spectrum_begin_run();
         if (rc) return rc;
+    } else if (decay_.active) {  // (engine_decay.hip.h)
+        const int rc = decay_begin_run();
+        if (rc) return rc;
     }
     while (completed < n_steps && flag == 0) {
         // where this batch ends: it may hold captures for half the snapshot ring
@@ -265,6 +268,9 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
             if (rc) return rc;
         } else if (spec_.active) {  // ... or as many captures as the spectrum's stage has free slots, folded first when it has none
             const int rc = spectrum_plan_batch();
+            if (rc) return rc;
+        } else if (decay_.active) {  // ... the decay plan's stage likewise
+            const int rc = decay_plan_batch();
             if (rc) return rc;
         }
         uint64_t batch = plan_batch(n_steps - completed);
@@ -379,7 +385,8 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
         uint64_t good = 0;
         if ((rc = commit_batch(batch, flags_host_, &good, &flag))) return rc;
         if (snap_.active && good < batch) snapshot_discard_after(steps_done);  // (a flag stopped the run before those steps)
-        if (spec_.active) spectrum_commit(steps_done);  // the batch's captures of completed steps stay staged, the others are dropped
+        if (decay_.active) decay_.st.commit(steps_done);
+        if (spec_.active) spec_.st.commit(steps_done);  // the batch's captures of completed steps stay staged, the others are dropped
         completed += good;
     }
     // on return every snapshot of a completed step can be fetched
@@ -462,7 +469,7 @@ int Engine<Real>::query(int what, uint64_t* value) {
         case WV_QUERY_SNAPSHOTS_TAKEN: *value = snap_.taken; return WV_OK;
         case WV_QUERY_WIDE_GATHERS: *value = wide_gathers_; return WV_OK;
         case WV_QUERY_DIRECTIONAL_LAUNCHES: *value = dir_.launches; return WV_OK;
-        case WV_QUERY_SPECTRUM_CAPTURES: *value = spec_.folded + (uint64_t)spec_.committed; return WV_OK;
+        case WV_QUERY_SPECTRUM_CAPTURES: *value = spec_.st.captures(); return WV_OK;
         case WV_QUERY_SPECTRUM_FOLDS: *value = spec_.folds; return WV_OK;
         case WV_QUERY_SPECTRUM_NS: {
             DeviceGuard guard(device_);
@@ -471,6 +478,17 @@ int Engine<Real>::query(int what, uint64_t* value) {
                 if (rc) return rc;
             }
             *value = (uint64_t)(spec_.kernel_ms * 1e6 + 0.5);
+            return WV_OK;
+        }
+        case WV_QUERY_DECAY_CAPTURES: *value = decay_.st.captures(); return WV_OK;
+        case WV_QUERY_DECAY_FOLDS: *value = decay_.folds; return WV_OK;
+        case WV_QUERY_DECAY_NS: {
+            DeviceGuard guard(device_);
+            for (int b = 0; b < 2; ++b) {
+                const int rc = decay_drain_timing(b);
+                if (rc) return rc;
+            }
+            *value = (uint64_t)(decay_.kernel_ms * 1e6 + 0.5);
             return WV_OK;
         }
         default: return fail(WV_E_INVALID_ARGUMENT, "unknown query");

@@ -353,6 +353,7 @@ int Engine<Real>::checkpoint(int op) {
         if (ckpt_.fmem) (void)hipFree(ckpt_.fmem);
         if (ckpt_.dir_velocity) (void)hipFree(ckpt_.dir_velocity);
         if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
+        if (ckpt_.decay_bins) (void)hipFree(ckpt_.decay_bins);
         ckpt_ = Checkpoint{};
         return WV_OK;
     }
@@ -396,6 +397,12 @@ int Engine<Real>::checkpoint(int op) {
             if (rc) return rc;
         }
         ckpt_.spec_generation = spec_.generation;
+        // the decay plan's bins, count and next plan step (engine_decay.hip.h): likewise
+        if (decay_.active) {
+            const int rc = decay_checkpoint();
+            if (rc) return rc;
+        }
+        ckpt_.decay_generation = decay_.generation;
         WV_HIP(hipMemcpyAsync(ckpt_.field[0], field_[cur_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.field[1], field_[prv_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.fmem, fmem_, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
@@ -424,11 +431,17 @@ int Engine<Real>::checkpoint(int op) {
         return fail(WV_E_STATE, "wv_rollback: the source was changed after the checkpoint");
     if (spec_.active && ckpt_.spec_generation != spec_.generation)
         return fail(WV_E_STATE, "wv_rollback: the spectrum plan was set after the checkpoint (its sums have no copy to go back to)");
+    if (decay_.active && ckpt_.decay_generation != decay_.generation)
+        return fail(WV_E_STATE, "wv_rollback: the decay plan was set after the checkpoint (its bins have no copy to go back to)");
     WV_HIP(hipMemcpyAsync(field_[cur_], ckpt_.field[0], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(field_[prv_], ckpt_.field[1], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(fmem_, ckpt_.fmem, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
     if (spec_.active) {  // sums and count back; what is staged is of abandoned steps
         const int rc = spectrum_rollback();
+        if (rc) return rc;
+    }
+    if (decay_.active) {  // bins and count back; what is staged is of abandoned steps
+        const int rc = decay_rollback();
         if (rc) return rc;
     }
     if (dir_.active) {

@@ -545,6 +545,8 @@ void Engine<Real>::release() {
     snapshot_release(snap_);
     spectrum_release(spec_);
     if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
+    decay_release(decay_);
+    if (ckpt_.decay_bins) (void)hipFree(ckpt_.decay_bins);
     for (auto& e : events_) (void)hipEventDestroy(e);
     events_.clear();
     for (auto& e : halo_events_)

@@ -49,6 +49,7 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
         return fail(WV_E_STATE, "wv_set_snapshots: not on a slab of a chain (one domain only)");
     // (a spectrum plan cuts the passes at its own steps: one consumer of capture steps at a time, engine_spectrum.hip.h)
     if (spec_.active) return fail(WV_E_STATE, "wv_set_snapshots: a spectrum plan is active (wv_set_spectrum(e, NULL, NULL) stops it); the two plans exclude each other");
+    if (decay_.active) return fail(WV_E_STATE, "wv_set_snapshots: a decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");
     wv::SnapshotBox box;
     box.x0 = plan->x0, box.y0 = plan->y0, box.z0 = plan->z0;
     box.nx = plan->nx, box.ny = plan->ny, box.nz = plan->nz;
@@ -98,8 +99,8 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
 }
 
 // snapshot_gather_kernel on the compute stream: `box` of the field `current` -> the dense floats at `dst` (`wide`: four nodes per
-// lane, snapshot_kernels.hip.h).  The one launch site of the kernel: a snapshot plan's captures and a spectrum plan's
-// (engine_spectrum.hip.h) are the same launch.
+// lane, snapshot_kernels.hip.h).  The one launch site of the kernel: a snapshot plan's captures, a spectrum plan's
+// (engine_spectrum.hip.h) and a decay plan's (engine_decay.hip.h) are the same launch.
 template <typename Real>
 int Engine<Real>::launch_snapshot_gather(const wv::SnapshotBox& box, bool wide, float* dst) {
     wv::SnapshotArgs<Real> a{};

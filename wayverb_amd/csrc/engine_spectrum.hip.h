@@ -9,7 +9,7 @@
 //             directly behind the pass that produced the step.  A plan step is the end of a pass exactly as a snapshot step is:
 //             engine_batch.hip.h cuts its batches and segments at whichever plan is active (the two plans exclude each other).
 //   commit    a batch's captures stay staged until commit_batch has said how many of its steps were good; those of later steps are
-//             dropped (spectrum_commit).  A capture of a step that was never completed is never folded in.
+//             dropped (CaptureStage::commit, capture_stage.h: the stage's bookkeeping, shared with engine_decay.hip.h).  A capture of a step that was never completed is never folded in.
 //   fold      spectrum_fold_kernel (spectrum_kernels.hip.h) folds all staged captures into the sums double[K][2][B] in ONE launch,
 //             and only when the stage has no slot left for the next batch -- or on fetch and checkpoint.  (A new plan, a NULL plan
 //             and wv_destroy fold nothing: the sums are forgotten with the stage.)
@@ -64,6 +64,7 @@ int Engine<Real>::set_spectrum(const wv_spectrum_plan* plan, const double* cycle
         return fail(WV_E_STATE, "wv_set_spectrum: not on a slab of a chain (one domain only)");
     // both plans want to decide where passes end: one consumer of capture steps at a time
     if (snap_.active) return fail(WV_E_STATE, "wv_set_spectrum: a snapshot plan is active (wv_set_snapshots(e, NULL) stops it); the two plans exclude each other");
+    if (decay_.active) return fail(WV_E_STATE, "wv_set_spectrum: a decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");
     if (plan->n_freqs < 1 || plan->n_freqs > wv::kSpectrumMaxFreqs) return fail(WV_E_INVALID_ARGUMENT, "wv_set_spectrum: n_freqs must be 1 .. 64");
     if (!cycles_per_step) return fail(WV_E_INVALID_ARGUMENT, "null argument");
     for (uint32_t k = 0; k < plan->n_freqs; ++k)
@@ -117,8 +118,7 @@ int Engine<Real>::set_spectrum(const wv_spectrum_plan* plan, const double* cycle
     }
     spectrum_release(spec_);
     spec_ = std::move(s);
-    spec_.next = wv::snapshot_next_step(plan->first_step, plan->period, steps_done);
-    spec_.batch_end = spec_.next;
+    spec_.st.start(plan->first_step, plan->period, steps_done);
     spec_.active = true;
     return WV_OK;
 }
@@ -129,11 +129,10 @@ template <typename Real>
 int Engine<Real>::spectrum_capture(uint64_t step) {
     Spectrum& s = spec_;
     // (spectrum_plan_batch gives a batch no more captures than the stage has free slots)
-    if ((int)s.steps.size() >= wv::kSpectrumStage) return fail(WV_E_STATE, "wv_run: the spectrum stage is full");
-    const int rc = launch_snapshot_gather(s.box, s.gather_wide, s.stage + (uint64_t)s.steps.size() * s.nodes);  // (engine_snapshot.hip.h)
+    if (s.st.full()) return fail(WV_E_STATE, "wv_run: the spectrum stage is full");
+    const int rc = launch_snapshot_gather(s.box, s.gather_wide, s.stage + (uint64_t)s.st.slot() * s.nodes);  // (engine_snapshot.hip.h)
     if (rc) return rc;
-    s.steps.push_back(step);
-    s.next = wv::snapshot_next_step(s.plan.first_step, s.plan.period, step + 1);
+    s.st.staged(step);
     return WV_OK;
 }
 
@@ -150,23 +149,13 @@ int Engine<Real>::spectrum_drain_timing(int b) {
     return WV_OK;
 }
 
-// Captures of steps that were never committed (a run that failed while enqueueing left them staged) are dropped and are due again.
-template <typename Real>
-void Engine<Real>::spectrum_drop_uncommitted() {
-    Spectrum& s = spec_;
-    if ((int)s.steps.size() > s.committed) {
-        s.next = s.steps[(size_t)s.committed];
-        s.steps.resize((size_t)s.committed);
-    }
-}
-
 // All committed captures -> the sums, one launch.  Only between batches, where nothing uncommitted is staged -- but for what a
 // failed run left, which goes first: the stage is filled from slot 0 again behind a fold.
 template <typename Real>
 int Engine<Real>::spectrum_fold() {
     Spectrum& s = spec_;
-    spectrum_drop_uncommitted();
-    const int t = s.committed;
+    s.st.drop_uncommitted();
+    const int t = s.st.committed;
     if (t == 0) return WV_OK;
     const int b = s.table;
     // the fold before last used this buffer: its copy has long left the host's table (a wait only if the device is two folds behind)
@@ -177,7 +166,7 @@ int Engine<Real>::spectrum_fold() {
     for (int j = 0; j < t; ++j)
         for (uint32_t k = 0; k < K; ++k) {
             double* w = s.tw_host[b] + wv::spectrum_table_index((uint32_t)j, k, K);
-            wv::spectrum_twiddle(s.freqs[k], s.steps[(size_t)j], w, w + 1);
+            wv::spectrum_twiddle(s.freqs[k], s.st.steps[(size_t)j], w, w + 1);
         }
     WV_HIP(hipMemcpyAsync(s.tw_dev[b], s.tw_host[b], (size_t)t * K * 2 * sizeof(double), hipMemcpyHostToDevice, stream_));
     const uint64_t items = s.fold_wide ? s.nodes / 2 : s.nodes;
@@ -195,25 +184,9 @@ int Engine<Real>::spectrum_fold() {
     WV_HIP(hipEventRecord(s.folded_ev[b], stream_));
     s.table_used[b] = true;
     s.table = 1 - b;
-    s.folded += (uint64_t)t;
     ++s.folds;
-    s.committed = 0;
-    s.steps.clear();
+    s.st.all_folded();
     return WV_OK;
-}
-
-// Behind commit_batch: the batch's captures of steps that were completed stay, the others are dropped (and are due again).
-template <typename Real>
-void Engine<Real>::spectrum_commit(uint64_t last_good_step) {
-    Spectrum& s = spec_;
-    const int staged = (int)s.steps.size() - s.committed;
-    const int good = wv::spectrum_good_captures(s.steps.data() + s.committed, staged, last_good_step);
-    if (good < staged) {
-        s.next = s.steps[(size_t)(s.committed + good)];
-        s.steps.resize((size_t)(s.committed + good));
-    }
-    s.committed += good;
-    if (s.committed > 0) s.last_step = s.steps.back();
 }
 
 // Before a batch is planned: the fold when the stage has no slot left, and where the batch ends at the latest -- on the last capture
@@ -221,14 +194,11 @@ void Engine<Real>::spectrum_commit(uint64_t last_good_step) {
 template <typename Real>
 int Engine<Real>::spectrum_plan_batch() {
     Spectrum& s = spec_;
-    if (wv::spectrum_fold_due(s.committed)) {
+    if (s.st.fold_due()) {
         const int rc = spectrum_fold();
         if (rc) return rc;
     }
-    int room = wv::spectrum_batch_captures(s.committed, opt_.tuning.graph != 0);
-    uint64_t end = s.next;
-    for (; room > 1 && end != wv::kNoSnapshotStep; --room) end = wv::snapshot_next_step(s.plan.first_step, s.plan.period, end + 1);
-    s.batch_end = end == wv::kNoSnapshotStep ? s.next : end;
+    s.st.plan_batch_end(opt_.tuning.graph != 0);
     return WV_OK;
 }
 
@@ -237,14 +207,11 @@ int Engine<Real>::spectrum_plan_batch() {
 template <typename Real>
 int Engine<Real>::spectrum_begin_run() {
     Spectrum& s = spec_;
-    spectrum_drop_uncommitted();
-    if (s.next < steps_done) s.next = wv::snapshot_next_step(s.plan.first_step, s.plan.period, steps_done);
-    s.batch_end = s.next;
-    if (s.next == steps_done) {
-        int rc = wv::spectrum_fold_due(s.committed) ? spectrum_fold() : WV_OK;
+    if (s.st.begin_run(steps_done)) {
+        int rc = s.st.fold_due() ? spectrum_fold() : WV_OK;
         if (rc) return rc;
         if ((rc = spectrum_capture(steps_done))) return rc;
-        spectrum_commit(steps_done);
+        s.st.commit(steps_done);
     }
     return WV_OK;
 }
@@ -270,9 +237,9 @@ int Engine<Real>::spectrum_checkpoint() {
     const int rc = spectrum_fold();
     if (rc) return rc;
     WV_HIP(hipMemcpyAsync(ckpt_.spec_acc, s.acc, bytes, hipMemcpyDeviceToDevice, stream_));
-    ckpt_.spec_captures = s.folded;
-    ckpt_.spec_last_step = s.last_step;
-    ckpt_.spec_next = s.next;
+    ckpt_.spec_captures = s.st.folded;
+    ckpt_.spec_last_step = s.st.last_step;
+    ckpt_.spec_next = s.st.next;
     return WV_OK;
 }
 
@@ -281,20 +248,15 @@ template <typename Real>
 int Engine<Real>::spectrum_rollback() {
     Spectrum& s = spec_;
     WV_HIP(hipMemcpyAsync(s.acc, ckpt_.spec_acc, ckpt_.spec_bytes, hipMemcpyDeviceToDevice, stream_));
-    s.steps.clear();
-    s.committed = 0;
-    s.folded = ckpt_.spec_captures;
-    s.last_step = ckpt_.spec_last_step;
-    s.next = ckpt_.spec_next;
-    s.batch_end = s.next;
+    s.st.rollback(ckpt_.spec_captures, ckpt_.spec_last_step, ckpt_.spec_next);
     return WV_OK;
 }
 
 template <typename Real>
 int Engine<Real>::spectrum_count(uint64_t* captures, uint64_t* last_step) {
     if (!spec_.active) return fail(WV_E_STATE, "wv_spectrum_count: no spectrum plan is set");
-    if (captures) *captures = spec_.folded + (uint64_t)spec_.committed;
-    if (last_step) *last_step = spec_.last_step;
+    if (captures) *captures = spec_.st.captures();
+    if (last_step) *last_step = spec_.st.last_step;
     return WV_OK;
 }
 
@@ -321,7 +283,7 @@ int Engine<Real>::fetch_spectrum(double* dst, uint64_t* captures) {
             out[2 * i + 1] = im[i];
         }
     }
-    if (captures) *captures = s.folded;
+    if (captures) *captures = s.st.folded;
     return WV_OK;
 }
 

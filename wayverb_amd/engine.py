@@ -38,6 +38,7 @@ EXPORTS = [
     "wv_compressed_waveguide_run", "wv_make_transparent", "wv_set_snapshots", "wv_snapshot_count", "wv_fetch_snapshots",
     "wv_set_directional_receivers", "wv_fetch_directional", "wv_directional_accumulate",
     "wv_set_spectrum", "wv_spectrum_count", "wv_fetch_spectrum", "wv_spectrum_twiddle",
+    "wv_set_decay", "wv_decay_count", "wv_fetch_decay",
 ]
 
 
@@ -79,6 +80,14 @@ class WvSpectrumPlan(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
                 ("sx", C.c_int32), ("sy", C.c_int32), ("sz", C.c_int32), ("first_step", C.c_uint64), ("period", C.c_uint64),
                 ("n_freqs", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WvDecayPlan(C.Structure):
+    """wv_decay_plan (include/wayverb_amd.h): the snapshot plan's box, strides and cadence, the number of time bins and the captures
+    per bin."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("sx", C.c_int32), ("sy", C.c_int32), ("sz", C.c_int32), ("first_step", C.c_uint64), ("period", C.c_uint64),
+                ("n_bins", C.c_uint32), ("bin_captures", C.c_uint32)]
 
 
 # Tuning applied to every engine this module creates unless the call says otherwise: {field of wv_tuning: value}, plus
@@ -188,6 +197,9 @@ def load_library():
     lib.wv_fetch_spectrum.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.wv_spectrum_twiddle.argtypes = [C.c_double, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.wv_spectrum_twiddle.restype = None
+    lib.wv_set_decay.argtypes = [C.c_void_p, C.POINTER(WvDecayPlan)]
+    lib.wv_decay_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.wv_fetch_decay.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.wv_set_directional_receivers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_double]
     lib.wv_fetch_directional.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.wv_directional_accumulate.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
@@ -371,6 +383,7 @@ class Engine:
         self.n_directional = 0
         self.snapshot_shape = None
         self.spectrum_shape = None
+        self.decay_shape = None
 
     @classmethod
     def from_handle(cls, handle, mesh, precision):
@@ -385,6 +398,7 @@ class Engine:
         eng.n_directional = 0
         eng.snapshot_shape = None
         eng.spectrum_shape = None
+        eng.decay_shape = None
         return eng
 
     def close(self):
@@ -600,6 +614,38 @@ class Engine:
         _check(self.lib.wv_fetch_spectrum(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
         return out, captures.value
 
+    # ---- time-binned field energy accumulated on the device while wv_run goes on ----------------------
+    def set_decay(self, n_bins, bin_captures=1, box="mesh", stride=1, first_step=0, period=1):
+        """wv_set_decay.  `box`, `stride`, `first_step`, `period` as for set_snapshots.  At every plan step the engine captures the box
+        as a snapshot would and adds its square, on the device, to the time bin of the capture: capture j (0, 1, ... since the plan was
+        set) goes to bin min(j // bin_captures, n_bins - 1), E[b] = E[b] + p * p in double, in capture order -- a NumPy loop over the
+        snapshots of the same plan reproduces the bins bit for bit.  The last bin is open-ended.  wayverb_amd.decay turns the bins into
+        the decay curve, EDT / T20 / T30 and level maps.  Excludes a snapshot plan and a spectrum plan.  set_decay(None) stops and
+        forgets.  Returns the shape (n_bins, nz, ny, nx)."""
+        if n_bins is None:
+            _check(self.lib.wv_set_decay(self.h, None))
+            self.decay_shape = None
+            return None
+        plan = WvDecayPlan()
+        taken = self._fill_box(plan, box, stride)
+        plan.first_step, plan.period, plan.n_bins, plan.bin_captures = int(first_step), int(period), int(n_bins), int(bin_captures)
+        _check(self.lib.wv_set_decay(self.h, C.byref(plan)))
+        self.decay_shape = (int(n_bins), taken[2], taken[1], taken[0])
+        return self.decay_shape
+
+    def decay_count(self):
+        """wv_decay_count: (captures of completed steps since the plan was set, the step of the last of them)."""
+        captures, last = C.c_uint64(), C.c_uint64()
+        _check(self.lib.wv_decay_count(self.h, C.byref(captures), C.byref(last)))
+        return captures.value, last.value
+
+    def fetch_decay(self):
+        """wv_fetch_decay: (float64[n_bins, nz, ny, nx], captures in it).  The plan keeps running."""
+        out = np.zeros(tuple(self.decay_shape or (0, 0, 0, 0)), dtype=np.float64)   # (no plan: the library says so)
+        captures = C.c_uint64()
+        _check(self.lib.wv_fetch_decay(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
+        return out, captures.value
+
     def step_count(self):
         s = C.c_uint64()
         _check(self.lib.wv_step_count(self.h, C.byref(s)))
@@ -631,6 +677,7 @@ class Engine:
     QUERY_SNAPSHOT_NS, QUERY_SNAPSHOT_BYTES, QUERY_SNAPSHOTS_TAKEN = 21, 22, 23
     QUERY_WIDE_GATHERS, QUERY_DIRECTIONAL_LAUNCHES = 24, 25
     QUERY_SPECTRUM_CAPTURES, QUERY_SPECTRUM_FOLDS, QUERY_SPECTRUM_NS = 26, 27, 28
+    QUERY_DECAY_CAPTURES, QUERY_DECAY_FOLDS, QUERY_DECAY_NS = 29, 30, 31
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

@@ -108,7 +108,7 @@ def compute_voxels_and_mesh(vertices, triangles, surface_absorptions, anchor, sa
 
 
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
-              device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None):
+              device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None, decay=None):
     """canonical (single band): hard source at `source`, directional receiver at `receiver`, for
     ceil(sample_rate * simulation_time) steps.  Returns [(directional records, sample_rate,
     (0, cutoff))] -- the bandpass_band list waveguide::postprocess takes -- or None when stopped early.
@@ -123,7 +123,13 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     `spectrum`: dict(freqs_hz=[...], box=..., stride=..., first_step=..., period=...) -- the engine Fourier-transforms that part of
     the field on the device at those frequencies while the run goes on (Engine.set_spectrum; Hz become cycles per step with the
     run's sample rate); the return value is then (bands, (complex128[K, nz, ny, nx], captures)).  One domain only, and not together
-    with `snapshots`."""
+    with `snapshots`.
+    `decay`: keyword arguments of Engine.set_decay (n_bins, bin_captures, box, stride, first_step, period) -- the engine sums the
+    squared field of that box into time bins on the device while the run goes on; the return value is then (bands, (float64[n_bins,
+    nz, ny, nx], captures)), which wayverb_amd.decay.decay_maps turns into EDT / T20 / T30 and level maps.  One domain only; together
+    with `snapshots` or `spectrum` the engine refuses the second plan (engine.WaveguideError, with the plan to stop in its message)."""
+    if decay is not None and slabs > 1:
+        raise ValueError("decay bins are accumulated on one domain only (slabs=1)")
     if snapshots is not None and slabs > 1:
         raise ValueError("snapshots are taken on one domain only (slabs=1)")
     if spectrum is not None and slabs > 1:
@@ -159,18 +165,22 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 eng.set_snapshots(**snapshots)
             if spectrum_plan is not None:
                 eng.set_spectrum(**spectrum_plan)
+            if decay is not None:
+                eng.set_decay(**decay)
             done, traces = E.run_fast(eng, E.SOURCE_HARD, mesh_index(source), signal, [receiver_index] + list(neighbours),
                                       keep_going=keep_going)
             taken = eng.fetch_snapshots() if snapshots is not None else None
             if spectrum_plan is not None:
                 taken = eng.fetch_spectrum()
+            if decay is not None:
+                taken = eng.fetch_decay()
         finally:
             eng.close()
     if done != ideal_steps:
         return None
     directional = P.directional_receiver(traces, mesh.spacing, sample_rate, environment.ambient_density)
     bands = [(directional, sample_rate, (0.0, float(cutoff)))]
-    return bands if snapshots is None and spectrum is None else (bands, taken)
+    return bands if snapshots is None and spectrum is None and decay is None else (bands, taken)
 
 
 def spectrum_plan_arguments(spectrum, sample_rate):
@@ -290,24 +300,29 @@ def canonical_multiband(vm, source, receiver, environment, bands, cutoff, usable
 
 def impulse_response(vertices, triangles, surface_absorptions, source, receiver, cutoff=200.0, usable_portion=0.6,
                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
-                     pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None):
+                     pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None, decay=None):
     """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio.
     `snapshots`: a function mesh -> keyword arguments of Engine.set_snapshots (the mesh's size is not known before it is built),
     or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member.
-    `spectrum`: a function mesh -> canonical's `spectrum` dict, or the dict; the fourth member is then (spectrum, captures)."""
+    `spectrum`: a function mesh -> canonical's `spectrum` dict, or the dict; the fourth member is then (spectrum, captures).
+    `decay`: a function (mesh, sample_rate) -> canonical's `decay` dict, or the dict; the fourth member is then (bins, captures)."""
     environment = environment or Environment()
     vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
     if spectrum is not None and snapshots is not None:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
-    if snapshots is None and spectrum is None:
+    if snapshots is None and spectrum is None and decay is None:
         bands = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device)
         taken = None
     else:
-        which = "snapshots" if snapshots is not None else "spectrum"
-        plan = snapshots if snapshots is not None else spectrum
-        plan = plan(vm.mesh) if callable(plan) else plan
-        both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, **{which: plan})
+        plans = {}
+        for which, plan in (("snapshots", snapshots), ("spectrum", spectrum)):
+            if plan is not None:
+                plans[which] = plan(vm.mesh) if callable(plan) else plan
+        if decay is not None:
+            rate = compute_sample_rate(vm.mesh.spacing, environment.speed_of_sound)
+            plans["decay"] = decay(vm.mesh, rate) if callable(decay) else decay
+        both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, **plans)
         if both is None:
             raise RuntimeError("the waveguide run was stopped early")
         bands, taken = both
