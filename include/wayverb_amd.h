@@ -435,6 +435,61 @@ int wv_set_decay(wv_engine* e, const wv_decay_plan* plan);
 int wv_decay_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
 int wv_fetch_decay(wv_engine* e, double* dst /* [n_bins][nz][ny][nx] */, uint64_t* captures);
 
+/* ---- band-limited decay maps: octave-band filters ahead of the energy fold ---------------------- */
+/* Reverberation times are quoted per octave band (ISO 3382), and an impulse-driven rectilinear mesh carries energy up to Nyquist
+ * while the waveguide is trusted below about a quarter of the sample rate: the broadband bins above sum both.  wv_set_decay_bands is
+ * a decay plan with a FILTER BANK in front of the square: n_bands cascades of n_sections biquad sections, run per node on the device
+ * on the series of captures, each band with bins of its own.  wv_decay_plan is the plan above, unchanged, and so is wv_set_decay.
+ * The arithmetic is the reference's core::filter::biquad / series_biquads<N> (src/core/include/core/filters_common.h), a wv_biquad
+ * its biquad::coefficients (a0 == 1); wv_butterworth_bandpass and wv_bandpass_biquad restate its designs.
+ *
+ * Definition.  p_j is the snapshot float of committed capture j (the block above) and x = (double)p_j.  For band k the sections
+ * s = 0 .. n_sections - 1 run in series on the node's own state z1[k][s], z2[k][s], which starts at +0.0; every product and sum is
+ * rounded on its own, nothing is contracted, in exactly this association:
+ *     out = x * b0 + z1
+ *     z1  = (x * b1 - a1 * out) + z2
+ *     z2  = x * b2 - a2 * out
+ *     x   = out                                                     (into the next section)
+ * and with y = x after the last section
+ *     E[k][b(j)] = E[k][b(j)] + y * y                               (the product is rounded, then the sum)
+ * b(j) is the plain plan's bin.  A loop over the snapshots of the same plan that evaluates these lines on float64 arrays
+ * (wayverb_amd/decay.py: banded_bins) reproduces bins AND states BIT FOR BIT; wv_biquad_run is the same cascade on the host.
+ *
+ *   - 1 <= n_bands <= 8, 1 <= n_sections <= 4, every coefficient finite; otherwise, and for whatever wv_set_decay refuses in a
+ *     plan: WV_E_INVALID_ARGUMENT.  A NULL plan stops, forgets and frees the plan, as wv_set_decay(e, NULL) does (either call
+ *     stops either kind)
+ *   - everything is allocated when the plan is set: the stage (64 bytes per node), 8 n_bins n_bands bytes of bins and
+ *     16 n_sections n_bands bytes of filter state per node, the coefficient table and the two bin tables.  With no room the call
+ *     answers WV_E_HIP and leaves the engine and any earlier plan untouched
+ *   - box, stride, cadence, one domain only, wv_run_group's refusal, wv_step / wv_swap capturing nothing, fetching any time
+ *     outside wv_run, and bit-identical fields / receiver rows / flags are the plain plan's rules.  A banded plan IS a decay plan
+ *     where plans exclude each other: the snapshot and spectrum setters refuse while it is active and it refuses while they are,
+ *     and the two kinds of decay plan refuse each other too; wv_last_error names the plan to stop
+ *   - after a run that stopped on a flag at step f the bins hold exactly the captures of steps <= f, and the filter states have
+ *     seen exactly those: a continued run goes on as if the dropped captures had never been taken
+ *   - wv_checkpoint copies bins AND filter states aside and wv_rollback puts both back; the re-run is bitwise the same
+ *   - wv_decay_count and the queries WV_QUERY_DECAY_CAPTURES / _FOLDS / _NS serve both kinds of plan.  wv_fetch_decay under a
+ *     banded plan answers WV_E_STATE, and so does wv_fetch_decay_bands under a plain plan; wv_last_error names the other call
+ *
+ * What the caller owns.  The series the filters see is sampled at sample_rate / period: design the sections for THAT rate.  With
+ * period > 1 field content above sample_rate / (2 period) aliases into the bands, so an impulse source needs period = 1 -- which
+ * ends every pass on every step -- while a source band-limited below sample_rate / 6 can run at period = 3 and keep three-step
+ * passes.  Plan steps skipped by wv_step / wv_swap are gaps in the series.
+ *
+ * Host side, no GPU.  wv_biquad_run filters in[0 .. n) through the cascade into out (which may be `in`); state [n_sections][2]
+ * = z1, z2 per section is read and written back, NULL = start from +0.0 and discard.  wv_butterworth_bandpass writes the two
+ * sections of compute_hipass_butterworth_coefficients<2>(lo_hz) followed by the two of compute_lopass_butterworth_coefficients<2>
+ * (hi_hz): a 4th-order Butterworth slope on either side.  wv_bandpass_biquad is compute_bandpass_biquad_coefficients.  Both want
+ * 0 < lo_hz < hi_hz < sample_rate / 2 (WV_E_INVALID_ARGUMENT otherwise) and keep the reference's order of operations. */
+typedef struct wv_biquad { double b0, b1, b2, a1, a2; } wv_biquad;   /* 40 bytes; core::filter::biquad::coefficients, a0 == 1 */
+int wv_set_decay_bands(wv_engine* e, const wv_decay_plan* plan,
+                       const wv_biquad* sections /* [n_bands][n_sections] */, uint32_t n_bands, uint32_t n_sections);
+int wv_fetch_decay_bands(wv_engine* e, double* dst /* [n_bands][n_bins][nz][ny][nx] */, uint64_t* captures);
+int wv_biquad_run(const wv_biquad* sections, uint32_t n_sections, const double* in, uint64_t n,
+                  double* state /* [n_sections][2] in/out, or NULL */, double* out);
+int wv_butterworth_bandpass(double lo_hz, double hi_hz, double sample_rate, wv_biquad out[4]);
+int wv_bandpass_biquad(double lo_hz, double hi_hz, double sample_rate, wv_biquad* out);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */

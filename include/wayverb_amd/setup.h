@@ -225,6 +225,21 @@ inline std::array<double, 9> band_edges_hz() {
     return e;
 }
 
+// ---- band-limited decay maps (wv_set_decay_bands) ------------------------------------------------------
+/// The sections of a banded decay plan for octave bands around `centres_hz` (c / sqrt 2 .. c * sqrt 2): per band the four sections of
+/// wv_butterworth_bandpass -- compute_hipass_butterworth_coefficients<2>(lo) then compute_lopass_butterworth_coefficients<2>(hi),
+/// src/core/include/core/filters_common.h:235-245 -- designed at the rate of the series the engine filters, sample_rate / period.
+/// The result is wv_set_decay_bands' `sections` with n_bands = centres_hz.size() (8 at the most) and n_sections = 4.  Throws
+/// std::invalid_argument for a band that does not lie below half that rate.
+inline std::vector<wv_biquad> octave_band_decay_sections(const std::vector<double>& centres_hz, double sample_rate, uint64_t period = 1) {
+    std::vector<wv_biquad> out(centres_hz.size() * 4);
+    const double root2 = std::sqrt(2.0);
+    for (size_t i = 0; i < centres_hz.size(); ++i)
+        if (wv_butterworth_bandpass(centres_hz[i] / root2, centres_hz[i] * root2, sample_rate / (double)(period ? period : 1), &out[4 * i]) != WV_OK)
+            throw std::invalid_argument(wv_last_error());
+    return out;
+}
+
 /// canonical.h:127-135
 inline void set_flat_coefficients_for_band(voxels_and_mesh& vm, size_t band) {
     std::vector<coefficients_canonical> c;

@@ -68,6 +68,11 @@ def main():
     ap.add_argument("--decay-bin-ms", type=float, default=10.0, help="the length of a time bin in milliseconds")
     ap.add_argument("--decay-every", type=int, default=3, help="capture every k-th step (3 keeps every pass a three-step pass; the "
                                                                "levels then lie 10 log10(k) dB low, the decay times do not change)")
+    ap.add_argument("--decay-bands", default=None, metavar="HZ,HZ,...",
+                    help="with --decay-map: octave-band centres in Hz (8 at the most), e.g. 125,250,500 -- every node's captures go "
+                         "through a 4th-order Butterworth band-pass per band on the device before they are squared, and the maps are "
+                         "written per band (a leading band axis).  The filters run at sample rate / --decay-every: an impulse needs "
+                         "--decay-every 1")
     ap.add_argument("--decay-out", default="decay.npz", help="the maps go here: bins float64[n_bins, ny, nx], edt_s / t20_s / t30_s and "
                                                              "their _r, level_db, edc_db, sample_rate, bin_captures, period, captures, "
                                                              "plane, origin (metres of the plane's first node), spacing")
@@ -144,6 +149,12 @@ def main():
             ap.error("--decay-every must be >= 1 and --decay-bin-ms positive")
         decay_height = float(args.decay_map[2:]) if args.decay_map else args.receiver[2]
         decay_plane = {}
+        try:
+            decay_centres = [float(c) for c in args.decay_bands.split(",")] if args.decay_bands else []
+        except ValueError:
+            ap.error("--decay-bands takes octave centres in Hz, e.g. 125,250,500")
+        if len(decay_centres) > 8 or any(not c > 0 for c in decay_centres):
+            ap.error("--decay-bands: 1 .. 8 positive centre frequencies")
 
         def decay(mesh, rate):
             plane = int(round((decay_height - mesh.min_corner[2]) / mesh.spacing))
@@ -154,7 +165,18 @@ def main():
             n_bins = max(1, min(4096, -(-captures // per_bin)))
             decay_plane.update(plane=plane, rate=rate, per_bin=per_bin,
                                origin=np.asarray(mesh.min_corner, dtype=np.float64) + np.array([0.0, 0.0, plane * mesh.spacing]))
-            return dict(n_bins=n_bins, bin_captures=per_bin, box=((0, 0, plane), (None, None, 1)), period=args.decay_every)
+            plan = dict(n_bins=n_bins, bin_captures=per_bin, box=((0, 0, plane), (None, None, 1)), period=args.decay_every)
+            if decay_centres:
+                from wayverb_amd import decay as D
+                plan["bands"] = D.octave_band_edges(decay_centres)
+                for c, (lo, hi) in zip(decay_centres, plan["bands"]):
+                    if hi > 0.25 * rate:
+                        print("warning: the %g Hz band reaches %.1f Hz, above a quarter of the sample rate (%.1f Hz): the waveguide "
+                              "is not trusted there" % (c, hi, 0.25 * rate), file=sys.stderr)
+                    if hi > 0.5 * rate / args.decay_every:
+                        print("warning: the %g Hz band reaches %.1f Hz, above the Nyquist rate of the captured series (%.1f Hz with "
+                              "--decay-every %d): it aliases" % (c, hi, 0.5 * rate / args.decay_every, args.decay_every), file=sys.stderr)
+            return plan
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
     if len(receivers) > 1:
@@ -188,13 +210,19 @@ def main():
         if decay is not None:
             from wayverb_amd import decay as D
             bins, captures = audio_etc[3]
-            maps = D.decay_maps(bins[:, 0], decay_plane["per_bin"], args.decay_every, decay_plane["rate"])
-            np.savez(args.decay_out, bins=bins[:, 0], sample_rate=decay_plane["rate"], bin_captures=decay_plane["per_bin"],
+            bins = bins[..., 0, :, :]   # the one plane: [n_bins, ny, nx], per band [K, n_bins, ny, nx]
+            extra = {}
+            if decay_centres:   # per band: every map gets a leading band axis
+                maps = D.band_decay_maps(bins, decay_plane["per_bin"], args.decay_every, decay_plane["rate"])
+                extra = dict(band_centres_hz=np.array(decay_centres), band_edges_hz=np.array(D.octave_band_edges(decay_centres)))
+            else:
+                maps = D.decay_maps(bins, decay_plane["per_bin"], args.decay_every, decay_plane["rate"])
+            np.savez(args.decay_out, bins=bins, sample_rate=decay_plane["rate"], bin_captures=decay_plane["per_bin"],
                      period=args.decay_every, captures=captures, plane=decay_plane["plane"], origin=decay_plane["origin"],
-                     spacing=audio_etc[2].mesh.spacing, **maps)
+                     spacing=audio_etc[2].mesh.spacing, **extra, **maps)
             t30 = maps["t30_s"][np.isfinite(maps["t30_s"])]
             print("wrote decay maps of plane z=%d (%d bins of %d captures, %d captures; median T30 %s) to %s"
-                  % (decay_plane["plane"], bins.shape[0], decay_plane["per_bin"], captures,
+                  % (decay_plane["plane"], bins.shape[-3], decay_plane["per_bin"], captures,
                      "%.3f s" % np.median(t30) if t30.size else "not defined", args.decay_out))
         if spectrum is not None:
             maps, captures = audio_etc[3]

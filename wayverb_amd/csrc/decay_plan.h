@@ -50,4 +50,23 @@ inline uint32_t decay_fold_bins(uint64_t first, uint32_t t, uint32_t bin_capture
 // bytes one fold of t staged captures moves: t floats read, r bins read and written, per node
 inline uint64_t decay_fold_traffic(uint64_t nodes, uint32_t t, uint32_t r) { return decay_mul(nodes, 4ull * t + 16ull * r); }
 
+// ---- band-limited decay maps (wv_set_decay_bands): n_bands cascades of n_sections biquad sections ahead of the square
+constexpr uint32_t kDecayMaxBands = 8;     // n_bands at the most
+constexpr int kDecayMaxSections = 4;       // n_sections at the most (the fold kernel has one instance per count)
+constexpr uint32_t kBiquadDoubles = 5;     // b0 b1 b2 a1 a2 (wv_biquad)
+
+inline bool decay_bands_valid(uint32_t n_bands, uint32_t n_sections) {
+    return n_bands >= 1 && n_bands <= kDecayMaxBands && n_sections >= 1 && n_sections <= (uint32_t)kDecayMaxSections;
+}
+// bytes of the bins double[n_bands][n_bins][B], of the filter state double[n_bands][n_sections][2][B], of the coefficient table
+inline uint64_t decay_band_bins_bytes(uint64_t nodes, uint32_t n_bins, uint32_t n_bands) { return decay_mul(decay_bins_bytes(nodes, n_bins), n_bands); }
+inline uint64_t decay_band_state_bytes(uint64_t nodes, uint32_t n_bands, uint32_t n_sections) {
+    return decay_mul(nodes, (uint64_t)n_bands * n_sections * 2 * sizeof(double));
+}
+inline uint64_t decay_band_coef_bytes(uint32_t n_bands, uint32_t n_sections) { return (uint64_t)n_bands * n_sections * kBiquadDoubles * sizeof(double); }
+// bytes one banded fold moves: per band t floats read (the re-reads expected from L2), the state and r bins read and written
+inline uint64_t decay_bands_fold_traffic(uint64_t nodes, uint32_t n_bands, uint32_t n_sections, uint32_t t, uint32_t r) {
+    return decay_mul(decay_mul(nodes, n_bands), 4ull * t + 32ull * n_sections + 16ull * r);
+}
+
 }  // namespace wv

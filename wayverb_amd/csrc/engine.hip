@@ -235,6 +235,14 @@ int wv_fetch_decay(wv_engine* e, double* dst, uint64_t* captures) {
     WV_NEED(e);
     return e->fetch_decay(dst, captures);
 }
+int wv_set_decay_bands(wv_engine* e, const wv_decay_plan* plan, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) {
+    WV_NEED(e);
+    return e->set_decay_bands(plan, sections, n_bands, n_sections);
+}
+int wv_fetch_decay_bands(wv_engine* e, double* dst, uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_decay_bands(dst, captures);
+}
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);
     return e->step(flag);

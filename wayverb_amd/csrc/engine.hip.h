@@ -22,6 +22,7 @@
 //   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the spectrum and the decay plan
 //   engine_decay.hip.h   time-binned field energy accumulated on the device while a run goes on (wv_set_decay): plan, stage, fold, fetch
 //   decay_plan.h         (host only, no HIP) the bin of a capture, sizes, the fold's traffic model
+//   decay_bands_kernels.hip.h   the fold of a band-limited decay plan (wv_set_decay_bands): biquad cascades ahead of the square
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -40,6 +41,7 @@
 #include "snapshot_kernels.hip.h"
 #include "spectrum_kernels.hip.h"
 #include "decay_kernels.hip.h"
+#include "decay_bands_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -186,6 +188,8 @@ public:
     int set_decay(const wv_decay_plan* plan) override;
     int decay_count(uint64_t* captures, uint64_t* last_step) override;
     int fetch_decay(double* dst, uint64_t* captures) override;
+    int set_decay_bands(const wv_decay_plan* plan, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) override;
+    int fetch_decay_bands(double* dst, uint64_t* captures) override;
     bool decay_active() const override { return decay_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
@@ -413,6 +417,8 @@ private:
         uint64_t spec_generation = 0, spec_captures = 0, spec_last_step = 0, spec_next = 0;
         double* decay_bins = nullptr;  // the decay plan's bins (engine_decay.hip.h), allocated by the first checkpoint under a plan
         size_t decay_bytes = 0;
+        double* decay_state = nullptr;  // a banded plan's filter states, likewise
+        size_t decay_state_bytes = 0;
         uint64_t decay_generation = 0, decay_captures = 0, decay_last_step = 0, decay_next = 0;
     } ckpt_;
     // field snapshots (engine_snapshot.hip.h): a ring of device slots the capture kernel fills on the compute stream, each copied to its
@@ -496,7 +502,10 @@ private:
         wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
         uint64_t nodes = 0;             // B: nodes taken
         float* stage = nullptr;         // [T][B]
-        double* bins = nullptr;         // [n_bins][B]
+        double* bins = nullptr;         // [n_bins][B]; a banded plan's: [n_bands][n_bins][B]
+        uint32_t n_bands = 0, n_sections = 0;  // wv_set_decay_bands: 1 .. 8 cascades of 1 .. 4 sections; 0 = a plain plan
+        double* state = nullptr;        // [n_bands][n_sections][2][B]: z1, z2 of every section (banded only)
+        double* coef = nullptr;         // [n_bands][n_sections][5] on the device (banded only)
         int32_t* table_host[2] = {nullptr, nullptr};
         int32_t* table_dev[2] = {nullptr, nullptr};
         hipEvent_t begun[2] = {nullptr, nullptr};      // before the fold that uses the table (kernel timing)
@@ -507,6 +516,8 @@ private:
         double kernel_ms = 0;           // fold kernels' time (kernel timing on)
     } decay_;
     static void decay_release(Decay& d);
+    int decay_set(const wv_decay_plan* plan, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections, bool banded);
+    int decay_fetch(double* dst, uint64_t* captures, bool banded);
     int decay_capture(uint64_t step);
     int decay_drain_timing(int table);
     int decay_fold();

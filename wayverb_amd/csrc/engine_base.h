@@ -99,6 +99,8 @@ struct wv_engine {
     virtual int set_decay(const wv_decay_plan* plan) = 0;
     virtual int decay_count(uint64_t* captures, uint64_t* last_step) = 0;
     virtual int fetch_decay(double* dst, uint64_t* captures) = 0;
+    virtual int set_decay_bands(const wv_decay_plan* plan, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) = 0;
+    virtual int fetch_decay_bands(double* dst, uint64_t* captures) = 0;
     virtual bool decay_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;

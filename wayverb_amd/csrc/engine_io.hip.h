@@ -354,6 +354,7 @@ int Engine<Real>::checkpoint(int op) {
         if (ckpt_.dir_velocity) (void)hipFree(ckpt_.dir_velocity);
         if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
         if (ckpt_.decay_bins) (void)hipFree(ckpt_.decay_bins);
+        if (ckpt_.decay_state) (void)hipFree(ckpt_.decay_state);
         ckpt_ = Checkpoint{};
         return WV_OK;
     }

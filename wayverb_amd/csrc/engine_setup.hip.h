@@ -547,6 +547,7 @@ void Engine<Real>::release() {
     if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
     decay_release(decay_);
     if (ckpt_.decay_bins) (void)hipFree(ckpt_.decay_bins);
+    if (ckpt_.decay_state) (void)hipFree(ckpt_.decay_state);
     for (auto& e : events_) (void)hipEventDestroy(e);
     events_.clear();
     for (auto& e : halo_events_)

@@ -39,6 +39,7 @@ EXPORTS = [
     "wv_set_directional_receivers", "wv_fetch_directional", "wv_directional_accumulate",
     "wv_set_spectrum", "wv_spectrum_count", "wv_fetch_spectrum", "wv_spectrum_twiddle",
     "wv_set_decay", "wv_decay_count", "wv_fetch_decay",
+    "wv_set_decay_bands", "wv_fetch_decay_bands", "wv_biquad_run", "wv_butterworth_bandpass", "wv_bandpass_biquad",
 ]
 
 
@@ -200,6 +201,11 @@ def load_library():
     lib.wv_set_decay.argtypes = [C.c_void_p, C.POINTER(WvDecayPlan)]
     lib.wv_decay_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.wv_fetch_decay.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.wv_set_decay_bands.argtypes = [C.c_void_p, C.POINTER(WvDecayPlan), C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.wv_fetch_decay_bands.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.wv_biquad_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.wv_butterworth_bandpass.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
+    lib.wv_bandpass_biquad.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.wv_set_directional_receivers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_double]
     lib.wv_fetch_directional.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.wv_directional_accumulate.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
@@ -384,6 +390,7 @@ class Engine:
         self.snapshot_shape = None
         self.spectrum_shape = None
         self.decay_shape = None
+        self.decay_banded = False
 
     @classmethod
     def from_handle(cls, handle, mesh, precision):
@@ -399,6 +406,7 @@ class Engine:
         eng.snapshot_shape = None
         eng.spectrum_shape = None
         eng.decay_shape = None
+        eng.decay_banded = False
         return eng
 
     def close(self):
@@ -615,22 +623,40 @@ class Engine:
         return out, captures.value
 
     # ---- time-binned field energy accumulated on the device while wv_run goes on ----------------------
-    def set_decay(self, n_bins, bin_captures=1, box="mesh", stride=1, first_step=0, period=1):
+    def set_decay(self, n_bins, bin_captures=1, box="mesh", stride=1, first_step=0, period=1, bands=None):
         """wv_set_decay.  `box`, `stride`, `first_step`, `period` as for set_snapshots.  At every plan step the engine captures the box
         as a snapshot would and adds its square, on the device, to the time bin of the capture: capture j (0, 1, ... since the plan was
         set) goes to bin min(j // bin_captures, n_bins - 1), E[b] = E[b] + p * p in double, in capture order -- a NumPy loop over the
         snapshots of the same plan reproduces the bins bit for bit.  The last bin is open-ended.  wayverb_amd.decay turns the bins into
         the decay curve, EDT / T20 / T30 and level maps.  Excludes a snapshot plan and a spectrum plan.  set_decay(None) stops and
-        forgets.  Returns the shape (n_bins, nz, ny, nx)."""
+        forgets.  Returns the shape (n_bins, nz, ny, nx).
+
+        `bands`: float64[K][S][5], K <= 8 cascades of S <= 4 biquad sections (b0, b1, b2, a1, a2; wayverb_amd.decay designs them) ->
+        wv_set_decay_bands: every node runs its captures through each cascade, in double, before the square, and each band has bins of
+        its own (decay.banded_bins is the same in NumPy, bit for bit).  The series the filters see is sampled every `period` steps:
+        design the sections for sample_rate / period.  Returns the shape (K, n_bins, nz, ny, nx).  None: the plain plan."""
         if n_bins is None:
-            _check(self.lib.wv_set_decay(self.h, None))
+            _check(self.lib.wv_set_decay(self.h, None))   # (stops either kind of plan)
             self.decay_shape = None
+            self.decay_banded = False
             return None
+        if bands is not None:
+            sections = np.ascontiguousarray(bands, dtype=np.float64)
+            if sections.ndim != 3 or sections.shape[2] != 5:
+                raise ValueError("set_decay: bands is float64[K][S][5], got shape %r" % (sections.shape,))
+            plan = WvDecayPlan()
+            taken = self._fill_box(plan, box, stride)
+            plan.first_step, plan.period, plan.n_bins, plan.bin_captures = int(first_step), int(period), int(n_bins), int(bin_captures)
+            _check(self.lib.wv_set_decay_bands(self.h, C.byref(plan), sections.ctypes.data_as(C.c_void_p), sections.shape[0], sections.shape[1]))
+            self.decay_shape = (sections.shape[0], int(n_bins), taken[2], taken[1], taken[0])
+            self.decay_banded = True
+            return self.decay_shape
         plan = WvDecayPlan()
         taken = self._fill_box(plan, box, stride)
         plan.first_step, plan.period, plan.n_bins, plan.bin_captures = int(first_step), int(period), int(n_bins), int(bin_captures)
         _check(self.lib.wv_set_decay(self.h, C.byref(plan)))
         self.decay_shape = (int(n_bins), taken[2], taken[1], taken[0])
+        self.decay_banded = False
         return self.decay_shape
 
     def decay_count(self):
@@ -639,11 +665,16 @@ class Engine:
         _check(self.lib.wv_decay_count(self.h, C.byref(captures), C.byref(last)))
         return captures.value, last.value
 
-    def fetch_decay(self):
-        """wv_fetch_decay: (float64[n_bins, nz, ny, nx], captures in it).  The plan keeps running."""
+    def fetch_decay(self, banded=None):
+        """wv_fetch_decay: (float64[n_bins, nz, ny, nx], captures in it); under a banded plan wv_fetch_decay_bands:
+        (float64[K, n_bins, nz, ny, nx], captures).  The plan keeps running.  `banded` = True / False asks for that call whatever the
+        plan (the library refuses the wrong one)."""
         out = np.zeros(tuple(self.decay_shape or (0, 0, 0, 0)), dtype=np.float64)   # (no plan: the library says so)
         captures = C.c_uint64()
-        _check(self.lib.wv_fetch_decay(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
+        if getattr(self, "decay_banded", False) if banded is None else banded:
+            _check(self.lib.wv_fetch_decay_bands(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
+        else:
+            _check(self.lib.wv_fetch_decay(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
         return out, captures.value
 
     def step_count(self):

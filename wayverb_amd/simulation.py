@@ -127,7 +127,10 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     `decay`: keyword arguments of Engine.set_decay (n_bins, bin_captures, box, stride, first_step, period) -- the engine sums the
     squared field of that box into time bins on the device while the run goes on; the return value is then (bands, (float64[n_bins,
     nz, ny, nx], captures)), which wayverb_amd.decay.decay_maps turns into EDT / T20 / T30 and level maps.  One domain only; together
-    with `snapshots` or `spectrum` the engine refuses the second plan (engine.WaveguideError, with the plan to stop in its message)."""
+    with `snapshots` or `spectrum` the engine refuses the second plan (engine.WaveguideError, with the plan to stop in its message).
+    With `bands=[(lo_hz, hi_hz), ...]` in it (8 at the most) every node's captures go through a 4th-order Butterworth band-pass per
+    band before the square (Engine.set_decay(bands=...); wayverb_amd.decay.butterworth_bandpass designs the sections at the rate of
+    the captured series, sample_rate / period) and the bins are float64[K, n_bins, nz, ny, nx] (decay.band_decay_maps)."""
     if decay is not None and slabs > 1:
         raise ValueError("decay bins are accumulated on one domain only (slabs=1)")
     if snapshots is not None and slabs > 1:
@@ -139,6 +142,10 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     mesh = vm.mesh
     sample_rate = compute_sample_rate(mesh.spacing, environment.speed_of_sound)
     spectrum_plan = spectrum_plan_arguments(spectrum, sample_rate) if spectrum is not None else None
+    if decay is not None and decay.get("bands") is not None:
+        from . import decay as D
+        series_rate = sample_rate / int(decay.get("period", 1))
+        decay = dict(decay, bands=np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in decay["bands"]]))
 
     def mesh_index(pt):
         idx = vm.compute_index(pt)
