@@ -490,6 +490,82 @@ int wv_biquad_run(const wv_biquad* sections, uint32_t n_sections, const double* 
 int wv_butterworth_bandpass(double lo_hz, double hi_hz, double sample_rate, wv_biquad out[4]);
 int wv_bandpass_biquad(double lo_hz, double hi_hz, double sample_rate, wv_biquad* out);
 
+/* ---- intensity maps: time-binned sound intensity of a box, on the device ----------------------- */
+/* Snapshots, spectra and decay maps see pressure and nothing else.  Where the energy COMES FROM and where it goes -- the direction
+ * the early energy reaches a seat from, the wall that sends the late echo, how diffuse the field is over an audience plane -- is
+ * answered by the sound intensity vector I = p v.  The reference computes it for one node at a time
+ * (postprocessor::directional_receiver, src/waveguide/src/postprocessor/directional_receiver.cpp:29-69) and
+ * wv_set_directional_receivers does so for a list of nodes, a 16-byte record per receiver and step.  An intensity plan has the
+ * engine capture a box as a decay plan would and accumulate, per node taken, the three components of I AND the squared pressure in
+ * n_bins time bins on the device: 32 n_bins bytes per node cross the link when the caller asks, however long the run.
+ *
+ * wv_intensity_plan holds wv_decay_plan's fields with the same meaning, and `spacing, sample_rate, ambient_density`: the three
+ * arguments of the reference's directional_receiver constructor.
+ *
+ * Definition.  For every node taken (c its index, n_i its six neighbours) and every committed capture j, in capture order:
+ *     pressure       = (float) field[c]                                  the snapshot float of a snapshot plan, unchanged
+ *     surrounding[i] = (float)( (double)( (float)field[n_i] - pressure ) / spacing )      i = 0..5: ports nx, px, ny, py, nz, pz
+ *     gx = surrounding[1] - surrounding[0]                               (float; gy from ports 3, 2 and gz from 5, 4 likewise)
+ *     m  = (double)g * 0.5
+ *     v  = v - m / k                                                     k = ambient_density * sample_rate; v is double[3] per
+ *                                                                        node and starts at +0.0; the division is IEEE
+ *     I[a][b(j)] = I[a][b(j)] + v[a] * (double)pressure                  a = x, y, z (the product is rounded, then the sum)
+ *     E[b(j)]    = E[b(j)]    + (double)pressure * (double)pressure
+ * b(j) = min(j / bin_captures, n_bins - 1) is the decay plan's bin, the last bin open-ended.  The first lines are the directional
+ * receivers' (wv_directional_accumulate): the same casts, the same association; nothing is contracted.  A capture "of step s" is a
+ * snapshot's, for the centre and all six neighbours: the field after exactly s completed steps, before the loop puts the source's
+ * sample of step s into its node.  E is therefore, bit for bit, what a plain decay plan of the same box and cadence holds, and a
+ * NumPy loop over snapshots of the box's hull that evaluates these lines (wayverb_amd/intensity.py: intensity_bins; the float
+ * lines on float32 arrays, the rest on float64) reproduces I, E AND the velocities BIT FOR BIT.
+ *
+ *   - 1 <= n_bins <= 4096, bin_captures >= 1, strides and period >= 1, and spacing, sample_rate, ambient_density positive and
+ *     finite; otherwise, and for a box that leaves the mesh: WV_E_INVALID_ARGUMENT
+ *   - a taken node with a neighbour off the grid answers WV_E_INVALID_ARGUMENT with the reference's sentence, as
+ *     wv_set_directional_receivers does: x0 >= 1 and x0 + (nx - 1) sx <= mesh_nx - 2, likewise for y and z.  Neighbours inside a
+ *     wall are read as the field holds them: the reference refuses only an off-grid neighbour
+ *   - everything (the stage of 16 captures, 256 bytes per node; the bins, 32 n_bins bytes per node; the velocities, 24 bytes per
+ *     node; two tables of 16 bin indices) is allocated when the plan is set: with no room the call answers WV_E_HIP and leaves the
+ *     engine and any earlier plan untouched.  A new plan replaces the old one and forgets its sums; a NULL plan stops, forgets and
+ *     frees (as does wv_destroy)
+ *   - one domain only: a slab of a chain answers WV_E_STATE, and wv_run_group refuses an engine with a plan
+ *   - an intensity plan excludes the snapshot plan, the spectrum plan and both kinds of decay plan: every setter answers WV_E_STATE
+ *     while another plan is active, and wv_last_error names the plan to stop
+ *   - after a run that stopped on a flag at step f, bins AND velocities have seen exactly the captures of steps <= f: a continued
+ *     run goes on as if the dropped captures had never been taken
+ *   - wv_step / wv_swap capture nothing; the plan steps they pass are gaps in the series the integrator sees
+ *   - wv_checkpoint folds what is staged and copies bins, velocities, the capture count and the next plan step aside (the copies are
+ *     allocated by the first checkpoint taken under a plan: WV_E_HIP, engine untouched, when there is no room); wv_rollback puts
+ *     them back, and the re-run is bitwise the same.  A plan set AFTER the checkpoint makes wv_rollback answer WV_E_STATE
+ *   - with no plan nothing is launched, allocated or waited for; with one the fields, receiver rows and flags are bit-identical to
+ *     a run without
+ *
+ * What the caller owns.  The integrator sees a series sampled at sample_rate / period: pass THAT rate.  With period > 1 field
+ * content above sample_rate / (2 period) aliases, so an impulse source needs period = 1 -- which ends every pass on every step --
+ * while a source band-limited below sample_rate / 6 can run at period = 3 and keep three-step passes (the decay plan's argument).
+ *
+ * wv_intensity_count: as wv_decay_count.  wv_fetch_intensity: float64 [4][n_bins][nz][ny][nx] = Ix, Iy, Iz, E; *captures (may be
+ * NULL) = how many captures they hold.  It may be called any time outside wv_run, folds what is staged and leaves the plan running.
+ * wv_fetch_intensity_velocity: the carried velocities, float64 [3][nz][ny][nx], after the same fold.
+ * wv_fetch_directional_velocity: the directional receivers' carried velocities, float64 [n][3] (the same integrator's state on the
+ * other path; WV_E_STATE without directional receivers). */
+typedef struct wv_intensity_plan {
+    int32_t x0, y0, z0;    /* first node of the box */
+    int32_t nx, ny, nz;    /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;    /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step;   /* captures at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;       /* >= 1 */
+    uint32_t n_bins;       /* 1 .. 4096 */
+    uint32_t bin_captures; /* W >= 1: captures per bin (the last bin is open-ended) */
+    double spacing;        /* mesh_descriptor::spacing, > 0 */
+    double sample_rate;    /* of the CAPTURED series: the mesh's sample rate / period, > 0 */
+    double ambient_density;/* > 0 */
+} wv_intensity_plan;
+int wv_set_intensity(wv_engine* e, const wv_intensity_plan* plan);
+int wv_intensity_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
+int wv_fetch_intensity(wv_engine* e, double* dst /* [4][n_bins][nz][ny][nx]: Ix, Iy, Iz, E */, uint64_t* captures);
+int wv_fetch_intensity_velocity(wv_engine* e, double* dst /* [3][nz][ny][nx] */);
+int wv_fetch_directional_velocity(wv_engine* e, double* dst /* [n][3] */);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */
@@ -526,7 +602,10 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *                            a spectrum plan is in neither this nor WV_QUERY_SNAPSHOT_NS: it is the snapshot plan's capture, whose
  *                            time DESIGN.md 4.7 has)
  *   WV_QUERY_DECAY_CAPTURES, WV_QUERY_DECAY_FOLDS, WV_QUERY_DECAY_NS   the same three since wv_set_decay: captures of completed steps,
- *                            launches of the decay plan's fold kernel, their total time with kernel timing on */
+ *                            launches of the decay plan's fold kernel, their total time with kernel timing on
+ *   WV_QUERY_INTENSITY_CAPTURES, WV_QUERY_INTENSITY_FOLDS, WV_QUERY_INTENSITY_NS   the same three since wv_set_intensity
+ *   WV_QUERY_INTENSITY_GATHER_NS, WV_QUERY_INTENSITY_GATHERS   total time of the intensity plan's capture kernels that ran with kernel
+ *                            timing on, and how many of them that is */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -544,7 +623,9 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
        WV_QUERY_SNAPSHOT_NS = 21, WV_QUERY_SNAPSHOT_BYTES = 22, WV_QUERY_SNAPSHOTS_TAKEN = 23,
        WV_QUERY_WIDE_GATHERS = 24, WV_QUERY_DIRECTIONAL_LAUNCHES = 25,
        WV_QUERY_SPECTRUM_CAPTURES = 26, WV_QUERY_SPECTRUM_FOLDS = 27, WV_QUERY_SPECTRUM_NS = 28,
-       WV_QUERY_DECAY_CAPTURES = 29, WV_QUERY_DECAY_FOLDS = 30, WV_QUERY_DECAY_NS = 31 };
+       WV_QUERY_DECAY_CAPTURES = 29, WV_QUERY_DECAY_FOLDS = 30, WV_QUERY_DECAY_NS = 31,
+       WV_QUERY_INTENSITY_CAPTURES = 32, WV_QUERY_INTENSITY_FOLDS = 33, WV_QUERY_INTENSITY_NS = 34,
+       WV_QUERY_INTENSITY_GATHER_NS = 35, WV_QUERY_INTENSITY_GATHERS = 36 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

@@ -76,6 +76,16 @@ def main():
     ap.add_argument("--decay-out", default="decay.npz", help="the maps go here: bins float64[n_bins, ny, nx], edt_s / t20_s / t30_s and "
                                                              "their _r, level_db, edc_db, sample_rate, bin_captures, period, captures, "
                                                              "plane, origin (metres of the plane's first node), spacing")
+    ap.add_argument("--intensity-map", action="store_true",
+                    help="sum the sound intensity vector and the squared pressure of one horizontal plane (less its rim) into time "
+                         "bins on the device while the run goes on (Engine.set_intensity; single-band runs, no other plan)")
+    ap.add_argument("--intensity-plane", default=None, metavar="z=METRES", help="the height of that plane (default: the receiver's)")
+    ap.add_argument("--intensity-every", type=int, default=1, help="capture every N-th step (the integrator then runs at sample rate / N: "
+                                                                   "an impulse needs 1; 3 keeps every pass a three-step pass)")
+    ap.add_argument("--intensity-bin-ms", type=float, default=10.0, help="the length of a time bin in milliseconds")
+    ap.add_argument("--intensity-out", default="intensity.npz",
+                    help="the maps go here: bins float64[4, n_bins, ny, nx] (Ix, Iy, Iz, E), times (seconds at which each bin begins), "
+                         "net_direction [3, ny, nx], net_magnitude, diffuseness [ny, nx], captures, period, sample_rate, spacing")
     args = ap.parse_args()
 
     bands = None
@@ -177,11 +187,21 @@ def main():
                         print("warning: the %g Hz band reaches %.1f Hz, above the Nyquist rate of the captured series (%.1f Hz with "
                               "--decay-every %d): it aliases" % (c, hi, 0.5 * rate / args.decay_every, args.decay_every), file=sys.stderr)
             return plan
+    intensity = None
+    if args.intensity_map:
+        if bands or snapshots is not None or spectrum is not None or decay is not None:
+            ap.error("--intensity-map: single-band runs without --snapshots, --spectrum or --decay-map")
+        if args.intensity_plane and not args.intensity_plane.startswith("z="):
+            ap.error("--intensity-plane takes z=<metres>")
+        if args.intensity_every < 1 or not args.intensity_bin_ms > 0:
+            ap.error("--intensity-every must be >= 1 and --intensity-bin-ms positive")
+        intensity = dict(plane=float(args.intensity_plane[2:]) if args.intensity_plane else args.receiver[2], every=args.intensity_every,
+                         bin_seconds=args.intensity_bin_ms * 1e-3)
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
     if len(receivers) > 1:
-        if bands or snapshots is not None or spectrum is not None or decay is not None:
-            ap.error("several --receiver: single-band runs without --snapshots, --spectrum or --decay-map")
+        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None:
+            ap.error("several --receiver: single-band runs without --snapshots, --spectrum, --decay-map or --intensity-map")
         audios, per, positions, vm = W.impulse_responses(v, t, absorptions, args.source, receivers, args.cutoff, args.usable_portion,
                                                          args.seconds, args.rate, method=method, pointing=args.pointing,
                                                          shape=args.mic_shape or 0.0, precision=args.precision)
@@ -195,6 +215,8 @@ def main():
             peak = write_wav(name, audio, args.rate)
             print("wrote %s: receiver at node position (%.3f, %.3f, %.3f) (normalised, peak was %.3e)" % ((name,) + tuple(pos) + (peak,)))
         return
+    if bands and intensity is not None:
+        ap.error("--intensity-map: single-band runs only")
     if bands:   # multiple_band_constant_spacing: one run per band with flat per-band walls
         env = W.Environment()
         vm = W.compute_voxels_and_mesh(v, t, absorptions, args.receiver,
@@ -206,7 +228,23 @@ def main():
         audio_etc = W.impulse_response(v, t, absorptions, args.source, args.receiver, args.cutoff,
                                        args.usable_portion, args.seconds, args.rate, method=method,
                                        pointing=args.pointing, shape=args.mic_shape or 0.0,
-                                       precision=args.precision, snapshots=snapshots, spectrum=spectrum, decay=decay)
+                                       precision=args.precision, snapshots=snapshots, spectrum=spectrum, decay=decay, intensity=intensity)
+        if intensity is not None:
+            from wayverb_amd import intensity as I
+            env, mesh = W.Environment(), audio_etc[2].mesh
+            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
+            plan = W.intensity_plan_arguments(intensity, mesh, rate, env, args.seconds)
+            bins, captures = audio_etc[3]
+            bins = bins[:, :, 0]   # the one plane: [4, n_bins, ny, nx]
+            _, magnitude, direction = I.net_intensity(bins)
+            diffuse = I.diffuseness(bins, env.speed_of_sound, env.ambient_density)
+            np.savez(args.intensity_out, bins=bins, times=np.arange(bins.shape[1]) * plan["bin_captures"] * plan["period"] / rate,
+                     net_direction=direction, net_magnitude=magnitude, diffuseness=diffuse, captures=captures, bin_captures=plan["bin_captures"],
+                     period=plan["period"], sample_rate=rate, plane=plan["box"][0][2], spacing=mesh.spacing,
+                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64))
+            print("wrote intensity maps of plane z=%d (%d bins of %d captures, %d captures; median diffuseness %s) to %s"
+                  % (plan["box"][0][2], bins.shape[1], plan["bin_captures"], captures,
+                     "%.3f" % np.nanmedian(diffuse) if np.isfinite(diffuse).any() else "not defined", args.intensity_out))
         if decay is not None:
             from wayverb_amd import decay as D
             bins, captures = audio_etc[3]

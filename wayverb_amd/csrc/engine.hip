@@ -16,6 +16,7 @@
 #include "engine_snapshot.hip.h"
 #include "engine_spectrum.hip.h"
 #include "engine_decay.hip.h"
+#include "engine_intensity.hip.h"
 #include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
@@ -242,6 +243,26 @@ int wv_set_decay_bands(wv_engine* e, const wv_decay_plan* plan, const wv_biquad*
 int wv_fetch_decay_bands(wv_engine* e, double* dst, uint64_t* captures) {
     WV_NEED(e);
     return e->fetch_decay_bands(dst, captures);
+}
+int wv_set_intensity(wv_engine* e, const wv_intensity_plan* plan) {
+    WV_NEED(e);
+    return e->set_intensity(plan);
+}
+int wv_intensity_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
+    WV_NEED(e);
+    return e->intensity_count(captures, last_step);
+}
+int wv_fetch_intensity(wv_engine* e, double* dst, uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_intensity(dst, captures);
+}
+int wv_fetch_intensity_velocity(wv_engine* e, double* dst) {
+    WV_NEED(e);
+    return e->fetch_intensity_velocity(dst);
+}
+int wv_fetch_directional_velocity(wv_engine* e, double* dst) {
+    WV_NEED(e);
+    return e->fetch_directional_velocity(dst);
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

@@ -23,6 +23,9 @@
 //   engine_decay.hip.h   time-binned field energy accumulated on the device while a run goes on (wv_set_decay): plan, stage, fold, fetch
 //   decay_plan.h         (host only, no HIP) the bin of a capture, sizes, the fold's traffic model
 //   decay_bands_kernels.hip.h   the fold of a band-limited decay plan (wv_set_decay_bands): biquad cascades ahead of the square
+//   engine_intensity.hip.h  time-binned sound intensity of a box accumulated on the device (wv_set_intensity): plan, stage, fold, fetch
+//   intensity_plan.h     (host only, no HIP) what an intensity plan is refused for, sizes, the fold's traffic model
+//   intensity_kernels.hip.h   its capture (pressure and gradient differences of every taken node) and its fold
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -32,6 +35,7 @@
 #include "snapshot_plan.h"
 #include "spectrum_plan.h"
 #include "decay_plan.h"
+#include "intensity_plan.h"
 #include "capture_stage.h"
 
 #include "boundary_kernels.hip.h"
@@ -42,6 +46,7 @@
 #include "spectrum_kernels.hip.h"
 #include "decay_kernels.hip.h"
 #include "decay_bands_kernels.hip.h"
+#include "intensity_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -174,6 +179,7 @@ public:
     // ---- engine_directional.hip.h
     int set_directional_receivers(const uint64_t* nodes, uint32_t n, double spacing, double sample_rate, double ambient_density) override;
     int fetch_directional(uint64_t first, uint64_t n, wv_directional_output* dst) override;
+    int fetch_directional_velocity(double* dst) override;
     // ---- engine_snapshot.hip.h
     int set_snapshots(const wv_snapshot_plan* plan) override;
     int snapshot_count(uint64_t* taken, uint64_t* first_held) override;
@@ -191,6 +197,12 @@ public:
     int set_decay_bands(const wv_decay_plan* plan, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) override;
     int fetch_decay_bands(double* dst, uint64_t* captures) override;
     bool decay_active() const override { return decay_.active; }
+    // ---- engine_intensity.hip.h
+    int set_intensity(const wv_intensity_plan* plan) override;
+    int intensity_count(uint64_t* captures, uint64_t* last_step) override;
+    int fetch_intensity(double* dst, uint64_t* captures) override;
+    int fetch_intensity_velocity(double* dst) override;
+    bool intensity_active() const override { return inten_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -420,6 +432,10 @@ private:
         double* decay_state = nullptr;  // a banded plan's filter states, likewise
         size_t decay_state_bytes = 0;
         uint64_t decay_generation = 0, decay_captures = 0, decay_last_step = 0, decay_next = 0;
+        double* inten_bins = nullptr;      // the intensity plan's bins and velocities (engine_intensity.hip.h), likewise
+        double* inten_velocity = nullptr;
+        size_t inten_bytes = 0, inten_velocity_bytes = 0;
+        uint64_t inten_generation = 0, inten_captures = 0, inten_last_step = 0, inten_next = 0;
     } ckpt_;
     // field snapshots (engine_snapshot.hip.h): a ring of device slots the capture kernel fills on the compute stream, each copied to its
     // page-locked twin on a stream of its own, and the log of the snapshots the host holds
@@ -525,13 +541,53 @@ private:
     int decay_begin_run();
     int decay_checkpoint();
     int decay_rollback();
-    // whichever plan is active decides where passes end (engine_batch.hip.h): the three exclude each other
-    bool capture_plan_active() const { return snap_.active || spec_.active || decay_.active; }
-    uint64_t capture_next() const { return snap_.active ? snap_.next : spec_.active ? spec_.st.next : decay_.active ? decay_.st.next : wv::kNoSnapshotStep; }
-    uint64_t capture_batch_end() const {
-        return snap_.active ? snap_.batch_end : spec_.active ? spec_.st.batch_end : decay_.active ? decay_.st.batch_end : wv::kNoSnapshotStep;
+    // intensity maps (engine_intensity.hip.h): the device-only stage of four float planes per capture the capture kernel fills on the
+    // compute stream, the velocities the integrator carries per node, the time-binned sums Ix, Iy, Iz, E the fold kernel accumulates,
+    // two tables of the staged captures' bins (page-locked, and their device copies) the host writes in turn
+    struct Intensity {
+        bool active = false;
+        wv_intensity_plan plan{};
+        wv::SnapshotBox box;
+        uint64_t generation = 0;        // bumped by every wv_set_intensity (a checkpoint remembers which plan it saw)
+        wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
+        uint64_t nodes = 0;             // B: nodes taken
+        double k = 0;                   // ambient_density * sample_rate
+        float* stage = nullptr;         // [T][4][B]: pressure, gx, gy, gz
+        double* velocity = nullptr;     // [3][B]
+        double* bins = nullptr;         // [4][n_bins][B]: Ix, Iy, Iz, E
+        int32_t* table_host[2] = {nullptr, nullptr};
+        int32_t* table_dev[2] = {nullptr, nullptr};
+        hipEvent_t begun[2] = {nullptr, nullptr};      // before the fold that uses the table (kernel timing)
+        hipEvent_t folded_ev[2] = {nullptr, nullptr};  // behind it: the host may write the table again
+        bool table_used[2] = {false, false}, timed[2] = {false, false};
+        int table = 0;                  // the table the next fold writes
+        uint64_t folds = 0;             // WV_QUERY_INTENSITY_FOLDS
+        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
+        hipEvent_t gather_begun[wv::kIntensityStage] = {}, gather_done[wv::kIntensityStage] = {};  // around a slot's capture (kernel timing)
+        bool gather_timed[wv::kIntensityStage] = {};
+        double gather_ms = 0;           // capture kernels' time (kernel timing on), over gathers_timed of them
+        uint64_t gathers_timed = 0;
+    } inten_;
+    static void intensity_release(Intensity& d);
+    int launch_intensity_gather(const wv::SnapshotBox& box, double spacing, float* dst);  // (engine_snapshot.hip.h, beside launch_snapshot_gather)
+    int intensity_capture(uint64_t step);
+    int intensity_drain_timing(int table = -1);
+    int intensity_fold();
+    int intensity_plan_batch();
+    int intensity_begin_run();
+    int intensity_checkpoint();
+    int intensity_rollback();
+    // whichever plan is active decides where passes end (engine_batch.hip.h): they all exclude each other
+    bool capture_plan_active() const { return snap_.active || spec_.active || decay_.active || inten_.active; }
+    uint64_t capture_next() const {
+        return snap_.active ? snap_.next : spec_.active ? spec_.st.next : decay_.active ? decay_.st.next : inten_.active ? inten_.st.next : wv::kNoSnapshotStep;
     }
-    int capture_step(uint64_t step) { return snap_.active ? snapshot_capture(step) : spec_.active ? spectrum_capture(step) : decay_capture(step); }
+    uint64_t capture_batch_end() const {
+        return snap_.active ? snap_.batch_end : spec_.active ? spec_.st.batch_end : decay_.active ? decay_.st.batch_end : inten_.active ? inten_.st.batch_end : wv::kNoSnapshotStep;
+    }
+    int capture_step(uint64_t step) {
+        return snap_.active ? snapshot_capture(step) : spec_.active ? spectrum_capture(step) : decay_.active ? decay_capture(step) : intensity_capture(step);
+    }
 };
 
 }  // namespace wv

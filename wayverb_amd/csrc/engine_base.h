@@ -102,6 +102,12 @@ struct wv_engine {
     virtual int set_decay_bands(const wv_decay_plan* plan, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) = 0;
     virtual int fetch_decay_bands(double* dst, uint64_t* captures) = 0;
     virtual bool decay_active() const = 0;
+    virtual int set_intensity(const wv_intensity_plan* plan) = 0;
+    virtual int intensity_count(uint64_t* captures, uint64_t* last_step) = 0;
+    virtual int fetch_intensity(double* dst, uint64_t* captures) = 0;
+    virtual int fetch_intensity_velocity(double* dst) = 0;
+    virtual int fetch_directional_velocity(double* dst) = 0;
+    virtual bool intensity_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;
     virtual int set_source(int kind, uint64_t node, const double* signal, uint64_t n) = 0;

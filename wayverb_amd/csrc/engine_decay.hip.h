@@ -72,6 +72,7 @@ int Engine<Real>::decay_set(const wv_decay_plan* plan, const wv_biquad* sections
     // all three plans want to decide where passes end: one consumer of capture steps at a time
     if (snap_.active) return fail(WV_E_STATE, who + ": a snapshot plan is active (wv_set_snapshots(e, NULL) stops it); the plans exclude each other");
     if (spec_.active) return fail(WV_E_STATE, who + ": a spectrum plan is active (wv_set_spectrum(e, NULL, NULL) stops it); the plans exclude each other");
+    if (inten_.active) return fail(WV_E_STATE, who + ": an intensity plan is active (wv_set_intensity(e, NULL) stops it); the plans exclude each other");
     // the two kinds of decay plan answer to different fetches: neither setter turns one into the other behind the caller's back
     if (decay_.active && banded && !decay_.n_bands)
         return fail(WV_E_STATE, "wv_set_decay_bands: a plain decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");

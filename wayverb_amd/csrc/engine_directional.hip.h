@@ -116,4 +116,15 @@ int Engine<Real>::fetch_directional(uint64_t first, uint64_t n, wv_directional_o
     return WV_OK;
 }
 
+// The integrator's carried state as it lies, [n][3]: what the records of the completed steps left behind.
+template <typename Real>
+int Engine<Real>::fetch_directional_velocity(double* dst) {
+    DeviceGuard guard(device_);
+    if (!dir_.active) return fail(WV_E_STATE, "wv_fetch_directional_velocity: no directional receivers are set (wv_set_directional_receivers)");
+    if (!dst) return fail(WV_E_INVALID_ARGUMENT, "null argument");
+    WV_HIP(hipStreamSynchronize(stream_));
+    WV_HIP(hipMemcpy(dst, dir_.velocity, (size_t)dir_.n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return WV_OK;
+}
+
 }  // namespace wv

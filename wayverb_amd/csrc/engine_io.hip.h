@@ -355,6 +355,8 @@ int Engine<Real>::checkpoint(int op) {
         if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
         if (ckpt_.decay_bins) (void)hipFree(ckpt_.decay_bins);
         if (ckpt_.decay_state) (void)hipFree(ckpt_.decay_state);
+        if (ckpt_.inten_bins) (void)hipFree(ckpt_.inten_bins);
+        if (ckpt_.inten_velocity) (void)hipFree(ckpt_.inten_velocity);
         ckpt_ = Checkpoint{};
         return WV_OK;
     }
@@ -404,6 +406,12 @@ int Engine<Real>::checkpoint(int op) {
             if (rc) return rc;
         }
         ckpt_.decay_generation = decay_.generation;
+        // the intensity plan's bins and velocities, count and next plan step (engine_intensity.hip.h): likewise
+        if (inten_.active) {
+            const int rc = intensity_checkpoint();
+            if (rc) return rc;
+        }
+        ckpt_.inten_generation = inten_.generation;
         WV_HIP(hipMemcpyAsync(ckpt_.field[0], field_[cur_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.field[1], field_[prv_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.fmem, fmem_, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
@@ -434,6 +442,8 @@ int Engine<Real>::checkpoint(int op) {
         return fail(WV_E_STATE, "wv_rollback: the spectrum plan was set after the checkpoint (its sums have no copy to go back to)");
     if (decay_.active && ckpt_.decay_generation != decay_.generation)
         return fail(WV_E_STATE, "wv_rollback: the decay plan was set after the checkpoint (its bins have no copy to go back to)");
+    if (inten_.active && ckpt_.inten_generation != inten_.generation)
+        return fail(WV_E_STATE, "wv_rollback: the intensity plan was set after the checkpoint (its bins have no copy to go back to)");
     WV_HIP(hipMemcpyAsync(field_[cur_], ckpt_.field[0], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(field_[prv_], ckpt_.field[1], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(fmem_, ckpt_.fmem, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
@@ -443,6 +453,10 @@ int Engine<Real>::checkpoint(int op) {
     }
     if (decay_.active) {  // bins and count back; what is staged is of abandoned steps
         const int rc = decay_rollback();
+        if (rc) return rc;
+    }
+    if (inten_.active) {  // bins, velocities and count back; what is staged is of abandoned steps
+        const int rc = intensity_rollback();
         if (rc) return rc;
     }
     if (dir_.active) {

@@ -546,6 +546,9 @@ void Engine<Real>::release() {
     spectrum_release(spec_);
     if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
     decay_release(decay_);
+    intensity_release(inten_);
+    if (ckpt_.inten_bins) (void)hipFree(ckpt_.inten_bins);
+    if (ckpt_.inten_velocity) (void)hipFree(ckpt_.inten_velocity);
     if (ckpt_.decay_bins) (void)hipFree(ckpt_.decay_bins);
     if (ckpt_.decay_state) (void)hipFree(ckpt_.decay_state);
     for (auto& e : events_) (void)hipEventDestroy(e);

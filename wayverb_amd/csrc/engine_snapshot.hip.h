@@ -50,6 +50,7 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
     // (a spectrum plan cuts the passes at its own steps: one consumer of capture steps at a time, engine_spectrum.hip.h)
     if (spec_.active) return fail(WV_E_STATE, "wv_set_snapshots: a spectrum plan is active (wv_set_spectrum(e, NULL, NULL) stops it); the two plans exclude each other");
     if (decay_.active) return fail(WV_E_STATE, "wv_set_snapshots: a decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");
+    if (inten_.active) return fail(WV_E_STATE, "wv_set_snapshots: an intensity plan is active (wv_set_intensity(e, NULL) stops it); the plans exclude each other");
     wv::SnapshotBox box;
     box.x0 = plan->x0, box.y0 = plan->y0, box.z0 = plan->z0;
     box.nx = plan->nx, box.ny = plan->ny, box.nz = plan->nz;
@@ -118,6 +119,28 @@ int Engine<Real>::launch_snapshot_gather(const wv::SnapshotBox& box, bool wide, 
         hipLaunchKernelGGL((wv::snapshot_gather_kernel<Real, true>), grid, dim3(256), 0, stream_, a);
     else
         hipLaunchKernelGGL((wv::snapshot_gather_kernel<Real, false>), grid, dim3(256), 0, stream_, a);
+    WV_HIP(hipGetLastError());
+    return WV_OK;
+}
+
+// intensity_gather_kernel (intensity_kernels.hip.h) on the compute stream: per node of `box` the pressure and the three float
+// differences of its neighbours' gradients, from the field `current` -> the four dense planes at `dst`.  The one launch site of that
+// kernel (an intensity plan's capture, engine_intensity.hip.h); the box keeps clear of the mesh's faces (intensity_plan.h).
+template <typename Real>
+int Engine<Real>::launch_intensity_gather(const wv::SnapshotBox& box, double spacing, float* dst) {
+    wv::IntensityGatherArgs<Real> a{};
+    a.field = field_[cur_];
+    a.dst = dst;
+    a.pitch = pitch_;
+    a.nodes = (int64_t)wv::snapshot_elements(box);
+    a.mesh_ny = ny_;
+    a.x0 = box.x0, a.y0 = box.y0, a.z0 = box.z0;
+    a.nx = box.nx, a.ny = box.ny, a.nz = box.nz;
+    a.sx = box.sx, a.sy = box.sy, a.sz = box.sz;
+    a.spacing = spacing;
+    const uint64_t items = (uint64_t)box.nx * (uint64_t)box.ny;
+    const dim3 grid((unsigned)std::min<uint64_t>((items + 255) / 256, 1u << 14), (unsigned)std::min(box.nz, 1024));
+    hipLaunchKernelGGL((wv::intensity_gather_kernel<Real>), grid, dim3(256), 0, stream_, a);
     WV_HIP(hipGetLastError());
     return WV_OK;
 }

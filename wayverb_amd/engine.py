@@ -40,6 +40,7 @@ EXPORTS = [
     "wv_set_spectrum", "wv_spectrum_count", "wv_fetch_spectrum", "wv_spectrum_twiddle",
     "wv_set_decay", "wv_decay_count", "wv_fetch_decay",
     "wv_set_decay_bands", "wv_fetch_decay_bands", "wv_biquad_run", "wv_butterworth_bandpass", "wv_bandpass_biquad",
+    "wv_set_intensity", "wv_intensity_count", "wv_fetch_intensity", "wv_fetch_intensity_velocity", "wv_fetch_directional_velocity",
 ]
 
 
@@ -89,6 +90,12 @@ class WvDecayPlan(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
                 ("sx", C.c_int32), ("sy", C.c_int32), ("sz", C.c_int32), ("first_step", C.c_uint64), ("period", C.c_uint64),
                 ("n_bins", C.c_uint32), ("bin_captures", C.c_uint32)]
+
+
+class WvIntensityPlan(C.Structure):
+    """wv_intensity_plan (include/wayverb_amd.h): wv_decay_plan's fields, then the three arguments of the reference's
+    directional_receiver constructor."""
+    _fields_ = WvDecayPlan._fields_ + [("spacing", C.c_double), ("sample_rate", C.c_double), ("ambient_density", C.c_double)]
 
 
 # Tuning applied to every engine this module creates unless the call says otherwise: {field of wv_tuning: value}, plus
@@ -203,6 +210,11 @@ def load_library():
     lib.wv_fetch_decay.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.wv_set_decay_bands.argtypes = [C.c_void_p, C.POINTER(WvDecayPlan), C.c_void_p, C.c_uint32, C.c_uint32]
     lib.wv_fetch_decay_bands.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.wv_set_intensity.argtypes = [C.c_void_p, C.POINTER(WvIntensityPlan)]
+    lib.wv_intensity_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.wv_fetch_intensity.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.wv_fetch_intensity_velocity.argtypes = [C.c_void_p, C.c_void_p]
+    lib.wv_fetch_directional_velocity.argtypes = [C.c_void_p, C.c_void_p]
     lib.wv_biquad_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.wv_butterworth_bandpass.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.wv_bandpass_biquad.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
@@ -391,6 +403,7 @@ class Engine:
         self.spectrum_shape = None
         self.decay_shape = None
         self.decay_banded = False
+        self.intensity_shape = None
 
     @classmethod
     def from_handle(cls, handle, mesh, precision):
@@ -407,6 +420,7 @@ class Engine:
         eng.spectrum_shape = None
         eng.decay_shape = None
         eng.decay_banded = False
+        eng.intensity_shape = None
         return eng
 
     def close(self):
@@ -677,6 +691,56 @@ class Engine:
             _check(self.lib.wv_fetch_decay(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
         return out, captures.value
 
+    # ---- time-binned sound intensity accumulated on the device while wv_run goes on ------------------
+    def set_intensity(self, n_bins, bin_captures=1, box=None, stride=1, first_step=0, period=1, spacing=None, sample_rate=None,
+                      ambient_density=None):
+        """wv_set_intensity.  `box`, `stride`, `first_step`, `period` as for set_snapshots (None: the mesh's interior -- every taken
+        node needs its six neighbours on the grid).  At every plan step the engine runs the reference's directional_receiver
+        integrator at every node taken -- velocity from the pressure differences to the six neighbours, with `spacing`,
+        `sample_rate` (of the CAPTURED series: the mesh's rate / period) and `ambient_density` -- and adds v * p per axis and p * p
+        to the time bin of the capture, in double, in capture order; intensity.intensity_bins over snapshots of the box's hull
+        reproduces bins and velocities bit for bit.  Excludes every other plan.  set_intensity(None) stops and forgets.  Returns the
+        shape (4, n_bins, nz, ny, nx): Ix, Iy, Iz, E."""
+        if n_bins is None:
+            _check(self.lib.wv_set_intensity(self.h, None))
+            self.intensity_shape = None
+            return None
+        if box is None:
+            box = ((1, 1, 1), tuple(d - 2 for d in self.mesh.dims))
+        plan = WvIntensityPlan()
+        taken = self._fill_box(plan, box, stride)
+        plan.first_step, plan.period, plan.n_bins, plan.bin_captures = int(first_step), int(period), int(n_bins), int(bin_captures)
+        plan.spacing, plan.sample_rate, plan.ambient_density = float(spacing), float(sample_rate), float(ambient_density)
+        _check(self.lib.wv_set_intensity(self.h, C.byref(plan)))
+        self.intensity_shape = (4, int(n_bins), taken[2], taken[1], taken[0])
+        return self.intensity_shape
+
+    def intensity_count(self):
+        """wv_intensity_count: (captures of completed steps since the plan was set, the step of the last of them)."""
+        captures, last = C.c_uint64(), C.c_uint64()
+        _check(self.lib.wv_intensity_count(self.h, C.byref(captures), C.byref(last)))
+        return captures.value, last.value
+
+    def fetch_intensity(self):
+        """wv_fetch_intensity: (float64[4, n_bins, nz, ny, nx] = Ix, Iy, Iz, E, captures in it).  The plan keeps running."""
+        out = np.zeros(tuple(getattr(self, "intensity_shape", None) or (0, 0, 0, 0, 0)), dtype=np.float64)   # (no plan: the library says so)
+        captures = C.c_uint64()
+        _check(self.lib.wv_fetch_intensity(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
+        return out, captures.value
+
+    def fetch_intensity_velocity(self):
+        """wv_fetch_intensity_velocity: float64[3, nz, ny, nx], the velocities the integrator carries, after the captures folded so far."""
+        shape = getattr(self, "intensity_shape", None)
+        out = np.zeros((3,) + tuple(shape[2:]) if shape else (0, 0, 0, 0), dtype=np.float64)
+        _check(self.lib.wv_fetch_intensity_velocity(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def fetch_directional_velocity(self, n):
+        """wv_fetch_directional_velocity: float64[n, 3], the carried velocities of the n directional receivers."""
+        out = np.zeros((int(n), 3), dtype=np.float64)
+        _check(self.lib.wv_fetch_directional_velocity(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def step_count(self):
         s = C.c_uint64()
         _check(self.lib.wv_step_count(self.h, C.byref(s)))
@@ -709,6 +773,7 @@ class Engine:
     QUERY_WIDE_GATHERS, QUERY_DIRECTIONAL_LAUNCHES = 24, 25
     QUERY_SPECTRUM_CAPTURES, QUERY_SPECTRUM_FOLDS, QUERY_SPECTRUM_NS = 26, 27, 28
     QUERY_DECAY_CAPTURES, QUERY_DECAY_FOLDS, QUERY_DECAY_NS = 29, 30, 31
+    QUERY_INTENSITY_CAPTURES, QUERY_INTENSITY_FOLDS, QUERY_INTENSITY_NS, QUERY_INTENSITY_GATHER_NS, QUERY_INTENSITY_GATHERS = 32, 33, 34, 35, 36
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

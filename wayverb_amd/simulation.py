@@ -107,8 +107,37 @@ def compute_voxels_and_mesh(vertices, triangles, surface_absorptions, anchor, sa
     return VoxelsAndMesh(vox, (c0, c1), side, vertices, triangles, mesh, c0, absorptions)
 
 
+def intensity_plan_arguments(intensity, mesh, sample_rate, environment, simulation_time):
+    """canonical's `intensity` dict -> keyword arguments of Engine.set_intensity: dict(plane=z in metres | box=((x0, y0, z0), extent),
+    stride=1, every=1, n_bins=None, bin_seconds=None).  `plane`: that horizontal plane less its rim (every taken node needs its six
+    neighbours on the grid).  The bins are `bin_seconds` long (default: the run in `n_bins` bins, default 1); spacing, the rate of the
+    captured series (sample_rate / every) and the environment's density are filled in."""
+    unknown = set(intensity) - {"plane", "box", "stride", "every", "n_bins", "bin_seconds", "first_step"}
+    if unknown or ("plane" in intensity) == ("box" in intensity):
+        raise ValueError("intensity=dict(plane=<z in metres> or box=..., every=, n_bins=, bin_seconds=, stride=, first_step=)")
+    every = int(intensity.get("every", 1))
+    if every < 1:
+        raise ValueError("intensity: every must be >= 1")
+    if "plane" in intensity:
+        plane = int(round((float(intensity["plane"]) - mesh.min_corner[2]) / mesh.spacing))
+        if not 1 <= plane <= mesh.dims[2] - 2:
+            raise ValueError("intensity: plane z=%g m has no node with both neighbours in the mesh" % float(intensity["plane"]))
+        box = ((1, 1, plane), (mesh.dims[0] - 2, mesh.dims[1] - 2, 1))
+    else:
+        box = intensity["box"]
+    captures = int(math.ceil(sample_rate * simulation_time)) // every + 1
+    if intensity.get("bin_seconds") is not None:
+        bin_captures = max(1, int(round(float(intensity["bin_seconds"]) * sample_rate / every)))
+        n_bins = int(intensity["n_bins"]) if intensity.get("n_bins") is not None else max(1, min(4096, -(-captures // bin_captures)))
+    else:
+        n_bins = int(intensity.get("n_bins") or 1)
+        bin_captures = max(1, -(-captures // n_bins))
+    return dict(n_bins=n_bins, bin_captures=bin_captures, box=box, stride=intensity.get("stride", 1), first_step=int(intensity.get("first_step", 0)),
+                period=every, spacing=mesh.spacing, sample_rate=sample_rate / every, ambient_density=environment.ambient_density)
+
+
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
-              device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None, decay=None):
+              device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None, decay=None, intensity=None):
     """canonical (single band): hard source at `source`, directional receiver at `receiver`, for
     ceil(sample_rate * simulation_time) steps.  Returns [(directional records, sample_rate,
     (0, cutoff))] -- the bandpass_band list waveguide::postprocess takes -- or None when stopped early.
@@ -130,7 +159,14 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     with `snapshots` or `spectrum` the engine refuses the second plan (engine.WaveguideError, with the plan to stop in its message).
     With `bands=[(lo_hz, hi_hz), ...]` in it (8 at the most) every node's captures go through a 4th-order Butterworth band-pass per
     band before the square (Engine.set_decay(bands=...); wayverb_amd.decay.butterworth_bandpass designs the sections at the rate of
-    the captured series, sample_rate / period) and the bins are float64[K, n_bins, nz, ny, nx] (decay.band_decay_maps)."""
+    the captured series, sample_rate / period) and the bins are float64[K, n_bins, nz, ny, nx] (decay.band_decay_maps).
+    `intensity`: dict(plane=<z in metres> or box=..., every=, n_bins=, bin_seconds=) (intensity_plan_arguments) -- the engine runs the
+    directional receiver's integrator at every node of that plane or box and sums the sound intensity and the squared pressure into
+    time bins on the device (Engine.set_intensity; spacing, sample_rate / every and the environment's density are filled in); the
+    return value is then (bands, (float64[4, n_bins, nz, ny, nx], captures)), which wayverb_amd.intensity turns into direction and
+    diffuseness maps.  One domain only, and not together with another plan."""
+    if intensity is not None and slabs > 1:
+        raise ValueError("intensity bins are accumulated on one domain only (slabs=1)")
     if decay is not None and slabs > 1:
         raise ValueError("decay bins are accumulated on one domain only (slabs=1)")
     if snapshots is not None and slabs > 1:
@@ -146,6 +182,7 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
         from . import decay as D
         series_rate = sample_rate / int(decay.get("period", 1))
         decay = dict(decay, bands=np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in decay["bands"]]))
+    intensity_plan = intensity_plan_arguments(intensity, mesh, sample_rate, environment, simulation_time) if intensity is not None else None
 
     def mesh_index(pt):
         idx = vm.compute_index(pt)
@@ -174,6 +211,8 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 eng.set_spectrum(**spectrum_plan)
             if decay is not None:
                 eng.set_decay(**decay)
+            if intensity_plan is not None:
+                eng.set_intensity(**intensity_plan)
             done, traces = E.run_fast(eng, E.SOURCE_HARD, mesh_index(source), signal, [receiver_index] + list(neighbours),
                                       keep_going=keep_going)
             taken = eng.fetch_snapshots() if snapshots is not None else None
@@ -181,13 +220,15 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 taken = eng.fetch_spectrum()
             if decay is not None:
                 taken = eng.fetch_decay()
+            if intensity_plan is not None:
+                taken = eng.fetch_intensity()
         finally:
             eng.close()
     if done != ideal_steps:
         return None
     directional = P.directional_receiver(traces, mesh.spacing, sample_rate, environment.ambient_density)
     bands = [(directional, sample_rate, (0.0, float(cutoff)))]
-    return bands if snapshots is None and spectrum is None and decay is None else (bands, taken)
+    return bands if snapshots is None and spectrum is None and decay is None and intensity is None else (bands, taken)
 
 
 def spectrum_plan_arguments(spectrum, sample_rate):
@@ -307,18 +348,20 @@ def canonical_multiband(vm, source, receiver, environment, bands, cutoff, usable
 
 def impulse_response(vertices, triangles, surface_absorptions, source, receiver, cutoff=200.0, usable_portion=0.6,
                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
-                     pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None, decay=None):
+                     pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None, decay=None,
+                     intensity=None):
     """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio.
     `snapshots`: a function mesh -> keyword arguments of Engine.set_snapshots (the mesh's size is not known before it is built),
     or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member.
     `spectrum`: a function mesh -> canonical's `spectrum` dict, or the dict; the fourth member is then (spectrum, captures).
-    `decay`: a function (mesh, sample_rate) -> canonical's `decay` dict, or the dict; the fourth member is then (bins, captures)."""
+    `decay`: a function (mesh, sample_rate) -> canonical's `decay` dict, or the dict; the fourth member is then (bins, captures).
+    `intensity`: canonical's `intensity` dict; the fourth member is then (bins [4, n_bins, nz, ny, nx], captures)."""
     environment = environment or Environment()
     vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
     if spectrum is not None and snapshots is not None:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
-    if snapshots is None and spectrum is None and decay is None:
+    if snapshots is None and spectrum is None and decay is None and intensity is None:
         bands = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device)
         taken = None
     else:
@@ -329,6 +372,8 @@ def impulse_response(vertices, triangles, surface_absorptions, source, receiver,
         if decay is not None:
             rate = compute_sample_rate(vm.mesh.spacing, environment.speed_of_sound)
             plans["decay"] = decay(vm.mesh, rate) if callable(decay) else decay
+        if intensity is not None:
+            plans["intensity"] = intensity
         both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, **plans)
         if both is None:
             raise RuntimeError("the waveguide run was stopped early")
