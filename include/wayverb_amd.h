@@ -566,6 +566,70 @@ int wv_fetch_intensity(wv_engine* e, double* dst /* [4][n_bins][nz][ny][nx]: Ix,
 int wv_fetch_intensity_velocity(wv_engine* e, double* dst /* [3][nz][ny][nx] */);
 int wv_fetch_directional_velocity(wv_engine* e, double* dst /* [n][3] */);
 
+/* ---- arrival-aligned energy maps: onset, peak and energy binned from each node's own arrival ---- */
+/* Decay and intensity maps bin every node by ONE clock: the capture's number since the plan was set.  Clarity C50 / C80, definition
+ * D50 and centre time Ts (ISO 3382) measure early and late energy from the arrival of the direct sound AT THAT SEAT, and across a
+ * hall the direct sound arrives tens of milliseconds apart -- the size of the 50 / 80 ms windows themselves.  An arrival plan has
+ * the engine capture a box exactly as a decay plan captures it and keep, per node taken and on the device: the capture at which the
+ * node's direct sound arrived (its onset), the node's peak and when it occurred, the squared pressure summed into bins counted from
+ * the node's OWN onset, the energy ahead of the onset, and the first time moment of the energy behind it.  What crosses the link is
+ * 28 + 8 n_bins bytes per node when the caller asks, however long the run; wayverb_amd/arrival.py turns it into arrival time, direct
+ * level, C50 / C80, D50 and Ts.
+ *
+ * Definition.  p_c is the float a snapshot of the same plan holds for the node (the snapshot block above, unchanged); c = 0, 1, ...
+ * counts the committed captures since the plan was set.  thr is the node's threshold: the plan's scalar, or the node's entry of
+ * threshold_map.  The state starts as onset = NONE (0xFFFFFFFF), peak = +0.0f, peak_capture = NONE, pre = M = E[k] = +0.0, and per
+ * capture, in capture order:
+ *     a  = fabsf(p_c)
+ *     if (a > peak)                    { peak = a; peak_capture = c; }     strict: the FIRST occurrence; a NaN changes nothing
+ *     if (onset == NONE && a >= thr)   onset = c;                          the onset capture itself falls into bin 0
+ *     sq = (double)p_c * (double)p_c                                       exact
+ *     if (onset == NONE)  pre = pre + sq;
+ *     else { rel = c - onset;  k = the largest k with edges[k] <= rel;
+ *            E[k] = E[k] + sq;  M = M + (double)rel * sq; }                the product is rounded, then the sum; nothing is contracted
+ * edges[0] = 0 < edges[1] < ... < edges[n_bins - 1] are in captures behind the onset; the last bin is open-ended.  A loop over the
+ * snapshots that evaluates these lines (wayverb_amd/arrival.py: arrival_fold; the float lines on float32 arrays, the rest on float64)
+ * reproduces all six outputs BIT FOR BIT.  A threshold of 0 is legal: every onset is then capture 0, `pre` stays +0.0 and with
+ * edges[k] = k W the bins are, bit for bit, a decay plan's of the same box, cadence and bin_captures = W.
+ *
+ *   - 1 <= n_bins <= 16, edges as above, the threshold (and every entry of the map) >= 0 and finite, strides and period >= 1;
+ *     otherwise, and for a box that leaves the mesh: WV_E_INVALID_ARGUMENT
+ *   - everything (the stage of 16 captures, 64 bytes per node; the state, 28 + 8 n_bins bytes per node; the map's copy, 4 bytes per
+ *     node where one is given) is allocated when the plan is set: with no room the call answers WV_E_HIP and leaves the engine and
+ *     any earlier plan untouched.  The map is copied: the caller's array is free when the call returns.  A new plan replaces the old
+ *     one and forgets its state; a NULL plan stops, forgets and frees (as does wv_destroy)
+ *   - one domain only: a slab of a chain answers WV_E_STATE, and wv_run_group refuses an engine with a plan
+ *   - an arrival plan excludes the snapshot plan, the spectrum plan, both kinds of decay plan and the intensity plan: every setter
+ *     answers WV_E_STATE while another plan is active, and wv_last_error names the plan to stop
+ *   - after a run that stopped on a flag at step f the state has seen exactly the captures of steps <= f: no onset, peak or sum of a
+ *     step that was never committed
+ *   - wv_step / wv_swap capture nothing; the plan steps they pass are gaps in the series, and `rel` counts captures, not steps
+ *   - captures are numbered with 32 bits: wv_run answers WV_E_STATE rather than take capture 2^32 - 1
+ *   - wv_checkpoint folds what is staged and copies all per-node state, the capture count and the next plan step aside (the copy is
+ *     allocated by the first checkpoint taken under a plan: WV_E_HIP, engine untouched, when there is no room); wv_rollback puts
+ *     them back, and the re-run is bitwise the same.  A plan set AFTER the checkpoint makes wv_rollback answer WV_E_STATE
+ *   - with no plan nothing is launched, allocated or waited for; with one the fields, receiver rows and flags are bit-identical to
+ *     a run without
+ *
+ * wv_arrival_count: as wv_decay_count.  wv_fetch_arrival: onset, peak, peak_capture, pre and moment are [nz][ny][nx], bins is
+ * float64 [n_bins][nz][ny][nx]; ANY destination may be NULL and is then skipped; *captures (may be NULL) = how many captures they
+ * hold.  It may be called any time outside wv_run, folds what is staged and leaves the plan running.  The step of a node's onset is
+ * first_step + onset * period when the run was one wv_run after another from the step the plan was set at. */
+typedef struct wv_arrival_plan {
+    int32_t x0, y0, z0;    /* first node of the box */
+    int32_t nx, ny, nz;    /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;    /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step;   /* captures at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;       /* >= 1 */
+    uint32_t n_bins;       /* 1 .. 16 */
+    float threshold;       /* >= 0, finite; used where threshold_map is NULL */
+    uint32_t edges[16];    /* first relative capture of bin k; edges[0] == 0, strictly increasing over n_bins entries */
+} wv_arrival_plan;
+int wv_set_arrival(wv_engine* e, const wv_arrival_plan* plan, const float* threshold_map /* [nz][ny][nx] or NULL; every entry >= 0, finite */);
+int wv_arrival_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
+int wv_fetch_arrival(wv_engine* e, uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment,
+                     double* bins /* [n_bins][nz][ny][nx] */, uint64_t* captures);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */
@@ -605,7 +669,8 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *                            launches of the decay plan's fold kernel, their total time with kernel timing on
  *   WV_QUERY_INTENSITY_CAPTURES, WV_QUERY_INTENSITY_FOLDS, WV_QUERY_INTENSITY_NS   the same three since wv_set_intensity
  *   WV_QUERY_INTENSITY_GATHER_NS, WV_QUERY_INTENSITY_GATHERS   total time of the intensity plan's capture kernels that ran with kernel
- *                            timing on, and how many of them that is */
+ *                            timing on, and how many of them that is
+ *   WV_QUERY_ARRIVAL_CAPTURES, WV_QUERY_ARRIVAL_FOLDS, WV_QUERY_ARRIVAL_NS   the decay plan's three since wv_set_arrival */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -625,7 +690,8 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
        WV_QUERY_SPECTRUM_CAPTURES = 26, WV_QUERY_SPECTRUM_FOLDS = 27, WV_QUERY_SPECTRUM_NS = 28,
        WV_QUERY_DECAY_CAPTURES = 29, WV_QUERY_DECAY_FOLDS = 30, WV_QUERY_DECAY_NS = 31,
        WV_QUERY_INTENSITY_CAPTURES = 32, WV_QUERY_INTENSITY_FOLDS = 33, WV_QUERY_INTENSITY_NS = 34,
-       WV_QUERY_INTENSITY_GATHER_NS = 35, WV_QUERY_INTENSITY_GATHERS = 36 };
+       WV_QUERY_INTENSITY_GATHER_NS = 35, WV_QUERY_INTENSITY_GATHERS = 36,
+       WV_QUERY_ARRIVAL_CAPTURES = 37, WV_QUERY_ARRIVAL_FOLDS = 38, WV_QUERY_ARRIVAL_NS = 39 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

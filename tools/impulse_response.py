@@ -86,6 +86,17 @@ def main():
     ap.add_argument("--intensity-out", default="intensity.npz",
                     help="the maps go here: bins float64[4, n_bins, ny, nx] (Ix, Iy, Iz, E), times (seconds at which each bin begins), "
                          "net_direction [3, ny, nx], net_magnitude, diffuseness [ny, nx], captures, period, sample_rate, spacing")
+    ap.add_argument("--clarity-map", action="store_true",
+                    help="keep, per node of one horizontal plane and on the device, when the direct sound arrives, the peak, and the "
+                         "squared pressure in bins of 0-50, 50-80 and 80+ ms counted from the node's OWN arrival (Engine.set_arrival; "
+                         "single-band runs, no other plan): arrival time, direct level, C50, C80, D50 and centre time maps")
+    ap.add_argument("--arrival-plane", default=None, metavar="z=METRES", help="the height of that plane (default: the receiver's)")
+    ap.add_argument("--arrival-threshold", type=float, default=1e-4,
+                    help="the pressure magnitude that counts as the arrival of the direct sound (default 1e-4; the source's impulse is 1)")
+    ap.add_argument("--arrival-every", type=int, default=1, help="capture every N-th step (arrival times are then known to N steps)")
+    ap.add_argument("--arrival-out", default="arrival.npz",
+                    help="the maps go here: onset, peak, peak_capture, pre, moment [ny, nx], bins [3, ny, nx], edges, arrival_s, direct_db, "
+                         "c50_db, c80_db, d50, d80, ts_s, pre_fraction, captures, period, sample_rate, plane, origin, spacing")
     args = ap.parse_args()
 
     bands = None
@@ -197,11 +208,21 @@ def main():
             ap.error("--intensity-every must be >= 1 and --intensity-bin-ms positive")
         intensity = dict(plane=float(args.intensity_plane[2:]) if args.intensity_plane else args.receiver[2], every=args.intensity_every,
                          bin_seconds=args.intensity_bin_ms * 1e-3)
+    arrival = None
+    if args.clarity_map:
+        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None:
+            ap.error("--clarity-map: single-band runs without --snapshots, --spectrum, --decay-map or --intensity-map")
+        if args.arrival_plane and not args.arrival_plane.startswith("z="):
+            ap.error("--arrival-plane takes z=<metres>")
+        if args.arrival_every < 1 or not (args.arrival_threshold >= 0 and np.isfinite(args.arrival_threshold)):
+            ap.error("--arrival-every must be >= 1 and --arrival-threshold >= 0 and finite")
+        arrival = dict(plane=float(args.arrival_plane[2:]) if args.arrival_plane else args.receiver[2], every=args.arrival_every,
+                       threshold=args.arrival_threshold, early_ms=(50.0, 80.0))
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
     if len(receivers) > 1:
-        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None:
-            ap.error("several --receiver: single-band runs without --snapshots, --spectrum, --decay-map or --intensity-map")
+        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None:
+            ap.error("several --receiver: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map or --clarity-map")
         audios, per, positions, vm = W.impulse_responses(v, t, absorptions, args.source, receivers, args.cutoff, args.usable_portion,
                                                          args.seconds, args.rate, method=method, pointing=args.pointing,
                                                          shape=args.mic_shape or 0.0, precision=args.precision)
@@ -215,8 +236,8 @@ def main():
             peak = write_wav(name, audio, args.rate)
             print("wrote %s: receiver at node position (%.3f, %.3f, %.3f) (normalised, peak was %.3e)" % ((name,) + tuple(pos) + (peak,)))
         return
-    if bands and intensity is not None:
-        ap.error("--intensity-map: single-band runs only")
+    if bands and (intensity is not None or arrival is not None):
+        ap.error("--intensity-map, --clarity-map: single-band runs only")
     if bands:   # multiple_band_constant_spacing: one run per band with flat per-band walls
         env = W.Environment()
         vm = W.compute_voxels_and_mesh(v, t, absorptions, args.receiver,
@@ -228,7 +249,25 @@ def main():
         audio_etc = W.impulse_response(v, t, absorptions, args.source, args.receiver, args.cutoff,
                                        args.usable_portion, args.seconds, args.rate, method=method,
                                        pointing=args.pointing, shape=args.mic_shape or 0.0,
-                                       precision=args.precision, snapshots=snapshots, spectrum=spectrum, decay=decay, intensity=intensity)
+                                       precision=args.precision, snapshots=snapshots, spectrum=spectrum, decay=decay, intensity=intensity,
+                                       arrival=arrival)
+        if arrival is not None:
+            from wayverb_amd import arrival as A
+            env, mesh = W.Environment(), audio_etc[2].mesh
+            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
+            plan = W.arrival_plan_arguments(arrival, mesh, rate)
+            out, captures = audio_etc[3]
+            out = {k: (v[:, 0] if k == "bins" else v[0]) for k, v in out.items()}   # the one plane: [ny, nx], bins [3, ny, nx]
+            maps = A.arrival_maps(out, plan["edges"], plan["first_step"], plan["period"], rate)
+            np.savez(args.arrival_out, edges=np.array(plan["edges"]), captures=captures, period=plan["period"], sample_rate=rate,
+                     plane=plan["box"][0][2], spacing=mesh.spacing,
+                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64),
+                     **out, **maps)
+            heard = out["onset"] != A.NONE
+            c80 = maps["c80_db"][np.isfinite(maps["c80_db"])]
+            print("wrote arrival maps of plane z=%d (%d captures; %d of %d nodes heard an arrival; median C80 %s) to %s"
+                  % (plan["box"][0][2], captures, heard.sum(), heard.size, "%.1f dB" % np.median(c80) if c80.size else "not defined",
+                     args.arrival_out))
         if intensity is not None:
             from wayverb_amd import intensity as I
             env, mesh = W.Environment(), audio_etc[2].mesh

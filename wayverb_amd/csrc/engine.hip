@@ -17,6 +17,7 @@
 #include "engine_spectrum.hip.h"
 #include "engine_decay.hip.h"
 #include "engine_intensity.hip.h"
+#include "engine_arrival.hip.h"
 #include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
@@ -263,6 +264,18 @@ int wv_fetch_intensity_velocity(wv_engine* e, double* dst) {
 int wv_fetch_directional_velocity(wv_engine* e, double* dst) {
     WV_NEED(e);
     return e->fetch_directional_velocity(dst);
+}
+int wv_set_arrival(wv_engine* e, const wv_arrival_plan* plan, const float* threshold_map) {
+    WV_NEED(e);
+    return e->set_arrival(plan, threshold_map);
+}
+int wv_arrival_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
+    WV_NEED(e);
+    return e->arrival_count(captures, last_step);
+}
+int wv_fetch_arrival(wv_engine* e, uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_arrival(onset, peak, peak_capture, pre, moment, bins, captures);
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

@@ -26,6 +26,9 @@
 //   engine_intensity.hip.h  time-binned sound intensity of a box accumulated on the device (wv_set_intensity): plan, stage, fold, fetch
 //   intensity_plan.h     (host only, no HIP) what an intensity plan is refused for, sizes, the fold's traffic model
 //   intensity_kernels.hip.h   its capture (pressure and gradient differences of every taken node) and its fold
+//   engine_arrival.hip.h  energy of a box binned from each node's OWN arrival, onset and peak per node (wv_set_arrival): plan, stage, fold, fetch
+//   arrival_plan.h       (host only, no HIP) edge tables, the bin of a capture behind an onset, sizes and places, the fold's traffic model
+//   arrival_kernels.hip.h     its fold: decay_fold_kernel's scheme with a bin that differs from lane to lane
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -36,6 +39,7 @@
 #include "spectrum_plan.h"
 #include "decay_plan.h"
 #include "intensity_plan.h"
+#include "arrival_plan.h"
 #include "capture_stage.h"
 
 #include "boundary_kernels.hip.h"
@@ -47,6 +51,7 @@
 #include "decay_kernels.hip.h"
 #include "decay_bands_kernels.hip.h"
 #include "intensity_kernels.hip.h"
+#include "arrival_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -203,6 +208,11 @@ public:
     int fetch_intensity(double* dst, uint64_t* captures) override;
     int fetch_intensity_velocity(double* dst) override;
     bool intensity_active() const override { return inten_.active; }
+    // ---- engine_arrival.hip.h
+    int set_arrival(const wv_arrival_plan* plan, const float* threshold_map) override;
+    int arrival_count(uint64_t* captures, uint64_t* last_step) override;
+    int fetch_arrival(uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) override;
+    bool arrival_active() const override { return arr_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -436,6 +446,9 @@ private:
         double* inten_velocity = nullptr;
         size_t inten_bytes = 0, inten_velocity_bytes = 0;
         uint64_t inten_generation = 0, inten_captures = 0, inten_last_step = 0, inten_next = 0;
+        unsigned char* arr_state = nullptr;  // the arrival plan's per-node state, one block (engine_arrival.hip.h), likewise
+        size_t arr_bytes = 0;
+        uint64_t arr_generation = 0, arr_captures = 0, arr_last_step = 0, arr_next = 0;
     } ckpt_;
     // field snapshots (engine_snapshot.hip.h): a ring of device slots the capture kernel fills on the compute stream, each copied to its
     // page-locked twin on a stream of its own, and the log of the snapshots the host holds
@@ -577,16 +590,45 @@ private:
     int intensity_begin_run();
     int intensity_checkpoint();
     int intensity_rollback();
+    // arrival-aligned energy maps (engine_arrival.hip.h): the device-only stage the capture kernel fills on the compute stream, and ONE
+    // block of per-node state the fold kernel carries (arrival_plan.h has the places): pre, moment, bins, onset, peak, peak_capture.
+    // The edge table and the number of the first staged capture go to the kernel as arguments: there is no table to copy
+    struct Arrival {
+        bool active = false, gather_wide = false;
+        wv_arrival_plan plan{};
+        wv::SnapshotBox box;
+        uint64_t generation = 0;        // bumped by every wv_set_arrival (a checkpoint remembers which plan it saw)
+        wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
+        uint64_t nodes = 0;             // B: nodes taken
+        float* stage = nullptr;         // [T][B]
+        unsigned char* state = nullptr; // double pre[B], moment[B], bins[n_bins][B]; uint32 onset[B]; float peak[B]; uint32 peak_capture[B]
+        size_t state_bytes = 0;
+        float* threshold_map = nullptr; // [B], or NULL: the plan's scalar for every node
+        hipEvent_t begun[2] = {nullptr, nullptr};      // around a fold, in turn (kernel timing)
+        hipEvent_t folded_ev[2] = {nullptr, nullptr};
+        bool timed[2] = {false, false};
+        int pair = 0;                   // the event pair the next fold records
+        uint64_t folds = 0;             // WV_QUERY_ARRIVAL_FOLDS
+        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
+    } arr_;
+    static void arrival_release(Arrival& d);
+    int arrival_capture(uint64_t step);
+    int arrival_drain_timing(int pair = -1);
+    int arrival_fold();
+    int arrival_plan_batch();
+    int arrival_begin_run();
+    int arrival_checkpoint();
+    int arrival_rollback();
     // whichever plan is active decides where passes end (engine_batch.hip.h): they all exclude each other
-    bool capture_plan_active() const { return snap_.active || spec_.active || decay_.active || inten_.active; }
+    bool capture_plan_active() const { return snap_.active || spec_.active || decay_.active || inten_.active || arr_.active; }
     uint64_t capture_next() const {
-        return snap_.active ? snap_.next : spec_.active ? spec_.st.next : decay_.active ? decay_.st.next : inten_.active ? inten_.st.next : wv::kNoSnapshotStep;
+        return snap_.active ? snap_.next : spec_.active ? spec_.st.next : decay_.active ? decay_.st.next : inten_.active ? inten_.st.next : arr_.active ? arr_.st.next : wv::kNoSnapshotStep;
     }
     uint64_t capture_batch_end() const {
-        return snap_.active ? snap_.batch_end : spec_.active ? spec_.st.batch_end : decay_.active ? decay_.st.batch_end : inten_.active ? inten_.st.batch_end : wv::kNoSnapshotStep;
+        return snap_.active ? snap_.batch_end : spec_.active ? spec_.st.batch_end : decay_.active ? decay_.st.batch_end : inten_.active ? inten_.st.batch_end : arr_.active ? arr_.st.batch_end : wv::kNoSnapshotStep;
     }
     int capture_step(uint64_t step) {
-        return snap_.active ? snapshot_capture(step) : spec_.active ? spectrum_capture(step) : decay_.active ? decay_capture(step) : intensity_capture(step);
+        return snap_.active ? snapshot_capture(step) : spec_.active ? spectrum_capture(step) : decay_.active ? decay_capture(step) : inten_.active ? intensity_capture(step) : arrival_capture(step);
     }
 };
 

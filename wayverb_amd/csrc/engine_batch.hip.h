@@ -263,6 +263,9 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
     } else if (inten_.active) {  // (engine_intensity.hip.h)
         const int rc = intensity_begin_run();
         if (rc) return rc;
+    } else if (arr_.active) {  // (engine_arrival.hip.h)
+        const int rc = arrival_begin_run();
+        if (rc) return rc;
     }
     while (completed < n_steps && flag == 0) {
         // where this batch ends: it may hold captures for half the snapshot ring
@@ -277,6 +280,9 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
             if (rc) return rc;
         } else if (inten_.active) {  // ... and the intensity plan's
             const int rc = intensity_plan_batch();
+            if (rc) return rc;
+        } else if (arr_.active) {  // ... and the arrival plan's
+            const int rc = arrival_plan_batch();
             if (rc) return rc;
         }
         uint64_t batch = plan_batch(n_steps - completed);
@@ -393,6 +399,7 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
         if (snap_.active && good < batch) snapshot_discard_after(steps_done);  // (a flag stopped the run before those steps)
         if (decay_.active) decay_.st.commit(steps_done);
         if (inten_.active) inten_.st.commit(steps_done);
+        if (arr_.active) arr_.st.commit(steps_done);
         if (spec_.active) spec_.st.commit(steps_done);  // the batch's captures of completed steps stay staged, the others are dropped
         completed += good;
     }
@@ -508,6 +515,15 @@ int Engine<Real>::query(int what, uint64_t* value) {
             if (rc) return rc;
             *value = what == WV_QUERY_INTENSITY_GATHERS ? inten_.gathers_timed
                                                         : (uint64_t)((what == WV_QUERY_INTENSITY_NS ? inten_.kernel_ms : inten_.gather_ms) * 1e6 + 0.5);
+            return WV_OK;
+        }
+        case WV_QUERY_ARRIVAL_CAPTURES: *value = arr_.st.captures(); return WV_OK;
+        case WV_QUERY_ARRIVAL_FOLDS: *value = arr_.folds; return WV_OK;
+        case WV_QUERY_ARRIVAL_NS: {
+            DeviceGuard guard(device_);
+            const int rc = arrival_drain_timing();
+            if (rc) return rc;
+            *value = (uint64_t)(arr_.kernel_ms * 1e6 + 0.5);
             return WV_OK;
         }
         default: return fail(WV_E_INVALID_ARGUMENT, "unknown query");

@@ -73,6 +73,7 @@ int Engine<Real>::decay_set(const wv_decay_plan* plan, const wv_biquad* sections
     if (snap_.active) return fail(WV_E_STATE, who + ": a snapshot plan is active (wv_set_snapshots(e, NULL) stops it); the plans exclude each other");
     if (spec_.active) return fail(WV_E_STATE, who + ": a spectrum plan is active (wv_set_spectrum(e, NULL, NULL) stops it); the plans exclude each other");
     if (inten_.active) return fail(WV_E_STATE, who + ": an intensity plan is active (wv_set_intensity(e, NULL) stops it); the plans exclude each other");
+    if (arr_.active) return fail(WV_E_STATE, who + ": an arrival plan is active (wv_set_arrival(e, NULL, NULL) stops it); the plans exclude each other");
     // the two kinds of decay plan answer to different fetches: neither setter turns one into the other behind the caller's back
     if (decay_.active && banded && !decay_.n_bands)
         return fail(WV_E_STATE, "wv_set_decay_bands: a plain decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");

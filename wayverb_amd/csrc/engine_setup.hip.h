@@ -547,6 +547,8 @@ void Engine<Real>::release() {
     if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
     decay_release(decay_);
     intensity_release(inten_);
+    arrival_release(arr_);
+    if (ckpt_.arr_state) (void)hipFree(ckpt_.arr_state);
     if (ckpt_.inten_bins) (void)hipFree(ckpt_.inten_bins);
     if (ckpt_.inten_velocity) (void)hipFree(ckpt_.inten_velocity);
     if (ckpt_.decay_bins) (void)hipFree(ckpt_.decay_bins);

@@ -41,6 +41,7 @@ EXPORTS = [
     "wv_set_decay", "wv_decay_count", "wv_fetch_decay",
     "wv_set_decay_bands", "wv_fetch_decay_bands", "wv_biquad_run", "wv_butterworth_bandpass", "wv_bandpass_biquad",
     "wv_set_intensity", "wv_intensity_count", "wv_fetch_intensity", "wv_fetch_intensity_velocity", "wv_fetch_directional_velocity",
+    "wv_set_arrival", "wv_arrival_count", "wv_fetch_arrival",
 ]
 
 
@@ -96,6 +97,15 @@ class WvIntensityPlan(C.Structure):
     """wv_intensity_plan (include/wayverb_amd.h): wv_decay_plan's fields, then the three arguments of the reference's
     directional_receiver constructor."""
     _fields_ = WvDecayPlan._fields_ + [("spacing", C.c_double), ("sample_rate", C.c_double), ("ambient_density", C.c_double)]
+
+
+class WvArrivalPlan(C.Structure):
+    """wv_arrival_plan (include/wayverb_amd.h): the box and the cadence as wv_decay_plan has them, then n_bins, the scalar threshold
+    and the 16 bin edges in captures behind a node's onset."""
+    _fields_ = WvDecayPlan._fields_[:11] + [("n_bins", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 16)]
+
+
+ARRIVAL_NONE = 0xFFFFFFFF   # onset / peak_capture of a node that has none yet
 
 
 # Tuning applied to every engine this module creates unless the call says otherwise: {field of wv_tuning: value}, plus
@@ -215,6 +225,9 @@ def load_library():
     lib.wv_fetch_intensity.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.wv_fetch_intensity_velocity.argtypes = [C.c_void_p, C.c_void_p]
     lib.wv_fetch_directional_velocity.argtypes = [C.c_void_p, C.c_void_p]
+    lib.wv_set_arrival.argtypes = [C.c_void_p, C.POINTER(WvArrivalPlan), C.c_void_p]
+    lib.wv_arrival_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.wv_fetch_arrival.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.POINTER(C.c_uint64)]
     lib.wv_biquad_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.wv_butterworth_bandpass.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.wv_bandpass_biquad.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
@@ -404,6 +417,7 @@ class Engine:
         self.decay_shape = None
         self.decay_banded = False
         self.intensity_shape = None
+        self.arrival_shape = None
 
     @classmethod
     def from_handle(cls, handle, mesh, precision):
@@ -421,6 +435,7 @@ class Engine:
         eng.decay_shape = None
         eng.decay_banded = False
         eng.intensity_shape = None
+        eng.arrival_shape = None
         return eng
 
     def close(self):
@@ -741,6 +756,51 @@ class Engine:
         _check(self.lib.wv_fetch_directional_velocity(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # ---- arrival-aligned energy maps accumulated on the device while wv_run goes on ------------------
+    def set_arrival(self, edges, threshold=0.0, box="mesh", stride=1, first_step=0, period=1, threshold_map=None):
+        """wv_set_arrival.  `box`, `stride`, `first_step`, `period` as for set_snapshots.  `edges`: 1 .. 16 integers, edges[0] == 0,
+        strictly increasing: the first capture of bin k counted from the node's OWN onset, the first capture at which |p| >=
+        `threshold` (or the node's entry of `threshold_map`, float32 [nz, ny, nx]).  Per node the engine keeps onset, peak,
+        peak_capture, the energy ahead of the onset, the bins and the first time moment; arrival.arrival_fold over the snapshots
+        reproduces all of it bit for bit.  Excludes every other plan.  set_arrival(None) stops and forgets.  Returns the shape of the
+        bins, (n_bins, nz, ny, nx)."""
+        if edges is None:
+            _check(self.lib.wv_set_arrival(self.h, None, None))
+            self.arrival_shape = None
+            return None
+        edges = [int(v) for v in edges]
+        if len(edges) > 16:
+            raise ValueError("set_arrival: 16 bins at the most")
+        plan = WvArrivalPlan()
+        taken = self._fill_box(plan, box, stride)
+        plan.first_step, plan.period, plan.n_bins, plan.threshold = int(first_step), int(period), len(edges), float(threshold)
+        for k, v in enumerate(edges):
+            plan.edges[k] = v
+        if threshold_map is not None:
+            threshold_map = np.ascontiguousarray(threshold_map, dtype=np.float32)
+            if threshold_map.shape != (taken[2], taken[1], taken[0]):
+                raise ValueError("set_arrival: the threshold map must have the box's shape %r" % ((taken[2], taken[1], taken[0]),))
+        _check(self.lib.wv_set_arrival(self.h, C.byref(plan), threshold_map.ctypes.data_as(C.c_void_p) if threshold_map is not None else None))
+        self.arrival_shape = (len(edges), taken[2], taken[1], taken[0])
+        return self.arrival_shape
+
+    def arrival_count(self):
+        """wv_arrival_count: (captures of completed steps since the plan was set, the step of the last of them)."""
+        captures, last = C.c_uint64(), C.c_uint64()
+        _check(self.lib.wv_arrival_count(self.h, C.byref(captures), C.byref(last)))
+        return captures.value, last.value
+
+    def fetch_arrival(self):
+        """wv_fetch_arrival: (dict(onset=uint32[nz, ny, nx], peak=float32, peak_capture=uint32, pre=float64, moment=float64,
+        bins=float64[n_bins, nz, ny, nx]), captures in them).  ARRIVAL_NONE marks a node without an onset.  The plan keeps running."""
+        shape = tuple(getattr(self, "arrival_shape", None) or (0, 0, 0, 0))   # (no plan: the library says so)
+        out = dict(onset=np.zeros(shape[1:], np.uint32), peak=np.zeros(shape[1:], np.float32), peak_capture=np.zeros(shape[1:], np.uint32),
+                   pre=np.zeros(shape[1:], np.float64), moment=np.zeros(shape[1:], np.float64), bins=np.zeros(shape, np.float64))
+        captures = C.c_uint64()
+        _check(self.lib.wv_fetch_arrival(self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in ("onset", "peak", "peak_capture", "pre", "moment", "bins")],
+                                         C.byref(captures)))
+        return out, captures.value
+
     def step_count(self):
         s = C.c_uint64()
         _check(self.lib.wv_step_count(self.h, C.byref(s)))
@@ -774,6 +834,7 @@ class Engine:
     QUERY_SPECTRUM_CAPTURES, QUERY_SPECTRUM_FOLDS, QUERY_SPECTRUM_NS = 26, 27, 28
     QUERY_DECAY_CAPTURES, QUERY_DECAY_FOLDS, QUERY_DECAY_NS = 29, 30, 31
     QUERY_INTENSITY_CAPTURES, QUERY_INTENSITY_FOLDS, QUERY_INTENSITY_NS, QUERY_INTENSITY_GATHER_NS, QUERY_INTENSITY_GATHERS = 32, 33, 34, 35, 36
+    QUERY_ARRIVAL_CAPTURES, QUERY_ARRIVAL_FOLDS, QUERY_ARRIVAL_NS = 37, 38, 39
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

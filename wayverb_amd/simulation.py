@@ -136,8 +136,33 @@ def intensity_plan_arguments(intensity, mesh, sample_rate, environment, simulati
                 period=every, spacing=mesh.spacing, sample_rate=sample_rate / every, ambient_density=environment.ambient_density)
 
 
+def arrival_plan_arguments(arrival, mesh, sample_rate):
+    """canonical's `arrival` dict -> keyword arguments of Engine.set_arrival: dict(plane=z in metres | box=((x0, y0, z0), extent),
+    stride=1, every=1, threshold=, threshold_map=None, early_ms=(50, 80), first_step=0).  `plane`: that whole horizontal plane.  The
+    bins begin at each node's onset and at every one of `early_ms` milliseconds behind it (arrival.edges_from_ms at the rate of the
+    captured series, sample_rate / every); `threshold` is the pressure magnitude that counts as the arrival of the direct sound."""
+    from . import arrival as A
+    unknown = set(arrival) - {"plane", "box", "stride", "every", "threshold", "threshold_map", "early_ms", "first_step"}
+    if unknown or ("plane" in arrival) == ("box" in arrival) or "threshold" not in arrival:
+        raise ValueError("arrival=dict(plane=<z in metres> or box=..., threshold=, every=, early_ms=, threshold_map=, stride=, first_step=)")
+    every = int(arrival.get("every", 1))
+    if every < 1:
+        raise ValueError("arrival: every must be >= 1")
+    if "plane" in arrival:
+        plane = int(round((float(arrival["plane"]) - mesh.min_corner[2]) / mesh.spacing))
+        if not 0 <= plane <= mesh.dims[2] - 1:
+            raise ValueError("arrival: plane z=%g m is outside the mesh" % float(arrival["plane"]))
+        box = ((0, 0, plane), (None, None, 1))
+    else:
+        box = arrival["box"]
+    return dict(edges=A.edges_from_ms(arrival.get("early_ms", (50.0, 80.0)), every, sample_rate), threshold=float(arrival["threshold"]),
+                threshold_map=arrival.get("threshold_map"), box=box, stride=arrival.get("stride", 1),
+                first_step=int(arrival.get("first_step", 0)), period=every)
+
+
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
-              device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None, decay=None, intensity=None):
+              device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None, decay=None, intensity=None,
+              arrival=None):
     """canonical (single band): hard source at `source`, directional receiver at `receiver`, for
     ceil(sample_rate * simulation_time) steps.  Returns [(directional records, sample_rate,
     (0, cutoff))] -- the bandpass_band list waveguide::postprocess takes -- or None when stopped early.
@@ -164,7 +189,14 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     directional receiver's integrator at every node of that plane or box and sums the sound intensity and the squared pressure into
     time bins on the device (Engine.set_intensity; spacing, sample_rate / every and the environment's density are filled in); the
     return value is then (bands, (float64[4, n_bins, nz, ny, nx], captures)), which wayverb_amd.intensity turns into direction and
-    diffuseness maps.  One domain only, and not together with another plan."""
+    diffuseness maps.  One domain only, and not together with another plan.
+    `arrival`: dict(plane=<z in metres> or box=..., every=, threshold=, early_ms=(50, 80)) (arrival_plan_arguments) -- the engine keeps,
+    per node of that plane or box and on the device, the capture at which the direct sound arrived, the peak, and the squared pressure
+    in bins counted from the node's OWN arrival (Engine.set_arrival); the return value is then (bands, (dict(onset, peak, peak_capture,
+    pre, moment, bins), captures)), which wayverb_amd.arrival turns into arrival time, C50 / C80, D50 and centre time.  One domain
+    only, and not together with another plan."""
+    if arrival is not None and slabs > 1:
+        raise ValueError("arrival maps are accumulated on one domain only (slabs=1)")
     if intensity is not None and slabs > 1:
         raise ValueError("intensity bins are accumulated on one domain only (slabs=1)")
     if decay is not None and slabs > 1:
@@ -183,6 +215,7 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
         series_rate = sample_rate / int(decay.get("period", 1))
         decay = dict(decay, bands=np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in decay["bands"]]))
     intensity_plan = intensity_plan_arguments(intensity, mesh, sample_rate, environment, simulation_time) if intensity is not None else None
+    arrival_plan = arrival_plan_arguments(arrival, mesh, sample_rate) if arrival is not None else None
 
     def mesh_index(pt):
         idx = vm.compute_index(pt)
@@ -213,6 +246,8 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 eng.set_decay(**decay)
             if intensity_plan is not None:
                 eng.set_intensity(**intensity_plan)
+            if arrival_plan is not None:
+                eng.set_arrival(**arrival_plan)
             done, traces = E.run_fast(eng, E.SOURCE_HARD, mesh_index(source), signal, [receiver_index] + list(neighbours),
                                       keep_going=keep_going)
             taken = eng.fetch_snapshots() if snapshots is not None else None
@@ -222,13 +257,15 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 taken = eng.fetch_decay()
             if intensity_plan is not None:
                 taken = eng.fetch_intensity()
+            if arrival_plan is not None:
+                taken = eng.fetch_arrival()
         finally:
             eng.close()
     if done != ideal_steps:
         return None
     directional = P.directional_receiver(traces, mesh.spacing, sample_rate, environment.ambient_density)
     bands = [(directional, sample_rate, (0.0, float(cutoff)))]
-    return bands if snapshots is None and spectrum is None and decay is None and intensity is None else (bands, taken)
+    return bands if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None else (bands, taken)
 
 
 def spectrum_plan_arguments(spectrum, sample_rate):
@@ -349,19 +386,20 @@ def canonical_multiband(vm, source, receiver, environment, bands, cutoff, usable
 def impulse_response(vertices, triangles, surface_absorptions, source, receiver, cutoff=200.0, usable_portion=0.6,
                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
                      pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None, decay=None,
-                     intensity=None):
+                     intensity=None, arrival=None):
     """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio.
     `snapshots`: a function mesh -> keyword arguments of Engine.set_snapshots (the mesh's size is not known before it is built),
     or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member.
     `spectrum`: a function mesh -> canonical's `spectrum` dict, or the dict; the fourth member is then (spectrum, captures).
     `decay`: a function (mesh, sample_rate) -> canonical's `decay` dict, or the dict; the fourth member is then (bins, captures).
-    `intensity`: canonical's `intensity` dict; the fourth member is then (bins [4, n_bins, nz, ny, nx], captures)."""
+    `intensity`: canonical's `intensity` dict; the fourth member is then (bins [4, n_bins, nz, ny, nx], captures).
+    `arrival`: canonical's `arrival` dict; the fourth member is then (dict(onset, peak, peak_capture, pre, moment, bins), captures)."""
     environment = environment or Environment()
     vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
     if spectrum is not None and snapshots is not None:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
-    if snapshots is None and spectrum is None and decay is None and intensity is None:
+    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None:
         bands = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device)
         taken = None
     else:
@@ -374,6 +412,8 @@ def impulse_response(vertices, triangles, surface_absorptions, source, receiver,
             plans["decay"] = decay(vm.mesh, rate) if callable(decay) else decay
         if intensity is not None:
             plans["intensity"] = intensity
+        if arrival is not None:
+            plans["arrival"] = arrival
         both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, **plans)
         if both is None:
             raise RuntimeError("the waveguide run was stopped early")
