@@ -126,10 +126,12 @@ static uint32_t count_crossings(const scene_t* s, v3 pos, v3 dir) {
     return count;
 }
 
-/* inside[i] = 1 when node i lies inside the triangle soup, else 0 */
-void wvo_nodes_inside(int nx, int ny, int nz, const float* min_corner, float spacing, const uint32_t* voxel_index,
-                      const float* aabb_min, const float* aabb_max, uint32_t side, const uint32_t* triangles,
-                      const float* vertices, uint8_t* inside) {
+/* The loop of set_node_inside / voxel_inside.  inside[i] = 1 when node i lies inside the triangle
+ * soup, else 0; ray[i] (optional) = index of the direction that decided node i, 32 when every
+ * direction was unsure (-> outside). */
+static void nodes_inside_loop(int nx, int ny, int nz, const float* min_corner, float spacing, const uint32_t* voxel_index,
+                              const float* aabb_min, const float* aabb_max, uint32_t side, const uint32_t* triangles,
+                              const float* vertices, uint8_t* inside, uint8_t* ray) {
     scene_t s;
     s.voxel_index = voxel_index;
     for (int k = 0; k < 3; ++k) {
@@ -148,7 +150,8 @@ void wvo_nodes_inside(int nx, int ny, int nz, const float* min_corner, float spa
         const v3 pos = {min_corner[0] + (float)x * spacing, min_corner[1] + (float)y * spacing,
                         min_corner[2] + (float)z * spacing};
         uint8_t result = 0;
-        for (int k = 0; k < 32; ++k) {
+        int k = 0;
+        for (; k < 32; ++k) {
             const uint32_t c = count_crossings(&s, pos, (v3){k_directions[k][0], k_directions[k][1], k_directions[k][2]});
             if (c != ~(uint32_t)0) {
                 result = (uint8_t)(c % 2);
@@ -156,5 +159,27 @@ void wvo_nodes_inside(int nx, int ny, int nz, const float* min_corner, float spa
             }
         }
         inside[i] = result;
+        if (ray) ray[i] = (uint8_t)k;
     }
+}
+
+void wvo_nodes_inside(int nx, int ny, int nz, const float* min_corner, float spacing, const uint32_t* voxel_index,
+                      const float* aabb_min, const float* aabb_max, uint32_t side, const uint32_t* triangles,
+                      const float* vertices, uint8_t* inside) {
+    nodes_inside_loop(nx, ny, nz, min_corner, spacing, voxel_index, aabb_min, aabb_max, side, triangles, vertices, inside,
+                      NULL);
+}
+
+/* Diagnostic for the tests' coverage tally: the same loop, also reporting which direction decided. */
+void wvo_nodes_inside_rays(int nx, int ny, int nz, const float* min_corner, float spacing, const uint32_t* voxel_index,
+                           const float* aabb_min, const float* aabb_max, uint32_t side, const uint32_t* triangles,
+                           const float* vertices, uint8_t* inside, uint8_t* ray) {
+    nodes_inside_loop(nx, ny, nz, min_corner, spacing, voxel_index, aabb_min, aabb_max, side, triangles, vertices, inside,
+                      ray);
+}
+
+/* the 32 directions, as the floats the loop uses: out[32][3] */
+void wvo_ray_directions(float* out) {
+    for (int k = 0; k < 32; ++k)
+        for (int e = 0; e < 3; ++e) out[3 * k + e] = k_directions[k][e];
 }

@@ -65,19 +65,33 @@ class Oracle:
         self.lib.wvo_set_boundary_indices(_ptr(nodes), nodes.shape[0], counts)
         return nodes, tuple(int(c) for c in counts)
 
-    def nodes_inside(self, dims, min_corner, spacing, voxel_index, aabb, side, triangles, vertices):
-        """`set_node_inside` restated: uint8 mask [nz, ny, nx]."""
+    def nodes_inside(self, dims, min_corner, spacing, voxel_index, aabb, side, triangles, vertices, rays=False):
+        """`set_node_inside` restated: uint8 mask [nz, ny, nx].  With rays=True also, per node, the index of the
+        direction that decided it (32: every direction was unsure, the node counts as outside): (mask, ray)."""
         nx, ny, nz = dims
         out = np.zeros(nx * ny * nz, dtype=np.uint8)
+        ray = np.zeros(nx * ny * nz, dtype=np.uint8) if rays else None
         mc = np.ascontiguousarray(min_corner, dtype=np.float32)
         a0 = np.ascontiguousarray(aabb[0], dtype=np.float32)
         a1 = np.ascontiguousarray(aabb[1], dtype=np.float32)
-        self.lib.wvo_nodes_inside.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.lib.wvo_nodes_inside.restype = None
-        self.lib.wvo_nodes_inside(nx, ny, nz, _ptr(mc), float(spacing), _ptr(voxel_index), _ptr(a0), _ptr(a1), side,
-                                  _ptr(triangles), _ptr(vertices), _ptr(out))
+        args = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                C.c_void_p, C.c_void_p]
+        f = self.lib.wvo_nodes_inside_rays if rays else self.lib.wvo_nodes_inside
+        f.argtypes = args + [C.c_void_p] if rays else args
+        f.restype = None
+        f(nx, ny, nz, _ptr(mc), float(spacing), _ptr(voxel_index), _ptr(a0), _ptr(a1), side, _ptr(triangles), _ptr(vertices),
+          _ptr(out), *([_ptr(ray)] if rays else []))
+        if rays:
+            return out.reshape(nz, ny, nx), ray.reshape(nz, ny, nx)
         return out.reshape(nz, ny, nx)
+
+    def ray_directions(self):
+        """The 32 fixed ray directions of `voxel_inside`, float32 [32, 3], as the restatement holds them."""
+        out = np.zeros((32, 3), dtype=np.float32)
+        self.lib.wvo_ray_directions.argtypes = [C.c_void_p]
+        self.lib.wvo_ray_directions.restype = None
+        self.lib.wvo_ray_directions(_ptr(out))
+        return out
 
     def point_triangle_dist2(self, v0, v1, v2, p):
         f = self.lib.wvo_point_triangle_dist2
