@@ -528,8 +528,8 @@ int wv_bandpass_biquad(double lo_hz, double hi_hz, double sample_rate, wv_biquad
  *     engine and any earlier plan untouched.  A new plan replaces the old one and forgets its sums; a NULL plan stops, forgets and
  *     frees (as does wv_destroy)
  *   - one domain only: a slab of a chain answers WV_E_STATE, and wv_run_group refuses an engine with a plan
- *   - an intensity plan excludes the snapshot plan, the spectrum plan and both kinds of decay plan: every setter answers WV_E_STATE
- *     while another plan is active, and wv_last_error names the plan to stop
+ *   - an intensity plan excludes every other plan (snapshot, spectrum, both kinds of decay, arrival, lateral): every setter answers
+ *     WV_E_STATE while another plan is active, and wv_last_error names the plan to stop
  *   - after a run that stopped on a flag at step f, bins AND velocities have seen exactly the captures of steps <= f: a continued
  *     run goes on as if the dropped captures had never been taken
  *   - wv_step / wv_swap capture nothing; the plan steps they pass are gaps in the series the integrator sees
@@ -599,8 +599,8 @@ int wv_fetch_directional_velocity(wv_engine* e, double* dst /* [n][3] */);
  *     any earlier plan untouched.  The map is copied: the caller's array is free when the call returns.  A new plan replaces the old
  *     one and forgets its state; a NULL plan stops, forgets and frees (as does wv_destroy)
  *   - one domain only: a slab of a chain answers WV_E_STATE, and wv_run_group refuses an engine with a plan
- *   - an arrival plan excludes the snapshot plan, the spectrum plan, both kinds of decay plan and the intensity plan: every setter
- *     answers WV_E_STATE while another plan is active, and wv_last_error names the plan to stop
+ *   - an arrival plan excludes the snapshot plan, the spectrum plan, both kinds of decay plan, the intensity plan and the lateral
+ *     plan: every setter answers WV_E_STATE while another plan is active, and wv_last_error names the plan to stop
  *   - after a run that stopped on a flag at step f the state has seen exactly the captures of steps <= f: no onset, peak or sum of a
  *     step that was never committed
  *   - wv_step / wv_swap capture nothing; the plan steps they pass are gaps in the series, and `rel` counts captures, not steps
@@ -629,6 +629,87 @@ int wv_set_arrival(wv_engine* e, const wv_arrival_plan* plan, const float* thres
 int wv_arrival_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
 int wv_fetch_arrival(wv_engine* e, uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment,
                      double* bins /* [n_bins][nz][ny][nx] */, uint64_t* captures);
+
+/* ---- lateral maps: velocity moments binned from each node's own onset -------------------------- */
+/* The early lateral energy fraction LF (J_LF, ISO 3382-1) is the energy a figure-of-eight microphone hears between 5 and 80 ms
+ * behind the direct sound over what an omnidirectional one hears in 0 .. 80 ms, AT THAT SEAT.  A figure-of-eight's signal is a
+ * component of the particle velocity, so its energy is quadratic in v: an intensity plan, which keeps p v, cannot give it, and bins
+ * by one global clock; an arrival plan has each node's own clock and sees pressure only.  A lateral plan has the engine capture a
+ * box exactly as an intensity plan captures it, run the reference's directional_receiver integrator at every node taken and keep,
+ * per node and on the device, in bins counted from the node's OWN onset: the squared pressure E, the intensity I = p v, and the
+ * symmetric second-moment tensor Q = v v^T.  With the tensor the lateral axis d is chosen AFTER the run and per seat (d^T Q d is
+ * the figure-of-eight's energy along d, up to (rho c)^2), facing wherever the first bin's intensity says the direct sound came
+ * from; its trace is the kinetic half of the energy density.  36 + 80 n_bins bytes per node cross the link when the caller asks,
+ * however long the run; wayverb_amd/lateral.py turns them into LF, the direct direction and the diffuseness.
+ *
+ * wv_lateral_plan holds wv_intensity_plan's box, strides, first_step, period, spacing, sample_rate and ambient_density with the same
+ * meaning, and wv_arrival_plan's n_bins, threshold and edges with the same meaning (8 bins at the most).
+ *
+ * Definition.  pressure, gx, gy, gz are the four floats of the intensity block's first three lines above for the node (the same
+ * casts, the same association); c = 0, 1, ... counts the committed captures since the plan was set.  thr is the node's threshold:
+ * the plan's scalar, or the node's entry of threshold_map, as wv_set_arrival has it.  The state starts as onset = NONE (0xFFFFFFFF),
+ * pre = v[i] = +0.0 and every bin +0.0, and per capture, in capture order:
+ *     a = fabsf(pressure)
+ *     if (onset == NONE && a >= thr)  onset = c;                  the onset capture itself falls into bin 0; a NaN is no onset
+ *     m = (double)g[i] * 0.5;  v[i] = v[i] - m / k;               i = x, y, z; k = ambient_density * sample_rate, an IEEE division;
+ *                                                                 EVERY capture, before the onset too
+ *     p = (double)pressure
+ *     if (onset == NONE)  pre = pre + p * p;
+ *     else { rel = c - onset;  b = the largest b with edges[b] <= rel;
+ *            E[b]   = E[b]   + p * p;
+ *            Ii[b]  = Ii[b]  + v[i] * p;                          the product is rounded, then the sum
+ *            Qij[b] = Qij[b] + v[i] * v[j]; }                     (i, j) = xx, yy, zz, xy, xz, yz, in that order
+ * edges[0] = 0 < edges[1] < ... < edges[n_bins - 1] are in captures behind the onset; the last bin is open-ended.  Nothing is
+ * contracted.  A NumPy loop over snapshots of the box's hull that evaluates these lines (wayverb_amd/lateral.py: lateral_fold; the
+ * float lines on float32 arrays, the rest on float64) reproduces onset, pre, v and all ten bin planes BIT FOR BIT.  A threshold of 0
+ * is legal: every onset is then capture 0, and with edges[b] = b W the planes E and I and the velocities are, bit for bit, an
+ * intensity plan's of the same box, cadence and bin_captures = W; with any threshold onset, pre and E are an arrival plan's.
+ *
+ *   - 1 <= n_bins <= 8, edges as above, the threshold (and every entry of the map) >= 0 and finite, strides and period >= 1, and
+ *     spacing, sample_rate, ambient_density positive and finite; otherwise, and for a box that leaves the mesh: WV_E_INVALID_ARGUMENT
+ *   - a taken node with a neighbour off the grid answers WV_E_INVALID_ARGUMENT with the reference's sentence ("Can't place
+ *     directional_receiver at this node as it is adjacent to a boundary."), as wv_set_intensity does: no taken node lies on a face of
+ *     the mesh.  Neighbours inside a wall are read as the field holds them
+ *   - everything (the stage of 16 captures, 256 bytes per node; the state, 36 + 80 n_bins bytes per node; the map's copy, 4 bytes
+ *     per node where one is given) is allocated when the plan is set: with no room the call answers WV_E_HIP and leaves the engine
+ *     and any earlier plan untouched.  The map is copied: the caller's array is free when the call returns.  A new plan replaces the
+ *     old one and forgets its state; a NULL plan stops, forgets and frees (as does wv_destroy)
+ *   - one domain only: a slab of a chain answers WV_E_STATE, and wv_run_group refuses an engine with a plan
+ *   - a lateral plan excludes the snapshot plan, the spectrum plan, both kinds of decay plan, the intensity plan and the arrival
+ *     plan: every setter answers WV_E_STATE while another plan is active, and wv_last_error names the plan to stop
+ *   - after a run that stopped on a flag at step f the state has seen exactly the captures of steps <= f: no onset, velocity or sum
+ *     of a step that was never committed
+ *   - wv_step / wv_swap capture nothing; the plan steps they pass are gaps in the series, and `rel` counts captures, not steps
+ *   - captures are numbered with 32 bits: wv_run answers WV_E_STATE rather than take capture 2^32 - 1
+ *   - wv_checkpoint folds what is staged and copies all per-node state, the capture count and the next plan step aside (the copy is
+ *     allocated by the first checkpoint taken under a plan: WV_E_HIP, engine untouched, when there is no room); wv_rollback puts
+ *     them back, and the re-run is bitwise the same.  A plan set AFTER the checkpoint makes wv_rollback answer WV_E_STATE
+ *   - with no plan nothing is launched, allocated or waited for; with one the fields, receiver rows and flags are bit-identical to
+ *     a run without
+ *
+ * What the caller owns: the integrator sees a series sampled at sample_rate / period, as under an intensity plan: pass THAT rate.
+ *
+ * wv_lateral_count: as wv_decay_count.  wv_fetch_lateral: onset and pre are [nz][ny][nx], velocity is float64 [3][nz][ny][nx], bins is
+ * float64 [10][n_bins][nz][ny][nx] = E, Ix, Iy, Iz, Qxx, Qyy, Qzz, Qxy, Qxz, Qyz; ANY destination may be NULL and is then skipped;
+ * *captures (may be NULL) = how many captures they hold.  It may be called any time outside wv_run, folds what is staged and leaves
+ * the plan running. */
+typedef struct wv_lateral_plan {
+    int32_t x0, y0, z0;    /* first node of the box */
+    int32_t nx, ny, nz;    /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;    /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step;   /* captures at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;       /* >= 1 */
+    uint32_t n_bins;       /* 1 .. 8 */
+    float threshold;       /* >= 0, finite; used where threshold_map is NULL */
+    uint32_t edges[8];     /* first relative capture of bin b; edges[0] == 0, strictly increasing over n_bins entries */
+    double spacing;        /* mesh_descriptor::spacing, > 0 */
+    double sample_rate;    /* of the CAPTURED series: the mesh's sample rate / period, > 0 */
+    double ambient_density;/* > 0 */
+} wv_lateral_plan;
+int wv_set_lateral(wv_engine* e, const wv_lateral_plan* plan, const float* threshold_map /* [nz][ny][nx] or NULL; every entry >= 0, finite */);
+int wv_lateral_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
+int wv_fetch_lateral(wv_engine* e, uint32_t* onset, double* pre, double* velocity /* [3][nz][ny][nx] */,
+                     double* bins /* [10][n_bins][nz][ny][nx] */, uint64_t* captures);
 
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
@@ -670,7 +751,9 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *   WV_QUERY_INTENSITY_CAPTURES, WV_QUERY_INTENSITY_FOLDS, WV_QUERY_INTENSITY_NS   the same three since wv_set_intensity
  *   WV_QUERY_INTENSITY_GATHER_NS, WV_QUERY_INTENSITY_GATHERS   total time of the intensity plan's capture kernels that ran with kernel
  *                            timing on, and how many of them that is
- *   WV_QUERY_ARRIVAL_CAPTURES, WV_QUERY_ARRIVAL_FOLDS, WV_QUERY_ARRIVAL_NS   the decay plan's three since wv_set_arrival */
+ *   WV_QUERY_ARRIVAL_CAPTURES, WV_QUERY_ARRIVAL_FOLDS, WV_QUERY_ARRIVAL_NS   the decay plan's three since wv_set_arrival
+ *   WV_QUERY_LATERAL_CAPTURES, WV_QUERY_LATERAL_FOLDS, WV_QUERY_LATERAL_NS, WV_QUERY_LATERAL_GATHER_NS, WV_QUERY_LATERAL_GATHERS
+ *                            the intensity plan's five since wv_set_lateral */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -691,7 +774,9 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
        WV_QUERY_DECAY_CAPTURES = 29, WV_QUERY_DECAY_FOLDS = 30, WV_QUERY_DECAY_NS = 31,
        WV_QUERY_INTENSITY_CAPTURES = 32, WV_QUERY_INTENSITY_FOLDS = 33, WV_QUERY_INTENSITY_NS = 34,
        WV_QUERY_INTENSITY_GATHER_NS = 35, WV_QUERY_INTENSITY_GATHERS = 36,
-       WV_QUERY_ARRIVAL_CAPTURES = 37, WV_QUERY_ARRIVAL_FOLDS = 38, WV_QUERY_ARRIVAL_NS = 39 };
+       WV_QUERY_ARRIVAL_CAPTURES = 37, WV_QUERY_ARRIVAL_FOLDS = 38, WV_QUERY_ARRIVAL_NS = 39,
+       WV_QUERY_LATERAL_CAPTURES = 40, WV_QUERY_LATERAL_FOLDS = 41, WV_QUERY_LATERAL_NS = 42,
+       WV_QUERY_LATERAL_GATHER_NS = 43, WV_QUERY_LATERAL_GATHERS = 44 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

@@ -97,6 +97,18 @@ def main():
     ap.add_argument("--arrival-out", default="arrival.npz",
                     help="the maps go here: onset, peak, peak_capture, pre, moment [ny, nx], bins [3, ny, nx], edges, arrival_s, direct_db, "
                          "c50_db, c80_db, d50, d80, ts_s, pre_fraction, captures, period, sample_rate, plane, origin, spacing")
+    ap.add_argument("--lateral-map", action="store_true",
+                    help="keep, per node of one horizontal plane (less its rim) and on the device, the squared pressure, the sound "
+                         "intensity and the second moments of the particle velocity in bins of 0-5, 5-80 and 80+ ms counted from the "
+                         "node's OWN arrival (Engine.set_lateral; single-band runs, no other plan): the early lateral energy fraction "
+                         "LF along each node's own lateral axis, the direction the direct sound came from and the diffuseness")
+    ap.add_argument("--lateral-plane", default=None, metavar="z=METRES", help="the height of that plane (default: the receiver's)")
+    ap.add_argument("--lateral-threshold", type=float, default=1e-4,
+                    help="the pressure magnitude that counts as the arrival of the direct sound (default 1e-4; the source's impulse is 1)")
+    ap.add_argument("--lateral-every", type=int, default=1, help="capture every N-th step (the integrator then runs at sample rate / N)")
+    ap.add_argument("--lateral-out", default="lateral.npz",
+                    help="the maps go here: lf, diffuseness [ny, nx], direct_direction, lateral_axis [3, ny, nx], onset, pre [ny, nx], "
+                         "velocity [3, ny, nx], bins [10, 3, ny, nx], edges, captures, period, sample_rate, plane, origin, spacing")
     args = ap.parse_args()
 
     bands = None
@@ -218,11 +230,21 @@ def main():
             ap.error("--arrival-every must be >= 1 and --arrival-threshold >= 0 and finite")
         arrival = dict(plane=float(args.arrival_plane[2:]) if args.arrival_plane else args.receiver[2], every=args.arrival_every,
                        threshold=args.arrival_threshold, early_ms=(50.0, 80.0))
+    lateral = None
+    if args.lateral_map:
+        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None:
+            ap.error("--lateral-map: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map or --clarity-map")
+        if args.lateral_plane and not args.lateral_plane.startswith("z="):
+            ap.error("--lateral-plane takes z=<metres>")
+        if args.lateral_every < 1 or not (args.lateral_threshold >= 0 and np.isfinite(args.lateral_threshold)):
+            ap.error("--lateral-every must be >= 1 and --lateral-threshold >= 0 and finite")
+        lateral = dict(plane=float(args.lateral_plane[2:]) if args.lateral_plane else args.receiver[2], every=args.lateral_every,
+                       threshold=args.lateral_threshold, edges_ms=(0.0, 5.0, 80.0))
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
     if len(receivers) > 1:
-        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None:
-            ap.error("several --receiver: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map or --clarity-map")
+        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None or lateral is not None:
+            ap.error("several --receiver: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map, --clarity-map or --lateral-map")
         audios, per, positions, vm = W.impulse_responses(v, t, absorptions, args.source, receivers, args.cutoff, args.usable_portion,
                                                          args.seconds, args.rate, method=method, pointing=args.pointing,
                                                          shape=args.mic_shape or 0.0, precision=args.precision)
@@ -236,8 +258,8 @@ def main():
             peak = write_wav(name, audio, args.rate)
             print("wrote %s: receiver at node position (%.3f, %.3f, %.3f) (normalised, peak was %.3e)" % ((name,) + tuple(pos) + (peak,)))
         return
-    if bands and (intensity is not None or arrival is not None):
-        ap.error("--intensity-map, --clarity-map: single-band runs only")
+    if bands and (intensity is not None or arrival is not None or lateral is not None):
+        ap.error("--intensity-map, --clarity-map, --lateral-map: single-band runs only")
     if bands:   # multiple_band_constant_spacing: one run per band with flat per-band walls
         env = W.Environment()
         vm = W.compute_voxels_and_mesh(v, t, absorptions, args.receiver,
@@ -250,7 +272,28 @@ def main():
                                        args.usable_portion, args.seconds, args.rate, method=method,
                                        pointing=args.pointing, shape=args.mic_shape or 0.0,
                                        precision=args.precision, snapshots=snapshots, spectrum=spectrum, decay=decay, intensity=intensity,
-                                       arrival=arrival)
+                                       arrival=arrival, lateral=lateral)
+        if lateral is not None:
+            from wayverb_amd import lateral as L
+            env, mesh = W.Environment(), audio_etc[2].mesh
+            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
+            plan = W.lateral_plan_arguments(lateral, mesh, rate, env)
+            out, captures = audio_etc[3]
+            out = {k: (v[:, :, 0] if k == "bins" else v[:, 0] if k == "velocity" else v[0]) for k, v in out.items()}   # the one plane
+            came_from = L.direct_direction(out)
+            axis = L.lateral_axis(came_from)
+            # J_LF: the figure-of-eight's energy in 5 - 80 ms over the omni's in 0 - 80 ms, where both edges are bins of the plan
+            lf = L.lateral_fraction(out, axis, 1, (0, 1), env.ambient_density, env.speed_of_sound) if len(plan["edges"]) == 3 else \
+                np.full(out["onset"].shape, np.nan)
+            diffuse = L.diffuseness(out, env.ambient_density, env.speed_of_sound)
+            np.savez(args.lateral_out, edges=np.array(plan["edges"]), captures=captures, period=plan["period"], sample_rate=rate,
+                     plane=plan["box"][0][2], spacing=mesh.spacing,
+                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64),
+                     lf=lf, direct_direction=came_from, lateral_axis=axis, diffuseness=diffuse, **out)
+            heard = out["onset"] != L.NONE
+            print("wrote lateral maps of plane z=%d (%d captures; %d of %d nodes heard an arrival; median LF %s) to %s"
+                  % (plan["box"][0][2], captures, heard.sum(), heard.size, "%.3f" % np.nanmedian(lf) if np.isfinite(lf).any() else "not defined",
+                     args.lateral_out))
         if arrival is not None:
             from wayverb_amd import arrival as A
             env, mesh = W.Environment(), audio_etc[2].mesh

@@ -18,6 +18,7 @@
 #include "engine_decay.hip.h"
 #include "engine_intensity.hip.h"
 #include "engine_arrival.hip.h"
+#include "engine_lateral.hip.h"
 #include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
@@ -276,6 +277,18 @@ int wv_arrival_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
 int wv_fetch_arrival(wv_engine* e, uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) {
     WV_NEED(e);
     return e->fetch_arrival(onset, peak, peak_capture, pre, moment, bins, captures);
+}
+int wv_set_lateral(wv_engine* e, const wv_lateral_plan* plan, const float* threshold_map) {
+    WV_NEED(e);
+    return e->set_lateral(plan, threshold_map);
+}
+int wv_lateral_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
+    WV_NEED(e);
+    return e->lateral_count(captures, last_step);
+}
+int wv_fetch_lateral(wv_engine* e, uint32_t* onset, double* pre, double* velocity, double* bins, uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_lateral(onset, pre, velocity, bins, captures);
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

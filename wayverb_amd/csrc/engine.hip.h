@@ -29,6 +29,9 @@
 //   engine_arrival.hip.h  energy of a box binned from each node's OWN arrival, onset and peak per node (wv_set_arrival): plan, stage, fold, fetch
 //   arrival_plan.h       (host only, no HIP) edge tables, the bin of a capture behind an onset, sizes and places, the fold's traffic model
 //   arrival_kernels.hip.h     its fold: decay_fold_kernel's scheme with a bin that differs from lane to lane
+//   engine_lateral.hip.h  p^2, p v and v v^T of a box binned from each node's OWN arrival (wv_set_lateral): plan, stage, fold, fetch
+//   lateral_plan.h       (host only, no HIP) what a lateral plan is refused for, sizes and places, the fold's traffic model
+//   lateral_kernels.hip.h     its fold: arrival_fold_kernel's onset and bin around intensity_fold_kernel's integrator
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -40,6 +43,7 @@
 #include "decay_plan.h"
 #include "intensity_plan.h"
 #include "arrival_plan.h"
+#include "lateral_plan.h"
 #include "capture_stage.h"
 
 #include "boundary_kernels.hip.h"
@@ -52,6 +56,7 @@
 #include "decay_bands_kernels.hip.h"
 #include "intensity_kernels.hip.h"
 #include "arrival_kernels.hip.h"
+#include "lateral_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -213,6 +218,11 @@ public:
     int arrival_count(uint64_t* captures, uint64_t* last_step) override;
     int fetch_arrival(uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) override;
     bool arrival_active() const override { return arr_.active; }
+    // ---- engine_lateral.hip.h
+    int set_lateral(const wv_lateral_plan* plan, const float* threshold_map) override;
+    int lateral_count(uint64_t* captures, uint64_t* last_step) override;
+    int fetch_lateral(uint32_t* onset, double* pre, double* velocity, double* bins, uint64_t* captures) override;
+    bool lateral_active() const override { return lat_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -449,6 +459,9 @@ private:
         unsigned char* arr_state = nullptr;  // the arrival plan's per-node state, one block (engine_arrival.hip.h), likewise
         size_t arr_bytes = 0;
         uint64_t arr_generation = 0, arr_captures = 0, arr_last_step = 0, arr_next = 0;
+        unsigned char* lat_state = nullptr;  // the lateral plan's per-node state, one block (engine_lateral.hip.h), likewise
+        size_t lat_bytes = 0;
+        uint64_t lat_generation = 0, lat_captures = 0, lat_last_step = 0, lat_next = 0;
     } ckpt_;
     // field snapshots (engine_snapshot.hip.h): a ring of device slots the capture kernel fills on the compute stream, each copied to its
     // page-locked twin on a stream of its own, and the log of the snapshots the host holds
@@ -619,16 +632,50 @@ private:
     int arrival_begin_run();
     int arrival_checkpoint();
     int arrival_rollback();
+    // lateral maps (engine_lateral.hip.h): the intensity plan's device-only stage, and ONE block of per-node state the fold kernel
+    // carries (lateral_plan.h has the places): pre, velocity, bins, onset.  The edge table and the number of the first staged capture
+    // go to the kernel as arguments: there is no table to copy
+    struct Lateral {
+        bool active = false;
+        wv_lateral_plan plan{};
+        wv::SnapshotBox box;
+        uint64_t generation = 0;        // bumped by every wv_set_lateral (a checkpoint remembers which plan it saw)
+        wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
+        uint64_t nodes = 0;             // B: nodes taken
+        double k = 0;                   // ambient_density * sample_rate
+        float* stage = nullptr;         // [T][4][B]: pressure, gx, gy, gz
+        unsigned char* state = nullptr; // double pre[B], velocity[3][B], bins[10][n_bins][B]; uint32 onset[B]
+        size_t state_bytes = 0;
+        float* threshold_map = nullptr; // [B], or NULL: the plan's scalar for every node
+        hipEvent_t begun[2] = {nullptr, nullptr};      // around a fold, in turn (kernel timing)
+        hipEvent_t folded_ev[2] = {nullptr, nullptr};
+        bool timed[2] = {false, false};
+        int pair = 0;                   // the event pair the next fold records
+        uint64_t folds = 0;             // WV_QUERY_LATERAL_FOLDS
+        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
+        hipEvent_t gather_begun[wv::kLateralStage] = {}, gather_done[wv::kLateralStage] = {};  // around a slot's capture (kernel timing)
+        bool gather_timed[wv::kLateralStage] = {};
+        double gather_ms = 0;           // capture kernels' time (kernel timing on), over gathers_timed of them
+        uint64_t gathers_timed = 0;
+    } lat_;
+    static void lateral_release(Lateral& d);
+    int lateral_capture(uint64_t step);
+    int lateral_drain_timing(int pair = -1);
+    int lateral_fold();
+    int lateral_plan_batch();
+    int lateral_begin_run();
+    int lateral_checkpoint();
+    int lateral_rollback();
     // whichever plan is active decides where passes end (engine_batch.hip.h): they all exclude each other
-    bool capture_plan_active() const { return snap_.active || spec_.active || decay_.active || inten_.active || arr_.active; }
+    bool capture_plan_active() const { return snap_.active || spec_.active || decay_.active || inten_.active || arr_.active || lat_.active; }
     uint64_t capture_next() const {
-        return snap_.active ? snap_.next : spec_.active ? spec_.st.next : decay_.active ? decay_.st.next : inten_.active ? inten_.st.next : arr_.active ? arr_.st.next : wv::kNoSnapshotStep;
+        return snap_.active ? snap_.next : spec_.active ? spec_.st.next : decay_.active ? decay_.st.next : inten_.active ? inten_.st.next : arr_.active ? arr_.st.next : lat_.active ? lat_.st.next : wv::kNoSnapshotStep;
     }
     uint64_t capture_batch_end() const {
-        return snap_.active ? snap_.batch_end : spec_.active ? spec_.st.batch_end : decay_.active ? decay_.st.batch_end : inten_.active ? inten_.st.batch_end : arr_.active ? arr_.st.batch_end : wv::kNoSnapshotStep;
+        return snap_.active ? snap_.batch_end : spec_.active ? spec_.st.batch_end : decay_.active ? decay_.st.batch_end : inten_.active ? inten_.st.batch_end : arr_.active ? arr_.st.batch_end : lat_.active ? lat_.st.batch_end : wv::kNoSnapshotStep;
     }
     int capture_step(uint64_t step) {
-        return snap_.active ? snapshot_capture(step) : spec_.active ? spectrum_capture(step) : decay_.active ? decay_capture(step) : inten_.active ? intensity_capture(step) : arrival_capture(step);
+        return snap_.active ? snapshot_capture(step) : spec_.active ? spectrum_capture(step) : decay_.active ? decay_capture(step) : inten_.active ? intensity_capture(step) : arr_.active ? arrival_capture(step) : lateral_capture(step);
     }
 };
 

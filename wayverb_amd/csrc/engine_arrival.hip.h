@@ -58,6 +58,7 @@ int Engine<Real>::set_arrival(const wv_arrival_plan* plan, const float* threshol
         return fail(WV_E_STATE, "wv_set_arrival: a banded decay plan is active (wv_set_decay_bands(e, NULL, NULL, 0, 0) stops it); the plans exclude each other");
     if (decay_.active) return fail(WV_E_STATE, "wv_set_arrival: a decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");
     if (inten_.active) return fail(WV_E_STATE, "wv_set_arrival: an intensity plan is active (wv_set_intensity(e, NULL) stops it); the plans exclude each other");
+    if (lat_.active) return fail(WV_E_STATE, "wv_set_arrival: a lateral plan is active (wv_set_lateral(e, NULL, NULL) stops it); the plans exclude each other");
     if (plan->n_bins < 1 || plan->n_bins > wv::kArrivalMaxBins) return fail(WV_E_INVALID_ARGUMENT, "wv_set_arrival: n_bins must be 1 .. 16");
     if (!wv::arrival_edges_valid(plan->edges, plan->n_bins))
         return fail(WV_E_INVALID_ARGUMENT, "wv_set_arrival: edges[0] must be 0 and the edges strictly increasing");

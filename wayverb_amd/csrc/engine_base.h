@@ -112,6 +112,10 @@ struct wv_engine {
     virtual int arrival_count(uint64_t* captures, uint64_t* last_step) = 0;
     virtual int fetch_arrival(uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) = 0;
     virtual bool arrival_active() const = 0;
+    virtual int set_lateral(const wv_lateral_plan* plan, const float* threshold_map) = 0;
+    virtual int lateral_count(uint64_t* captures, uint64_t* last_step) = 0;
+    virtual int fetch_lateral(uint32_t* onset, double* pre, double* velocity, double* bins, uint64_t* captures) = 0;
+    virtual bool lateral_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;
     virtual int set_source(int kind, uint64_t node, const double* signal, uint64_t n) = 0;

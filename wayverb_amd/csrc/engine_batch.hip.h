@@ -266,6 +266,9 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
     } else if (arr_.active) {  // (engine_arrival.hip.h)
         const int rc = arrival_begin_run();
         if (rc) return rc;
+    } else if (lat_.active) {  // (engine_lateral.hip.h)
+        const int rc = lateral_begin_run();
+        if (rc) return rc;
     }
     while (completed < n_steps && flag == 0) {
         // where this batch ends: it may hold captures for half the snapshot ring
@@ -283,6 +286,9 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
             if (rc) return rc;
         } else if (arr_.active) {  // ... and the arrival plan's
             const int rc = arrival_plan_batch();
+            if (rc) return rc;
+        } else if (lat_.active) {  // ... and the lateral plan's
+            const int rc = lateral_plan_batch();
             if (rc) return rc;
         }
         uint64_t batch = plan_batch(n_steps - completed);
@@ -400,6 +406,7 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
         if (decay_.active) decay_.st.commit(steps_done);
         if (inten_.active) inten_.st.commit(steps_done);
         if (arr_.active) arr_.st.commit(steps_done);
+        if (lat_.active) lat_.st.commit(steps_done);
         if (spec_.active) spec_.st.commit(steps_done);  // the batch's captures of completed steps stay staged, the others are dropped
         completed += good;
     }
@@ -524,6 +531,18 @@ int Engine<Real>::query(int what, uint64_t* value) {
             const int rc = arrival_drain_timing();
             if (rc) return rc;
             *value = (uint64_t)(arr_.kernel_ms * 1e6 + 0.5);
+            return WV_OK;
+        }
+        case WV_QUERY_LATERAL_CAPTURES: *value = lat_.st.captures(); return WV_OK;
+        case WV_QUERY_LATERAL_FOLDS: *value = lat_.folds; return WV_OK;
+        case WV_QUERY_LATERAL_NS:
+        case WV_QUERY_LATERAL_GATHER_NS:
+        case WV_QUERY_LATERAL_GATHERS: {
+            DeviceGuard guard(device_);
+            const int rc = lateral_drain_timing();
+            if (rc) return rc;
+            *value = what == WV_QUERY_LATERAL_GATHERS ? lat_.gathers_timed
+                                                      : (uint64_t)((what == WV_QUERY_LATERAL_NS ? lat_.kernel_ms : lat_.gather_ms) * 1e6 + 0.5);
             return WV_OK;
         }
         default: return fail(WV_E_INVALID_ARGUMENT, "unknown query");

@@ -74,6 +74,7 @@ int Engine<Real>::decay_set(const wv_decay_plan* plan, const wv_biquad* sections
     if (spec_.active) return fail(WV_E_STATE, who + ": a spectrum plan is active (wv_set_spectrum(e, NULL, NULL) stops it); the plans exclude each other");
     if (inten_.active) return fail(WV_E_STATE, who + ": an intensity plan is active (wv_set_intensity(e, NULL) stops it); the plans exclude each other");
     if (arr_.active) return fail(WV_E_STATE, who + ": an arrival plan is active (wv_set_arrival(e, NULL, NULL) stops it); the plans exclude each other");
+    if (lat_.active) return fail(WV_E_STATE, who + ": a lateral plan is active (wv_set_lateral(e, NULL, NULL) stops it); the plans exclude each other");
     // the two kinds of decay plan answer to different fetches: neither setter turns one into the other behind the caller's back
     if (decay_.active && banded && !decay_.n_bands)
         return fail(WV_E_STATE, "wv_set_decay_bands: a plain decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");

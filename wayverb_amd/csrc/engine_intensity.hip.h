@@ -63,6 +63,7 @@ int Engine<Real>::set_intensity(const wv_intensity_plan* plan) {
         return fail(WV_E_STATE, "wv_set_intensity: a banded decay plan is active (wv_set_decay_bands(e, NULL, NULL, 0, 0) stops it); the plans exclude each other");
     if (decay_.active) return fail(WV_E_STATE, "wv_set_intensity: a decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");
     if (arr_.active) return fail(WV_E_STATE, "wv_set_intensity: an arrival plan is active (wv_set_arrival(e, NULL, NULL) stops it); the plans exclude each other");
+    if (lat_.active) return fail(WV_E_STATE, "wv_set_intensity: a lateral plan is active (wv_set_lateral(e, NULL, NULL) stops it); the plans exclude each other");
     const char* why = nullptr;
     if (wv::intensity_plan_check(*plan, nx_, ny_, nz_, &why)) return fail(WV_E_INVALID_ARGUMENT, why);
     // everything is allocated here, aside, and only a complete set takes the old plan's place: no room -> WV_E_HIP, engine untouched

@@ -358,6 +358,7 @@ int Engine<Real>::checkpoint(int op) {
         if (ckpt_.inten_bins) (void)hipFree(ckpt_.inten_bins);
         if (ckpt_.inten_velocity) (void)hipFree(ckpt_.inten_velocity);
         if (ckpt_.arr_state) (void)hipFree(ckpt_.arr_state);
+        if (ckpt_.lat_state) (void)hipFree(ckpt_.lat_state);
         ckpt_ = Checkpoint{};
         return WV_OK;
     }
@@ -419,6 +420,12 @@ int Engine<Real>::checkpoint(int op) {
             if (rc) return rc;
         }
         ckpt_.arr_generation = arr_.generation;
+        // the lateral plan's per-node state, count and next plan step (engine_lateral.hip.h): likewise
+        if (lat_.active) {
+            const int rc = lateral_checkpoint();
+            if (rc) return rc;
+        }
+        ckpt_.lat_generation = lat_.generation;
         WV_HIP(hipMemcpyAsync(ckpt_.field[0], field_[cur_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.field[1], field_[prv_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.fmem, fmem_, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
@@ -453,6 +460,8 @@ int Engine<Real>::checkpoint(int op) {
         return fail(WV_E_STATE, "wv_rollback: the intensity plan was set after the checkpoint (its bins have no copy to go back to)");
     if (arr_.active && ckpt_.arr_generation != arr_.generation)
         return fail(WV_E_STATE, "wv_rollback: the arrival plan was set after the checkpoint (its state has no copy to go back to)");
+    if (lat_.active && ckpt_.lat_generation != lat_.generation)
+        return fail(WV_E_STATE, "wv_rollback: the lateral plan was set after the checkpoint (its state has no copy to go back to)");
     WV_HIP(hipMemcpyAsync(field_[cur_], ckpt_.field[0], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(field_[prv_], ckpt_.field[1], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(fmem_, ckpt_.fmem, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
@@ -470,6 +479,10 @@ int Engine<Real>::checkpoint(int op) {
     }
     if (arr_.active) {  // onsets, peaks, sums and count back; what is staged is of abandoned steps
         const int rc = arrival_rollback();
+        if (rc) return rc;
+    }
+    if (lat_.active) {  // onsets, velocities, sums and count back; what is staged is of abandoned steps
+        const int rc = lateral_rollback();
         if (rc) return rc;
     }
     if (dir_.active) {

@@ -548,6 +548,8 @@ void Engine<Real>::release() {
     decay_release(decay_);
     intensity_release(inten_);
     arrival_release(arr_);
+    lateral_release(lat_);
+    if (ckpt_.lat_state) (void)hipFree(ckpt_.lat_state);
     if (ckpt_.arr_state) (void)hipFree(ckpt_.arr_state);
     if (ckpt_.inten_bins) (void)hipFree(ckpt_.inten_bins);
     if (ckpt_.inten_velocity) (void)hipFree(ckpt_.inten_velocity);

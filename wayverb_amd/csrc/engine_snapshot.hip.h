@@ -52,6 +52,7 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
     if (decay_.active) return fail(WV_E_STATE, "wv_set_snapshots: a decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");
     if (inten_.active) return fail(WV_E_STATE, "wv_set_snapshots: an intensity plan is active (wv_set_intensity(e, NULL) stops it); the plans exclude each other");
     if (arr_.active) return fail(WV_E_STATE, "wv_set_snapshots: an arrival plan is active (wv_set_arrival(e, NULL, NULL) stops it); the plans exclude each other");
+    if (lat_.active) return fail(WV_E_STATE, "wv_set_snapshots: a lateral plan is active (wv_set_lateral(e, NULL, NULL) stops it); the plans exclude each other");
     wv::SnapshotBox box;
     box.x0 = plan->x0, box.y0 = plan->y0, box.z0 = plan->z0;
     box.nx = plan->nx, box.ny = plan->ny, box.nz = plan->nz;

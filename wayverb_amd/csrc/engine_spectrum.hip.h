@@ -67,6 +67,7 @@ int Engine<Real>::set_spectrum(const wv_spectrum_plan* plan, const double* cycle
     if (decay_.active) return fail(WV_E_STATE, "wv_set_spectrum: a decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");
     if (inten_.active) return fail(WV_E_STATE, "wv_set_spectrum: an intensity plan is active (wv_set_intensity(e, NULL) stops it); the plans exclude each other");
     if (arr_.active) return fail(WV_E_STATE, "wv_set_spectrum: an arrival plan is active (wv_set_arrival(e, NULL, NULL) stops it); the plans exclude each other");
+    if (lat_.active) return fail(WV_E_STATE, "wv_set_spectrum: a lateral plan is active (wv_set_lateral(e, NULL, NULL) stops it); the plans exclude each other");
     if (plan->n_freqs < 1 || plan->n_freqs > wv::kSpectrumMaxFreqs) return fail(WV_E_INVALID_ARGUMENT, "wv_set_spectrum: n_freqs must be 1 .. 64");
     if (!cycles_per_step) return fail(WV_E_INVALID_ARGUMENT, "null argument");
     for (uint32_t k = 0; k < plan->n_freqs; ++k)

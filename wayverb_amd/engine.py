@@ -42,6 +42,7 @@ EXPORTS = [
     "wv_set_decay_bands", "wv_fetch_decay_bands", "wv_biquad_run", "wv_butterworth_bandpass", "wv_bandpass_biquad",
     "wv_set_intensity", "wv_intensity_count", "wv_fetch_intensity", "wv_fetch_intensity_velocity", "wv_fetch_directional_velocity",
     "wv_set_arrival", "wv_arrival_count", "wv_fetch_arrival",
+    "wv_set_lateral", "wv_lateral_count", "wv_fetch_lateral",
 ]
 
 
@@ -103,6 +104,13 @@ class WvArrivalPlan(C.Structure):
     """wv_arrival_plan (include/wayverb_amd.h): the box and the cadence as wv_decay_plan has them, then n_bins, the scalar threshold
     and the 16 bin edges in captures behind a node's onset."""
     _fields_ = WvDecayPlan._fields_[:11] + [("n_bins", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 16)]
+
+
+class WvLateralPlan(C.Structure):
+    """wv_lateral_plan (include/wayverb_amd.h): the box and the cadence as wv_decay_plan has them, n_bins, the scalar threshold and
+    the 8 bin edges in captures behind a node's onset, then the three arguments of the reference's directional_receiver constructor."""
+    _fields_ = WvDecayPlan._fields_[:11] + [("n_bins", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 8),
+                                            ("spacing", C.c_double), ("sample_rate", C.c_double), ("ambient_density", C.c_double)]
 
 
 ARRIVAL_NONE = 0xFFFFFFFF   # onset / peak_capture of a node that has none yet
@@ -228,6 +236,9 @@ def load_library():
     lib.wv_set_arrival.argtypes = [C.c_void_p, C.POINTER(WvArrivalPlan), C.c_void_p]
     lib.wv_arrival_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.wv_fetch_arrival.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.POINTER(C.c_uint64)]
+    lib.wv_set_lateral.argtypes = [C.c_void_p, C.POINTER(WvLateralPlan), C.c_void_p]
+    lib.wv_lateral_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.wv_fetch_lateral.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.POINTER(C.c_uint64)]
     lib.wv_biquad_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.wv_butterworth_bandpass.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.wv_bandpass_biquad.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
@@ -418,6 +429,7 @@ class Engine:
         self.decay_banded = False
         self.intensity_shape = None
         self.arrival_shape = None
+        self.lateral_shape = None
 
     @classmethod
     def from_handle(cls, handle, mesh, precision):
@@ -436,6 +448,7 @@ class Engine:
         eng.decay_banded = False
         eng.intensity_shape = None
         eng.arrival_shape = None
+        eng.lateral_shape = None
         return eng
 
     def close(self):
@@ -801,6 +814,55 @@ class Engine:
                                          C.byref(captures)))
         return out, captures.value
 
+    # ---- lateral maps accumulated on the device while wv_run goes on ---------------------------------
+    def set_lateral(self, edges, threshold=0.0, box=None, stride=1, first_step=0, period=1, threshold_map=None, spacing=None,
+                    sample_rate=None, ambient_density=None):
+        """wv_set_lateral.  `box`, `stride`, `first_step`, `period`, `spacing`, `sample_rate` (of the CAPTURED series) and
+        `ambient_density` as for set_intensity (box None: the mesh's interior -- every taken node needs its six neighbours on the
+        grid); `edges` (8 at the most), `threshold` and `threshold_map` as for set_arrival.  Per node the engine runs the reference's
+        directional_receiver integrator and keeps the onset, the energy ahead of it, the velocities and, in bins counted from the
+        node's OWN onset, p^2, p v and the six distinct entries of v v^T; lateral.lateral_fold over snapshots of the box's hull
+        reproduces all of it bit for bit.  Excludes every other plan.  set_lateral(None) stops and forgets.  Returns the shape of the
+        bins, (10, n_bins, nz, ny, nx): E, Ix, Iy, Iz, Qxx, Qyy, Qzz, Qxy, Qxz, Qyz."""
+        if edges is None:
+            _check(self.lib.wv_set_lateral(self.h, None, None))
+            self.lateral_shape = None
+            return None
+        edges = [int(v) for v in edges]
+        if len(edges) > 8:
+            raise ValueError("set_lateral: 8 bins at the most")
+        if box is None:
+            box = ((1, 1, 1), tuple(d - 2 for d in self.mesh.dims))
+        plan = WvLateralPlan()
+        taken = self._fill_box(plan, box, stride)
+        plan.first_step, plan.period, plan.n_bins, plan.threshold = int(first_step), int(period), len(edges), float(threshold)
+        for k, v in enumerate(edges):
+            plan.edges[k] = v
+        plan.spacing, plan.sample_rate, plan.ambient_density = float(spacing), float(sample_rate), float(ambient_density)
+        if threshold_map is not None:
+            threshold_map = np.ascontiguousarray(threshold_map, dtype=np.float32)
+            if threshold_map.shape != (taken[2], taken[1], taken[0]):
+                raise ValueError("set_lateral: the threshold map must have the box's shape %r" % ((taken[2], taken[1], taken[0]),))
+        _check(self.lib.wv_set_lateral(self.h, C.byref(plan), threshold_map.ctypes.data_as(C.c_void_p) if threshold_map is not None else None))
+        self.lateral_shape = (10, len(edges), taken[2], taken[1], taken[0])
+        return self.lateral_shape
+
+    def lateral_count(self):
+        """wv_lateral_count: (captures of completed steps since the plan was set, the step of the last of them)."""
+        captures, last = C.c_uint64(), C.c_uint64()
+        _check(self.lib.wv_lateral_count(self.h, C.byref(captures), C.byref(last)))
+        return captures.value, last.value
+
+    def fetch_lateral(self):
+        """wv_fetch_lateral: (dict(onset=uint32[nz, ny, nx], pre=float64[nz, ny, nx], velocity=float64[3, nz, ny, nx],
+        bins=float64[10, n_bins, nz, ny, nx]), captures in them).  ARRIVAL_NONE marks a node without an onset.  The plan keeps running."""
+        shape = tuple(getattr(self, "lateral_shape", None) or (0, 0, 0, 0, 0))   # (no plan: the library says so)
+        out = dict(onset=np.zeros(shape[2:], np.uint32), pre=np.zeros(shape[2:], np.float64), velocity=np.zeros((3,) + shape[2:], np.float64),
+                   bins=np.zeros(shape, np.float64))
+        captures = C.c_uint64()
+        _check(self.lib.wv_fetch_lateral(self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in ("onset", "pre", "velocity", "bins")], C.byref(captures)))
+        return out, captures.value
+
     def step_count(self):
         s = C.c_uint64()
         _check(self.lib.wv_step_count(self.h, C.byref(s)))
@@ -835,6 +897,7 @@ class Engine:
     QUERY_DECAY_CAPTURES, QUERY_DECAY_FOLDS, QUERY_DECAY_NS = 29, 30, 31
     QUERY_INTENSITY_CAPTURES, QUERY_INTENSITY_FOLDS, QUERY_INTENSITY_NS, QUERY_INTENSITY_GATHER_NS, QUERY_INTENSITY_GATHERS = 32, 33, 34, 35, 36
     QUERY_ARRIVAL_CAPTURES, QUERY_ARRIVAL_FOLDS, QUERY_ARRIVAL_NS = 37, 38, 39
+    QUERY_LATERAL_CAPTURES, QUERY_LATERAL_FOLDS, QUERY_LATERAL_NS, QUERY_LATERAL_GATHER_NS, QUERY_LATERAL_GATHERS = 40, 41, 42, 43, 44
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

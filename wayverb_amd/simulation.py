@@ -160,9 +160,38 @@ def arrival_plan_arguments(arrival, mesh, sample_rate):
                 first_step=int(arrival.get("first_step", 0)), period=every)
 
 
+def lateral_plan_arguments(lateral, mesh, sample_rate, environment):
+    """canonical's `lateral` dict -> keyword arguments of Engine.set_lateral: dict(plane=z in metres | box=((x0, y0, z0), extent),
+    stride=1, every=1, threshold=, threshold_map=None, edges_ms=(0, 5, 80), first_step=0).  `plane`: that horizontal plane less its
+    rim (every taken node needs its six neighbours on the grid).  The bins begin at every one of `edges_ms` milliseconds behind each
+    node's onset, the first of which is 0 (lateral.edges_from_ms at the rate of the captured series, sample_rate / every: with the
+    default, bin 1 over bins 0 and 1 is J_LF's 5 .. 80 ms over 0 .. 80 ms); `threshold` is the pressure magnitude that counts as the
+    arrival of the direct sound; spacing, the rate of the captured series and the environment's density are filled in."""
+    from . import lateral as L
+    unknown = set(lateral) - {"plane", "box", "stride", "every", "threshold", "threshold_map", "edges_ms", "first_step"}
+    if unknown or ("plane" in lateral) == ("box" in lateral) or "threshold" not in lateral:
+        raise ValueError("lateral=dict(plane=<z in metres> or box=..., threshold=, every=, edges_ms=, threshold_map=, stride=, first_step=)")
+    every = int(lateral.get("every", 1))
+    if every < 1:
+        raise ValueError("lateral: every must be >= 1")
+    edges_ms = [float(m) for m in lateral.get("edges_ms", (0.0, 5.0, 80.0))]
+    if not edges_ms or edges_ms[0] != 0.0 or len(edges_ms) > L.MAX_BINS:
+        raise ValueError("lateral: edges_ms begins with 0 and has 8 entries at the most")
+    if "plane" in lateral:
+        plane = int(round((float(lateral["plane"]) - mesh.min_corner[2]) / mesh.spacing))
+        if not 1 <= plane <= mesh.dims[2] - 2:
+            raise ValueError("lateral: plane z=%g m has no node with both neighbours in the mesh" % float(lateral["plane"]))
+        box = ((1, 1, plane), (mesh.dims[0] - 2, mesh.dims[1] - 2, 1))
+    else:
+        box = lateral["box"]
+    return dict(edges=L.edges_from_ms(edges_ms[1:], every, sample_rate), threshold=float(lateral["threshold"]),
+                threshold_map=lateral.get("threshold_map"), box=box, stride=lateral.get("stride", 1), first_step=int(lateral.get("first_step", 0)),
+                period=every, spacing=mesh.spacing, sample_rate=sample_rate / every, ambient_density=environment.ambient_density)
+
+
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
               device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None, decay=None, intensity=None,
-              arrival=None):
+              arrival=None, lateral=None):
     """canonical (single band): hard source at `source`, directional receiver at `receiver`, for
     ceil(sample_rate * simulation_time) steps.  Returns [(directional records, sample_rate,
     (0, cutoff))] -- the bandpass_band list waveguide::postprocess takes -- or None when stopped early.
@@ -194,7 +223,14 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     per node of that plane or box and on the device, the capture at which the direct sound arrived, the peak, and the squared pressure
     in bins counted from the node's OWN arrival (Engine.set_arrival); the return value is then (bands, (dict(onset, peak, peak_capture,
     pre, moment, bins), captures)), which wayverb_amd.arrival turns into arrival time, C50 / C80, D50 and centre time.  One domain
-    only, and not together with another plan."""
+    only, and not together with another plan.
+    `lateral`: dict(plane=<z in metres> or box=..., every=, threshold=, edges_ms=(0, 5, 80)) (lateral_plan_arguments) -- the engine
+    runs the directional receiver's integrator at every node of that plane or box and keeps, on the device and in bins counted from
+    the node's OWN arrival, the squared pressure, the intensity and the second moments of the particle velocity (Engine.set_lateral);
+    the return value is then (bands, (dict(onset, pre, velocity, bins), captures)), which wayverb_amd.lateral turns into the early
+    lateral energy fraction, the direct sound's direction and the diffuseness.  One domain only, and not together with another plan."""
+    if lateral is not None and slabs > 1:
+        raise ValueError("lateral maps are accumulated on one domain only (slabs=1)")
     if arrival is not None and slabs > 1:
         raise ValueError("arrival maps are accumulated on one domain only (slabs=1)")
     if intensity is not None and slabs > 1:
@@ -216,6 +252,7 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
         decay = dict(decay, bands=np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in decay["bands"]]))
     intensity_plan = intensity_plan_arguments(intensity, mesh, sample_rate, environment, simulation_time) if intensity is not None else None
     arrival_plan = arrival_plan_arguments(arrival, mesh, sample_rate) if arrival is not None else None
+    lateral_plan = lateral_plan_arguments(lateral, mesh, sample_rate, environment) if lateral is not None else None
 
     def mesh_index(pt):
         idx = vm.compute_index(pt)
@@ -248,6 +285,8 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 eng.set_intensity(**intensity_plan)
             if arrival_plan is not None:
                 eng.set_arrival(**arrival_plan)
+            if lateral_plan is not None:
+                eng.set_lateral(**lateral_plan)
             done, traces = E.run_fast(eng, E.SOURCE_HARD, mesh_index(source), signal, [receiver_index] + list(neighbours),
                                       keep_going=keep_going)
             taken = eng.fetch_snapshots() if snapshots is not None else None
@@ -259,13 +298,17 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 taken = eng.fetch_intensity()
             if arrival_plan is not None:
                 taken = eng.fetch_arrival()
+            if lateral_plan is not None:
+                taken = eng.fetch_lateral()
         finally:
             eng.close()
     if done != ideal_steps:
         return None
     directional = P.directional_receiver(traces, mesh.spacing, sample_rate, environment.ambient_density)
     bands = [(directional, sample_rate, (0.0, float(cutoff)))]
-    return bands if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None else (bands, taken)
+    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None and lateral is None:
+        return bands
+    return bands, taken
 
 
 def spectrum_plan_arguments(spectrum, sample_rate):
@@ -386,20 +429,21 @@ def canonical_multiband(vm, source, receiver, environment, bands, cutoff, usable
 def impulse_response(vertices, triangles, surface_absorptions, source, receiver, cutoff=200.0, usable_portion=0.6,
                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
                      pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None, decay=None,
-                     intensity=None, arrival=None):
+                     intensity=None, arrival=None, lateral=None):
     """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio.
     `snapshots`: a function mesh -> keyword arguments of Engine.set_snapshots (the mesh's size is not known before it is built),
     or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member.
     `spectrum`: a function mesh -> canonical's `spectrum` dict, or the dict; the fourth member is then (spectrum, captures).
     `decay`: a function (mesh, sample_rate) -> canonical's `decay` dict, or the dict; the fourth member is then (bins, captures).
     `intensity`: canonical's `intensity` dict; the fourth member is then (bins [4, n_bins, nz, ny, nx], captures).
-    `arrival`: canonical's `arrival` dict; the fourth member is then (dict(onset, peak, peak_capture, pre, moment, bins), captures)."""
+    `arrival`: canonical's `arrival` dict; the fourth member is then (dict(onset, peak, peak_capture, pre, moment, bins), captures).
+    `lateral`: canonical's `lateral` dict; the fourth member is then (dict(onset, pre, velocity, bins), captures)."""
     environment = environment or Environment()
     vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
     if spectrum is not None and snapshots is not None:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
-    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None:
+    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None and lateral is None:
         bands = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device)
         taken = None
     else:
@@ -414,6 +458,8 @@ def impulse_response(vertices, triangles, surface_absorptions, source, receiver,
             plans["intensity"] = intensity
         if arrival is not None:
             plans["arrival"] = arrival
+        if lateral is not None:
+            plans["lateral"] = lateral
         both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, **plans)
         if both is None:
             raise RuntimeError("the waveguide run was stopped early")
