@@ -30,13 +30,25 @@ def test_arrival_planning_header_against_hand_derived_cases():
     # the plan's header is host code: no HIP in it; the engine file keeps no stage bookkeeping of its own; one launch site
     assert "hip" not in open(os.path.join(CSRC, "arrival_plan.h")).read().split("#pragma once")[1].lower()
     text = open(os.path.join(CSRC, "engine_arrival.hip.h")).read()
-    assert ".st." in text and "spectrum_good_captures" not in text and "steps.push_back" not in text
+    for word in ("spectrum_good_captures", "steps.push_back", "hipEventElapsedTime", "plan_batch_end(", "begin_run("):
+        assert word not in text, word
+    shared = open(os.path.join(CSRC, "engine_staged.hip.h")).read()   # (the life cycle's one copy, on capture_stage.h's bookkeeping)
+    assert ".st." in shared and "spectrum_good_captures" not in shared and "steps.push_back" not in shared
     launches = [name for name in sorted(os.listdir(CSRC)) if name.endswith((".h", ".hip")) and
                 re.search(r"hipLaunchKernelGGL\(\(?wv::arrival_fold_kernel\b", open(os.path.join(CSRC, name)).read())]
     assert launches == ["engine_arrival.hip.h"]
-    # every other plan's setter refuses while an arrival plan is active, in the wording of the existing refusals
-    for name in ("engine_snapshot.hip.h", "engine_spectrum.hip.h", "engine_decay.hip.h", "engine_intensity.hip.h"):
-        assert open(os.path.join(CSRC, name)).read().count("an arrival plan is active (wv_set_arrival(e, NULL, NULL) stops it); the plans exclude each other") == 1
+    # every other plan's setter refuses while an arrival plan is active, in the wording of the existing refusals: each plan's sentence
+    # stands once in all of the sources, in the one function every setter's file calls
+    sources = {name: open(os.path.join(CSRC, name)).read() for name in sorted(os.listdir(CSRC)) if name.endswith((".h", ".hip", ".cpp"))}
+    for sentence in ("a snapshot plan is active (wv_set_snapshots(e, NULL) stops it)", "a spectrum plan is active (wv_set_spectrum(e, NULL, NULL) stops it)",
+                     "a banded decay plan is active (wv_set_decay_bands(e, NULL, NULL, 0, 0) stops it)", "a decay plan is active (wv_set_decay(e, NULL) stops it)",
+                     "an intensity plan is active (wv_set_intensity(e, NULL) stops it)", "an arrival plan is active (wv_set_arrival(e, NULL, NULL) stops it)",
+                     "a lateral plan is active (wv_set_lateral(e, NULL, NULL) stops it)"):
+        assert sum(text.count(sentence + "; the plans exclude each other") for text in sources.values()) == 1, sentence
+    assert "two plans exclude" not in "".join(sources.values())
+    for name in ("engine_snapshot.hip.h", "engine_spectrum.hip.h", "engine_decay.hip.h", "engine_intensity.hip.h", "engine_arrival.hip.h", "engine_lateral.hip.h"):
+        # (engine_decay.hip.h keeps the one refusal that is its own: a banded plan asked for under a plain one)
+        assert sources[name].count("plan_refused(") == 1 and sources[name].count("plan is active (") == (name == "engine_decay.hip.h"), name
 
 
 def test_arrival_entry_points_are_exported_and_bound(built_library):

@@ -24,10 +24,17 @@ def test_decay_planning_header_against_hand_derived_cases():
     includes = lambda name: sorted(re.findall(r"#include [<\"]([^>\"]+)[>\"]", open(os.path.join(CSRC, name)).read()))   # noqa: E731
     assert includes("decay_plan.h") == ["cstdint", "limits"]
     assert includes("capture_stage.h") == ["cstdint", "snapshot_plan.h", "spectrum_plan.h", "vector"]
-    # one copy of the stage's bookkeeping: neither engine file keeps staged steps or a committed count of its own
-    for name in ("engine_spectrum.hip.h", "engine_decay.hip.h"):
+    # one copy of the stage's bookkeeping and of the life cycle around it: no plan's engine file keeps staged steps or a committed count
+    # of its own, times a fold, cuts a batch or enters a run; engine_staged.hip.h makes every call into the stage's bookkeeping
+    for name in ("engine_spectrum.hip.h", "engine_decay.hip.h", "engine_intensity.hip.h", "engine_arrival.hip.h", "engine_lateral.hip.h"):
         text = open(os.path.join(CSRC, name)).read()
-        assert ".st." in text and "spectrum_good_captures" not in text and "steps.push_back" not in text, name
+        for word in ("spectrum_good_captures", "steps.push_back", "hipEventElapsedTime", "plan_batch_end(", "begin_run("):
+            assert word not in text, (name, word)
+    shared = open(os.path.join(CSRC, "engine_staged.hip.h")).read()
+    for call in (".st.start(", ".st.full()", ".st.slot()", ".st.staged(", ".st.drop_uncommitted()", ".st.fold_due()", ".st.plan_batch_end(", ".st.begin_run(",
+                 ".st.commit(", ".st.all_folded()", ".st.captures()", ".st.rollback("):
+        assert call in shared, call
+    assert "spectrum_good_captures" not in shared and "steps.push_back" not in shared
     # ... and one launch site of the capture kernel
     launches = [name for name in sorted(os.listdir(CSRC)) if name.endswith((".h", ".hip")) and
                 "hipLaunchKernelGGL((wv::snapshot_gather_kernel" in open(os.path.join(CSRC, name)).read()]

@@ -32,7 +32,10 @@ def test_intensity_planning_header_against_hand_derived_cases():
     # the plan's header is host code: no HIP in it; the engine file keeps no stage bookkeeping of its own; one launch site per kernel
     assert "hip" not in open(os.path.join(CSRC, "intensity_plan.h")).read().split("#pragma once")[1].lower()
     text = open(os.path.join(CSRC, "engine_intensity.hip.h")).read()
-    assert ".st." in text and "spectrum_good_captures" not in text and "steps.push_back" not in text
+    for word in ("spectrum_good_captures", "steps.push_back", "hipEventElapsedTime", "plan_batch_end(", "begin_run("):
+        assert word not in text, word
+    shared = open(os.path.join(CSRC, "engine_staged.hip.h")).read()   # (the life cycle's one copy, on capture_stage.h's bookkeeping)
+    assert ".st." in shared and "launch_intensity_gather(" in shared and "spectrum_good_captures" not in shared and "steps.push_back" not in shared
     for kernel, where in (("intensity_gather_kernel", "engine_snapshot.hip.h"), ("intensity_fold_kernel", "engine_intensity.hip.h")):
         launches = [name for name in sorted(os.listdir(CSRC)) if name.endswith((".h", ".hip")) and
                     re.search(r"hipLaunchKernelGGL\(\(?wv::%s\b" % kernel, open(os.path.join(CSRC, name)).read())]

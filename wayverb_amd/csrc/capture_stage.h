@@ -1,10 +1,11 @@
-// capture_stage.h -- (host only, no HIP) the bookkeeping of a stage of captures, shared by the two plans that accumulate on the device:
-// field spectra (engine_spectrum.hip.h) and energy decay maps (engine_decay.hip.h).  Both capture a box as a snapshot plan does into
-// the next free slot of a device-only stage float[T][B], keep a batch's captures staged until commit_batch has said how many of the
-// batch's steps were good, and fold everything staged in one launch when the stage has no slot left.  What differs between them is
-// the fold itself; which steps were staged, how many of them are committed, which plan step comes next and where the batch being
-// planned ends is the same, and lives here.  The integer rules (free slots, fold due, captures per batch, good captures after a stop)
-// are spectrum_plan.h's, unchanged; which steps are plan steps is snapshot_plan.h's.
+// capture_stage.h -- (host only, no HIP) the bookkeeping of a stage of captures, shared by the five plans that accumulate on the device:
+// field spectra, energy decay maps (plain and banded), intensity maps, arrival-aligned energy maps and lateral maps (engine_staged.hip.h
+// has their life cycle, engine_<plan>.hip.h what is each plan's own).  All capture a box into the next free slot of a device-only
+// stage, keep a batch's captures staged until commit_batch has said how many of the batch's steps were good, and fold everything staged
+// in one launch when the stage has no slot left.  What differs between them is the fold itself; which steps were staged, how many of
+// them are committed, which plan step comes next and where the batch being planned ends is the same, and lives here.  The integer rules
+// (free slots, fold due, captures per batch, good captures after a stop) are spectrum_plan.h's, unchanged; which steps are plan steps is
+// snapshot_plan.h's.
 #pragma once
 #include <cstdint>
 #include <vector>

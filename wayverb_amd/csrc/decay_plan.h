@@ -10,7 +10,7 @@
 
 namespace wv {
 
-constexpr int kDecayStage = 16;            // T: captures the stage holds (== kSpectrumStage: engine_decay.hip.h asserts it)
+constexpr int kDecayStage = 16;            // T: captures the stage holds (== kSpectrumStage: engine_staged.hip.h asserts it)
 constexpr uint32_t kDecayMaxBins = 4096;   // n_bins at the most
 constexpr uint64_t kDecayNoSize = std::numeric_limits<uint64_t>::max();  // "does not fit 64 bits"
 

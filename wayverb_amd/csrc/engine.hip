@@ -14,6 +14,7 @@
 #include "engine_batch.hip.h"
 #include "engine_io.hip.h"
 #include "engine_snapshot.hip.h"
+#include "engine_staged.hip.h"
 #include "engine_spectrum.hip.h"
 #include "engine_decay.hip.h"
 #include "engine_intensity.hip.h"

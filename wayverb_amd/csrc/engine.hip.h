@@ -17,9 +17,10 @@
 //                        receivers
 //   engine_snapshot.hip.h  field snapshots taken on the device while a run goes on (wv_set_snapshots): plan, ring, capture, copy stream, held log
 //   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape
+//   engine_staged.hip.h  the life cycle the five accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release
 //   engine_spectrum.hip.h  field spectra accumulated on the device while a run goes on (wv_set_spectrum): plan, stage, fold, fetch
 //   spectrum_plan.h      (host only, no HIP) free slots of the stage, when a fold is due, which captures survive a stop, sizes
-//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the spectrum and the decay plan
+//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the five accumulating plans
 //   engine_decay.hip.h   time-binned field energy accumulated on the device while a run goes on (wv_set_decay): plan, stage, fold, fetch
 //   decay_plan.h         (host only, no HIP) the bin of a capture, sizes, the fold's traffic model
 //   decay_bands_kernels.hip.h   the fold of a band-limited decay plan (wv_set_decay_bands): biquad cascades ahead of the square
@@ -429,6 +430,9 @@ private:
     void directional_release();
     int directional_enqueue(uint64_t batch);
     std::unique_ptr<wv::SlabComm> comm_;
+    // the five plans that accumulate on the device (engine_staged.hip.h)
+    enum PlanKind { kSpectrumPlan, kDecayPlan, kIntensityPlan, kArrivalPlan, kLateralPlan, kPlanKinds };
+    static constexpr int kPlanBlocks = 2;  // device blocks of accumulated state a plan has at the most
     // wv_checkpoint / wv_rollback (engine_io.hip.h): device copies of the two live fields and the filter memories, and the
     // host-side position that goes with them
     struct Checkpoint {
@@ -444,24 +448,20 @@ private:
         uint32_t dir_n = 0;              // (receivers the copy has room for)
         size_t dir_log_size = 0;
         uint64_t dir_generation = 0;
-        double* spec_acc = nullptr;  // the spectrum plan's sums (engine_spectrum.hip.h), allocated by the first checkpoint under a plan
-        size_t spec_bytes = 0;
-        uint64_t spec_generation = 0, spec_captures = 0, spec_last_step = 0, spec_next = 0;
-        double* decay_bins = nullptr;  // the decay plan's bins (engine_decay.hip.h), allocated by the first checkpoint under a plan
-        size_t decay_bytes = 0;
-        double* decay_state = nullptr;  // a banded plan's filter states, likewise
-        size_t decay_state_bytes = 0;
-        uint64_t decay_generation = 0, decay_captures = 0, decay_last_step = 0, decay_next = 0;
-        double* inten_bins = nullptr;      // the intensity plan's bins and velocities (engine_intensity.hip.h), likewise
-        double* inten_velocity = nullptr;
-        size_t inten_bytes = 0, inten_velocity_bytes = 0;
-        uint64_t inten_generation = 0, inten_captures = 0, inten_last_step = 0, inten_next = 0;
-        unsigned char* arr_state = nullptr;  // the arrival plan's per-node state, one block (engine_arrival.hip.h), likewise
-        size_t arr_bytes = 0;
-        uint64_t arr_generation = 0, arr_captures = 0, arr_last_step = 0, arr_next = 0;
-        unsigned char* lat_state = nullptr;  // the lateral plan's per-node state, one block (engine_lateral.hip.h), likewise
-        size_t lat_bytes = 0;
-        uint64_t lat_generation = 0, lat_captures = 0, lat_last_step = 0, lat_next = 0;
+        // an accumulating plan's state blocks, count and position (engine_staged.hip.h), by PlanKind; the copies are allocated by the
+        // first checkpoint taken under the plan
+        struct PlanSave {
+            unsigned char* block[kPlanBlocks] = {nullptr, nullptr};
+            size_t bytes[kPlanBlocks] = {0, 0};
+            uint64_t generation = 0, captures = 0, last_step = 0, next = 0;
+        } plan[kPlanKinds];
+        void free_plans() {
+            for (PlanSave& s : plan)
+                for (unsigned char*& block : s.block) {
+                    if (block) (void)hipFree(block);
+                    block = nullptr;
+                }
+        }
     } ckpt_;
     // field snapshots (engine_snapshot.hip.h): a ring of device slots the capture kernel fills on the compute stream, each copied to its
     // page-locked twin on a stream of its own, and the log of the snapshots the host holds
@@ -504,179 +504,154 @@ private:
     int snapshot_plan_batch();
     int snapshot_begin_run();
     void snapshot_rollback(uint64_t to_step);
-    // field spectra (engine_spectrum.hip.h): the device-only stage the capture kernel fills on the compute stream, the planar sums the
-    // fold kernel accumulates, two twiddle tables (page-locked, and their device copies) the host writes in turn
-    struct Spectrum {
-        bool active = false, gather_wide = false, fold_wide = false;
-        wv_spectrum_plan plan{};
+    // ---- engine_staged.hip.h: the five plans that accumulate on the device -- spectrum, decay (plain and banded), intensity, arrival,
+    // lateral -- have ONE life cycle: captures into a device-only stage on the compute stream, committed batch by batch, folded into the
+    // plan's accumulated state in one launch when the stage has no slot left, on fetch and on checkpoint.  StagedPlan holds what they
+    // share; a plan's own struct adds its wv_*_plan, its tables and what its fold kernel needs
+    struct StagedPlan {
+        // what the kind is, set once by the plan's own struct
+        PlanKind kind;
+        const char* name;                   // "spectrum": in "wv_run: the spectrum stage is full" and the like
+        const char* setter;                 // "wv_set_spectrum"
+        const char* lost;                   // "its sums have": what wv_rollback says of a plan set after the checkpoint
+        const char* block_name[kPlanBlocks];  // "the spectrum's sums": what wv_checkpoint has no room for a copy of
+        bool host_table;                    // the fold reads a table the host writes: folded_ev is always recorded, and waited on before the table is rewritten
+        bool gradients;                     // a capture is intensity_gather_kernel's four planes (timed per slot), not snapshot_gather_kernel's one
+        uint64_t max_captures;              // captures the state can count (onsets 32 bits wide, all bits set = none); ~0: no limit
+        StagedPlan(PlanKind kind, const char* name, const char* setter, const char* lost, const char* block0, const char* block1, bool host_table,
+                   bool gradients, uint64_t max_captures = ~0ull)
+            : kind(kind), name(name), setter(setter), lost(lost), block_name{block0, block1}, host_table(host_table), gradients(gradients),
+              max_captures(max_captures) {}
+        bool active = false;
+        bool gather_wide = false;       // the capture takes four nodes per lane (as engine_snapshot.hip.h decides it)
+        bool fold_wide = false;         // the fold takes two nodes per lane
         wv::SnapshotBox box;
-        std::vector<double> freqs;      // cycles per step, [K]
-        uint64_t generation = 0;        // bumped by every wv_set_spectrum (a checkpoint remembers which plan it saw)
+        double spacing = 0;             // of the mesh (gradients only)
+        uint64_t generation = 0;        // bumped by every call of the setter (a checkpoint remembers which plan it saw)
         wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
         uint64_t nodes = 0;             // B: nodes taken
-        float* stage = nullptr;         // [T][B]
-        double* acc = nullptr;          // [K][2][B]
+        float* stage = nullptr;         // [T][B], with gradients [T][4][B]: pressure, gx, gy, gz
+        unsigned char* block[kPlanBlocks] = {nullptr, nullptr};  // the accumulated state: what a checkpoint copies and a rollback restores
+        size_t block_bytes[kPlanBlocks] = {0, 0};
+        int n_blocks = 0;
+        hipEvent_t begun[2] = {nullptr, nullptr};      // before a fold (kernel timing), in turn
+        hipEvent_t folded_ev[2] = {nullptr, nullptr};  // behind it; a host table: the host may write the turn's table again
+        bool used[2] = {false, false}, timed[2] = {false, false};
+        int turn = 0;                   // the event pair (and table) the next fold takes
+        uint64_t folds = 0;             // WV_QUERY_*_FOLDS
+        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
+        hipEvent_t gather_begun[wv::kSpectrumStage] = {}, gather_done[wv::kSpectrumStage] = {};  // around a slot's capture (gradients, kernel timing)
+        bool gather_timed[wv::kSpectrumStage] = {};
+        double gather_ms = 0;           // capture kernels' time (kernel timing on), over gathers_timed of them
+        uint64_t gathers_timed = 0;
+    };
+    // the staged captures' bins, int32[t], which the host writes into one of two page-locked tables in turn (two, so that it never rewrites
+    // a table a queued copy still reads) and copies ahead of the fold: the decay and the intensity plan's (engine_decay.hip.h)
+    struct BinTable {
+        int32_t* host[2] = {nullptr, nullptr};
+        int32_t* dev[2] = {nullptr, nullptr};
+    };
+    hipError_t bin_table_allocate(BinTable& table);
+    static void bin_table_free(BinTable& table);
+    int bin_table_write(BinTable& table, const StagedPlan& p, int b, int t, uint32_t bin_captures, uint32_t n_bins);
+    // field spectra (engine_spectrum.hip.h): the planar sums the fold kernel accumulates, two twiddle tables (page-locked, and their device
+    // copies) the host writes in turn
+    struct Spectrum : StagedPlan {
+        Spectrum() : StagedPlan(kSpectrumPlan, "spectrum", "wv_set_spectrum", "its sums have", "the spectrum's sums", nullptr, true, false) {}
+        wv_spectrum_plan plan{};
+        std::vector<double> freqs;      // cycles per step, [K]
+        double* acc() const { return reinterpret_cast<double*>(this->block[0]); }  // [K][2][B]
         double* tw_host[2] = {nullptr, nullptr};
         double* tw_dev[2] = {nullptr, nullptr};
-        hipEvent_t begun[2] = {nullptr, nullptr};      // before the fold that uses the table (kernel timing)
-        hipEvent_t folded_ev[2] = {nullptr, nullptr};  // behind it: the host may write the table again
-        bool table_used[2] = {false, false}, timed[2] = {false, false};
-        int table = 0;                  // the table the next fold writes
-        uint64_t folds = 0;             // WV_QUERY_SPECTRUM_FOLDS
-        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
+        void free_own();
     } spec_;
-    static void spectrum_release(Spectrum& s);
-    int spectrum_capture(uint64_t step);
-    int spectrum_drain_timing(int table);
-    int spectrum_fold();
-    int spectrum_plan_batch();
-    int spectrum_begin_run();
-    int spectrum_checkpoint();
-    int spectrum_rollback();
-    // energy decay maps (engine_decay.hip.h): the device-only stage the capture kernel fills on the compute stream, the time-binned
-    // energies the fold kernel accumulates, two tables of the staged captures' bins (page-locked, and their device copies) the host
-    // writes in turn
-    struct Decay {
-        bool active = false, gather_wide = false, fold_wide = false;
+    int spectrum_enqueue(Spectrum& s, int b, int t, unsigned blocks);
+    // energy decay maps (engine_decay.hip.h): the time-binned energies the fold kernel accumulates; a banded plan's filter states and
+    // coefficients beside them
+    struct Decay : StagedPlan {
+        Decay() : StagedPlan(kDecayPlan, "decay", "wv_set_decay", "its bins have", "the decay plan's bins", "the decay plan's filter states", true, false) {}
         wv_decay_plan plan{};
-        wv::SnapshotBox box;
-        uint64_t generation = 0;        // bumped by every wv_set_decay (a checkpoint remembers which plan it saw)
-        wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
-        uint64_t nodes = 0;             // B: nodes taken
-        float* stage = nullptr;         // [T][B]
-        double* bins = nullptr;         // [n_bins][B]; a banded plan's: [n_bands][n_bins][B]
+        double* bins() const { return reinterpret_cast<double*>(this->block[0]); }   // [n_bins][B]; a banded plan's: [n_bands][n_bins][B]
+        double* state() const { return reinterpret_cast<double*>(this->block[1]); }  // [n_bands][n_sections][2][B]: z1, z2 of every section (banded only)
         uint32_t n_bands = 0, n_sections = 0;  // wv_set_decay_bands: 1 .. 8 cascades of 1 .. 4 sections; 0 = a plain plan
-        double* state = nullptr;        // [n_bands][n_sections][2][B]: z1, z2 of every section (banded only)
         double* coef = nullptr;         // [n_bands][n_sections][5] on the device (banded only)
-        int32_t* table_host[2] = {nullptr, nullptr};
-        int32_t* table_dev[2] = {nullptr, nullptr};
-        hipEvent_t begun[2] = {nullptr, nullptr};      // before the fold that uses the table (kernel timing)
-        hipEvent_t folded_ev[2] = {nullptr, nullptr};  // behind it: the host may write the table again
-        bool table_used[2] = {false, false}, timed[2] = {false, false};
-        int table = 0;                  // the table the next fold writes
-        uint64_t folds = 0;             // WV_QUERY_DECAY_FOLDS
-        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
+        BinTable table;
+        void free_own();
     } decay_;
-    static void decay_release(Decay& d);
     int decay_set(const wv_decay_plan* plan, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections, bool banded);
     int decay_fetch(double* dst, uint64_t* captures, bool banded);
-    int decay_capture(uint64_t step);
-    int decay_drain_timing(int table);
-    int decay_fold();
-    int decay_plan_batch();
-    int decay_begin_run();
-    int decay_checkpoint();
-    int decay_rollback();
-    // intensity maps (engine_intensity.hip.h): the device-only stage of four float planes per capture the capture kernel fills on the
-    // compute stream, the velocities the integrator carries per node, the time-binned sums Ix, Iy, Iz, E the fold kernel accumulates,
-    // two tables of the staged captures' bins (page-locked, and their device copies) the host writes in turn
-    struct Intensity {
-        bool active = false;
+    int decay_enqueue(Decay& d, int b, int t, unsigned blocks);
+    // intensity maps (engine_intensity.hip.h): the velocities the integrator carries per node and the time-binned sums Ix, Iy, Iz, E the
+    // fold kernel accumulates
+    struct Intensity : StagedPlan {
+        Intensity()
+            : StagedPlan(kIntensityPlan, "intensity", "wv_set_intensity", "its bins have", "the intensity plan's bins", "the intensity plan's velocities", true, true) {}
         wv_intensity_plan plan{};
-        wv::SnapshotBox box;
-        uint64_t generation = 0;        // bumped by every wv_set_intensity (a checkpoint remembers which plan it saw)
-        wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
-        uint64_t nodes = 0;             // B: nodes taken
         double k = 0;                   // ambient_density * sample_rate
-        float* stage = nullptr;         // [T][4][B]: pressure, gx, gy, gz
-        double* velocity = nullptr;     // [3][B]
-        double* bins = nullptr;         // [4][n_bins][B]: Ix, Iy, Iz, E
-        int32_t* table_host[2] = {nullptr, nullptr};
-        int32_t* table_dev[2] = {nullptr, nullptr};
-        hipEvent_t begun[2] = {nullptr, nullptr};      // before the fold that uses the table (kernel timing)
-        hipEvent_t folded_ev[2] = {nullptr, nullptr};  // behind it: the host may write the table again
-        bool table_used[2] = {false, false}, timed[2] = {false, false};
-        int table = 0;                  // the table the next fold writes
-        uint64_t folds = 0;             // WV_QUERY_INTENSITY_FOLDS
-        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
-        hipEvent_t gather_begun[wv::kIntensityStage] = {}, gather_done[wv::kIntensityStage] = {};  // around a slot's capture (kernel timing)
-        bool gather_timed[wv::kIntensityStage] = {};
-        double gather_ms = 0;           // capture kernels' time (kernel timing on), over gathers_timed of them
-        uint64_t gathers_timed = 0;
+        double* bins() const { return reinterpret_cast<double*>(this->block[0]); }      // [4][n_bins][B]: Ix, Iy, Iz, E
+        double* velocity() const { return reinterpret_cast<double*>(this->block[1]); }  // [3][B]
+        BinTable table;
+        void free_own();
     } inten_;
-    static void intensity_release(Intensity& d);
     int launch_intensity_gather(const wv::SnapshotBox& box, double spacing, float* dst);  // (engine_snapshot.hip.h, beside launch_snapshot_gather)
-    int intensity_capture(uint64_t step);
-    int intensity_drain_timing(int table = -1);
-    int intensity_fold();
-    int intensity_plan_batch();
-    int intensity_begin_run();
-    int intensity_checkpoint();
-    int intensity_rollback();
-    // arrival-aligned energy maps (engine_arrival.hip.h): the device-only stage the capture kernel fills on the compute stream, and ONE
-    // block of per-node state the fold kernel carries (arrival_plan.h has the places): pre, moment, bins, onset, peak, peak_capture.
-    // The edge table and the number of the first staged capture go to the kernel as arguments: there is no table to copy
-    struct Arrival {
-        bool active = false, gather_wide = false;
+    int intensity_enqueue(Intensity& d, int b, int t, unsigned blocks);
+    // arrival-aligned energy maps (engine_arrival.hip.h): ONE block of per-node state the fold kernel carries (arrival_plan.h has the
+    // places): pre, moment, bins, onset, peak, peak_capture.  The edge table and the number of the first staged capture go to the kernel
+    // as arguments: there is no table to copy
+    struct Arrival : StagedPlan {
+        Arrival() : StagedPlan(kArrivalPlan, "arrival", "wv_set_arrival", "its state has", "the arrival plan's state", nullptr, false, false, wv::kArrivalMaxCaptures) {}
         wv_arrival_plan plan{};
-        wv::SnapshotBox box;
-        uint64_t generation = 0;        // bumped by every wv_set_arrival (a checkpoint remembers which plan it saw)
-        wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
-        uint64_t nodes = 0;             // B: nodes taken
-        float* stage = nullptr;         // [T][B]
-        unsigned char* state = nullptr; // double pre[B], moment[B], bins[n_bins][B]; uint32 onset[B]; float peak[B]; uint32 peak_capture[B]
-        size_t state_bytes = 0;
+        unsigned char* state() const { return this->block[0]; }  // double pre[B], moment[B], bins[n_bins][B]; uint32 onset[B]; float peak[B]; uint32 peak_capture[B]
         float* threshold_map = nullptr; // [B], or NULL: the plan's scalar for every node
-        hipEvent_t begun[2] = {nullptr, nullptr};      // around a fold, in turn (kernel timing)
-        hipEvent_t folded_ev[2] = {nullptr, nullptr};
-        bool timed[2] = {false, false};
-        int pair = 0;                   // the event pair the next fold records
-        uint64_t folds = 0;             // WV_QUERY_ARRIVAL_FOLDS
-        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
+        void free_own();
     } arr_;
-    static void arrival_release(Arrival& d);
-    int arrival_capture(uint64_t step);
-    int arrival_drain_timing(int pair = -1);
-    int arrival_fold();
-    int arrival_plan_batch();
-    int arrival_begin_run();
-    int arrival_checkpoint();
-    int arrival_rollback();
-    // lateral maps (engine_lateral.hip.h): the intensity plan's device-only stage, and ONE block of per-node state the fold kernel
-    // carries (lateral_plan.h has the places): pre, velocity, bins, onset.  The edge table and the number of the first staged capture
-    // go to the kernel as arguments: there is no table to copy
-    struct Lateral {
-        bool active = false;
+    int arrival_enqueue(Arrival& d, int b, int t, unsigned blocks);
+    // lateral maps (engine_lateral.hip.h): the intensity plan's stage, and ONE block of per-node state the fold kernel carries
+    // (lateral_plan.h has the places): pre, velocity, bins, onset.  No table either
+    struct Lateral : StagedPlan {
+        Lateral() : StagedPlan(kLateralPlan, "lateral", "wv_set_lateral", "its state has", "the lateral plan's state", nullptr, false, true, wv::kLateralMaxCaptures) {}
         wv_lateral_plan plan{};
-        wv::SnapshotBox box;
-        uint64_t generation = 0;        // bumped by every wv_set_lateral (a checkpoint remembers which plan it saw)
-        wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
-        uint64_t nodes = 0;             // B: nodes taken
         double k = 0;                   // ambient_density * sample_rate
-        float* stage = nullptr;         // [T][4][B]: pressure, gx, gy, gz
-        unsigned char* state = nullptr; // double pre[B], velocity[3][B], bins[10][n_bins][B]; uint32 onset[B]
-        size_t state_bytes = 0;
+        unsigned char* state() const { return this->block[0]; }  // double pre[B], velocity[3][B], bins[10][n_bins][B]; uint32 onset[B]
         float* threshold_map = nullptr; // [B], or NULL: the plan's scalar for every node
-        hipEvent_t begun[2] = {nullptr, nullptr};      // around a fold, in turn (kernel timing)
-        hipEvent_t folded_ev[2] = {nullptr, nullptr};
-        bool timed[2] = {false, false};
-        int pair = 0;                   // the event pair the next fold records
-        uint64_t folds = 0;             // WV_QUERY_LATERAL_FOLDS
-        double kernel_ms = 0;           // fold kernels' time (kernel timing on)
-        hipEvent_t gather_begun[wv::kLateralStage] = {}, gather_done[wv::kLateralStage] = {};  // around a slot's capture (kernel timing)
-        bool gather_timed[wv::kLateralStage] = {};
-        double gather_ms = 0;           // capture kernels' time (kernel timing on), over gathers_timed of them
-        uint64_t gathers_timed = 0;
+        void free_own();
     } lat_;
-    static void lateral_release(Lateral& d);
-    int lateral_capture(uint64_t step);
-    int lateral_drain_timing(int pair = -1);
-    int lateral_fold();
-    int lateral_plan_batch();
-    int lateral_begin_run();
-    int lateral_checkpoint();
-    int lateral_rollback();
+    int lateral_enqueue(Lateral& d, int b, int t, unsigned blocks);
+    // ---- engine_staged.hip.h: one copy of each step of the life cycle
+    StagedPlan* const staged_[kPlanKinds] = {&spec_, &decay_, &inten_, &arr_, &lat_};  // by PlanKind
+    StagedPlan* staged() const {  // the active one of the five, or null: they exclude each other (and a snapshot plan)
+        for (StagedPlan* p : staged_)
+            if (p->active) return p;
+        return nullptr;
+    }
+    enum PlanRow { kSnapshotRow, kSpectrumRow, kBandedDecayRow, kPlainDecayRow, kIntensityRow, kArrivalRow, kLateralRow };
+    int plan_refused(const std::string& setter, PlanRow self);
+    template <typename Plan>
+    static void plan_release(Plan& p);
+    static void staged_release(StagedPlan& p);
+    template <typename Plan>
+    int staged_stop(Plan& p);
+    hipError_t staged_allocate(StagedPlan& candidate, uint64_t stage_bytes, uint64_t block0_bytes, uint64_t block1_bytes = 0);
+    template <typename Plan>
+    int staged_install(Plan& current, Plan& candidate, hipError_t rc, const std::string& no_room, uint64_t first_step, uint64_t period);
+    int staged_capture(StagedPlan& p, uint64_t step);
+    int staged_drain_timing(StagedPlan& p, int turn = -1);
+    int staged_fold_begins(StagedPlan& p, int b);
+    int staged_enqueue(StagedPlan& p, int b, int t, unsigned blocks);
+    int staged_fold(StagedPlan& p);
+    int staged_settle(StagedPlan& p);
+    enum class PlanTime { folds_ns, gathers_ns, gathers };
+    int staged_time_query(StagedPlan& p, PlanTime what, uint64_t* value);
+    int staged_plan_batch(StagedPlan& p);
+    int staged_begin_run(StagedPlan& p);
+    int staged_count(const StagedPlan& p, uint64_t* captures, uint64_t* last_step);
+    int staged_checkpoint(StagedPlan& p);
+    int staged_rollback(StagedPlan& p);
     // whichever plan is active decides where passes end (engine_batch.hip.h): they all exclude each other
-    bool capture_plan_active() const { return snap_.active || spec_.active || decay_.active || inten_.active || arr_.active || lat_.active; }
-    uint64_t capture_next() const {
-        return snap_.active ? snap_.next : spec_.active ? spec_.st.next : decay_.active ? decay_.st.next : inten_.active ? inten_.st.next : arr_.active ? arr_.st.next : lat_.active ? lat_.st.next : wv::kNoSnapshotStep;
-    }
-    uint64_t capture_batch_end() const {
-        return snap_.active ? snap_.batch_end : spec_.active ? spec_.st.batch_end : decay_.active ? decay_.st.batch_end : inten_.active ? inten_.st.batch_end : arr_.active ? arr_.st.batch_end : lat_.active ? lat_.st.batch_end : wv::kNoSnapshotStep;
-    }
-    int capture_step(uint64_t step) {
-        return snap_.active ? snapshot_capture(step) : spec_.active ? spectrum_capture(step) : decay_.active ? decay_capture(step) : inten_.active ? intensity_capture(step) : arr_.active ? arrival_capture(step) : lateral_capture(step);
-    }
+    bool capture_plan_active() const { return snap_.active || staged(); }
+    uint64_t capture_next() const { return snap_.active ? snap_.next : staged() ? staged()->st.next : wv::kNoSnapshotStep; }
+    uint64_t capture_batch_end() const { return snap_.active ? snap_.batch_end : staged() ? staged()->st.batch_end : wv::kNoSnapshotStep; }
+    int capture_step(uint64_t step) { return snap_.active ? snapshot_capture(step) : staged_capture(*staged(), step); }
 };
 
 }  // namespace wv

@@ -254,20 +254,8 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
     if (snap_.active) {
         const int rc = snapshot_begin_run();
         if (rc) return rc;
-    } else if (spec_.active) {  // (engine_spectrum.hip.h)
-        const int rc = spectrum_begin_run();
-        if (rc) return rc;
-    } else if (decay_.active) {  // (engine_decay.hip.h)
-        const int rc = decay_begin_run();
-        if (rc) return rc;
-    } else if (inten_.active) {  // (engine_intensity.hip.h)
-        const int rc = intensity_begin_run();
-        if (rc) return rc;
-    } else if (arr_.active) {  // (engine_arrival.hip.h)
-        const int rc = arrival_begin_run();
-        if (rc) return rc;
-    } else if (lat_.active) {  // (engine_lateral.hip.h)
-        const int rc = lateral_begin_run();
+    } else if (StagedPlan* p = staged()) {  // (engine_staged.hip.h)
+        const int rc = staged_begin_run(*p);
         if (rc) return rc;
     }
     while (completed < n_steps && flag == 0) {
@@ -275,20 +263,8 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
         if (snap_.active) {
             const int rc = snapshot_plan_batch();
             if (rc) return rc;
-        } else if (spec_.active) {  // ... or as many captures as the spectrum's stage has free slots, folded first when it has none
-            const int rc = spectrum_plan_batch();
-            if (rc) return rc;
-        } else if (decay_.active) {  // ... the decay plan's stage likewise
-            const int rc = decay_plan_batch();
-            if (rc) return rc;
-        } else if (inten_.active) {  // ... and the intensity plan's
-            const int rc = intensity_plan_batch();
-            if (rc) return rc;
-        } else if (arr_.active) {  // ... and the arrival plan's
-            const int rc = arrival_plan_batch();
-            if (rc) return rc;
-        } else if (lat_.active) {  // ... and the lateral plan's
-            const int rc = lateral_plan_batch();
+        } else if (StagedPlan* p = staged()) {  // ... or as many captures as an accumulating plan's stage has free slots, folded first when it has none
+            const int rc = staged_plan_batch(*p);
             if (rc) return rc;
         }
         uint64_t batch = plan_batch(n_steps - completed);
@@ -403,11 +379,7 @@ int Engine<Real>::run(uint64_t n_steps, uint64_t* done, int32_t* flag_out) {
         uint64_t good = 0;
         if ((rc = commit_batch(batch, flags_host_, &good, &flag))) return rc;
         if (snap_.active && good < batch) snapshot_discard_after(steps_done);  // (a flag stopped the run before those steps)
-        if (decay_.active) decay_.st.commit(steps_done);
-        if (inten_.active) inten_.st.commit(steps_done);
-        if (arr_.active) arr_.st.commit(steps_done);
-        if (lat_.active) lat_.st.commit(steps_done);
-        if (spec_.active) spec_.st.commit(steps_done);  // the batch's captures of completed steps stay staged, the others are dropped
+        if (StagedPlan* p = staged()) p->st.commit(steps_done);  // the batch's captures of completed steps stay staged, the others are dropped
         completed += good;
     }
     // on return every snapshot of a completed step can be fetched
@@ -492,59 +464,24 @@ int Engine<Real>::query(int what, uint64_t* value) {
         case WV_QUERY_DIRECTIONAL_LAUNCHES: *value = dir_.launches; return WV_OK;
         case WV_QUERY_SPECTRUM_CAPTURES: *value = spec_.st.captures(); return WV_OK;
         case WV_QUERY_SPECTRUM_FOLDS: *value = spec_.folds; return WV_OK;
-        case WV_QUERY_SPECTRUM_NS: {
-            DeviceGuard guard(device_);
-            for (int b = 0; b < 2; ++b) {
-                const int rc = spectrum_drain_timing(b);
-                if (rc) return rc;
-            }
-            *value = (uint64_t)(spec_.kernel_ms * 1e6 + 0.5);
-            return WV_OK;
-        }
         case WV_QUERY_DECAY_CAPTURES: *value = decay_.st.captures(); return WV_OK;
         case WV_QUERY_DECAY_FOLDS: *value = decay_.folds; return WV_OK;
-        case WV_QUERY_DECAY_NS: {
-            DeviceGuard guard(device_);
-            for (int b = 0; b < 2; ++b) {
-                const int rc = decay_drain_timing(b);
-                if (rc) return rc;
-            }
-            *value = (uint64_t)(decay_.kernel_ms * 1e6 + 0.5);
-            return WV_OK;
-        }
         case WV_QUERY_INTENSITY_CAPTURES: *value = inten_.st.captures(); return WV_OK;
         case WV_QUERY_INTENSITY_FOLDS: *value = inten_.folds; return WV_OK;
-        case WV_QUERY_INTENSITY_NS:
-        case WV_QUERY_INTENSITY_GATHER_NS:
-        case WV_QUERY_INTENSITY_GATHERS: {
-            DeviceGuard guard(device_);
-            const int rc = intensity_drain_timing();
-            if (rc) return rc;
-            *value = what == WV_QUERY_INTENSITY_GATHERS ? inten_.gathers_timed
-                                                        : (uint64_t)((what == WV_QUERY_INTENSITY_NS ? inten_.kernel_ms : inten_.gather_ms) * 1e6 + 0.5);
-            return WV_OK;
-        }
         case WV_QUERY_ARRIVAL_CAPTURES: *value = arr_.st.captures(); return WV_OK;
         case WV_QUERY_ARRIVAL_FOLDS: *value = arr_.folds; return WV_OK;
-        case WV_QUERY_ARRIVAL_NS: {
-            DeviceGuard guard(device_);
-            const int rc = arrival_drain_timing();
-            if (rc) return rc;
-            *value = (uint64_t)(arr_.kernel_ms * 1e6 + 0.5);
-            return WV_OK;
-        }
         case WV_QUERY_LATERAL_CAPTURES: *value = lat_.st.captures(); return WV_OK;
         case WV_QUERY_LATERAL_FOLDS: *value = lat_.folds; return WV_OK;
-        case WV_QUERY_LATERAL_NS:
-        case WV_QUERY_LATERAL_GATHER_NS:
-        case WV_QUERY_LATERAL_GATHERS: {
-            DeviceGuard guard(device_);
-            const int rc = lateral_drain_timing();
-            if (rc) return rc;
-            *value = what == WV_QUERY_LATERAL_GATHERS ? lat_.gathers_timed
-                                                      : (uint64_t)((what == WV_QUERY_LATERAL_NS ? lat_.kernel_ms : lat_.gather_ms) * 1e6 + 0.5);
-            return WV_OK;
-        }
+        // (a plan's kernel times, once its timed folds and captures have run: engine_staged.hip.h)
+        case WV_QUERY_SPECTRUM_NS: return staged_time_query(spec_, PlanTime::folds_ns, value);
+        case WV_QUERY_DECAY_NS: return staged_time_query(decay_, PlanTime::folds_ns, value);
+        case WV_QUERY_INTENSITY_NS: return staged_time_query(inten_, PlanTime::folds_ns, value);
+        case WV_QUERY_INTENSITY_GATHER_NS: return staged_time_query(inten_, PlanTime::gathers_ns, value);
+        case WV_QUERY_INTENSITY_GATHERS: return staged_time_query(inten_, PlanTime::gathers, value);
+        case WV_QUERY_ARRIVAL_NS: return staged_time_query(arr_, PlanTime::folds_ns, value);
+        case WV_QUERY_LATERAL_NS: return staged_time_query(lat_, PlanTime::folds_ns, value);
+        case WV_QUERY_LATERAL_GATHER_NS: return staged_time_query(lat_, PlanTime::gathers_ns, value);
+        case WV_QUERY_LATERAL_GATHERS: return staged_time_query(lat_, PlanTime::gathers, value);
         default: return fail(WV_E_INVALID_ARGUMENT, "unknown query");
     }
 }

@@ -352,13 +352,7 @@ int Engine<Real>::checkpoint(int op) {
         }
         if (ckpt_.fmem) (void)hipFree(ckpt_.fmem);
         if (ckpt_.dir_velocity) (void)hipFree(ckpt_.dir_velocity);
-        if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
-        if (ckpt_.decay_bins) (void)hipFree(ckpt_.decay_bins);
-        if (ckpt_.decay_state) (void)hipFree(ckpt_.decay_state);
-        if (ckpt_.inten_bins) (void)hipFree(ckpt_.inten_bins);
-        if (ckpt_.inten_velocity) (void)hipFree(ckpt_.inten_velocity);
-        if (ckpt_.arr_state) (void)hipFree(ckpt_.arr_state);
-        if (ckpt_.lat_state) (void)hipFree(ckpt_.lat_state);
+        ckpt_.free_plans();
         ckpt_ = Checkpoint{};
         return WV_OK;
     }
@@ -396,36 +390,13 @@ int Engine<Real>::checkpoint(int op) {
             }
             ckpt_.dir_n = dir_.n;
         }
-        // the spectrum plan's sums and count (engine_spectrum.hip.h): their copy is allocated by the first checkpoint under the plan
-        if (spec_.active) {
-            const int rc = spectrum_checkpoint();
+        // an accumulating plan's state blocks, count and next plan step (engine_staged.hip.h): their copies are allocated by the first
+        // checkpoint under the plan; which plan of each kind the checkpoint saw
+        if (StagedPlan* p = staged()) {
+            const int rc = staged_checkpoint(*p);
             if (rc) return rc;
         }
-        ckpt_.spec_generation = spec_.generation;
-        // the decay plan's bins, count and next plan step (engine_decay.hip.h): likewise
-        if (decay_.active) {
-            const int rc = decay_checkpoint();
-            if (rc) return rc;
-        }
-        ckpt_.decay_generation = decay_.generation;
-        // the intensity plan's bins and velocities, count and next plan step (engine_intensity.hip.h): likewise
-        if (inten_.active) {
-            const int rc = intensity_checkpoint();
-            if (rc) return rc;
-        }
-        ckpt_.inten_generation = inten_.generation;
-        // the arrival plan's per-node state, count and next plan step (engine_arrival.hip.h): likewise
-        if (arr_.active) {
-            const int rc = arrival_checkpoint();
-            if (rc) return rc;
-        }
-        ckpt_.arr_generation = arr_.generation;
-        // the lateral plan's per-node state, count and next plan step (engine_lateral.hip.h): likewise
-        if (lat_.active) {
-            const int rc = lateral_checkpoint();
-            if (rc) return rc;
-        }
-        ckpt_.lat_generation = lat_.generation;
+        for (int kind = 0; kind < kPlanKinds; ++kind) ckpt_.plan[kind].generation = staged_[kind]->generation;
         WV_HIP(hipMemcpyAsync(ckpt_.field[0], field_[cur_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.field[1], field_[prv_], field_bytes_, hipMemcpyDeviceToDevice, stream_));
         WV_HIP(hipMemcpyAsync(ckpt_.fmem, fmem_, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
@@ -452,37 +423,14 @@ int Engine<Real>::checkpoint(int op) {
         return fail(WV_E_STATE, "wv_rollback: the receivers were changed after the checkpoint");
     if (signal_pos_ < ckpt_.signal_pos)
         return fail(WV_E_STATE, "wv_rollback: the source was changed after the checkpoint");
-    if (spec_.active && ckpt_.spec_generation != spec_.generation)
-        return fail(WV_E_STATE, "wv_rollback: the spectrum plan was set after the checkpoint (its sums have no copy to go back to)");
-    if (decay_.active && ckpt_.decay_generation != decay_.generation)
-        return fail(WV_E_STATE, "wv_rollback: the decay plan was set after the checkpoint (its bins have no copy to go back to)");
-    if (inten_.active && ckpt_.inten_generation != inten_.generation)
-        return fail(WV_E_STATE, "wv_rollback: the intensity plan was set after the checkpoint (its bins have no copy to go back to)");
-    if (arr_.active && ckpt_.arr_generation != arr_.generation)
-        return fail(WV_E_STATE, "wv_rollback: the arrival plan was set after the checkpoint (its state has no copy to go back to)");
-    if (lat_.active && ckpt_.lat_generation != lat_.generation)
-        return fail(WV_E_STATE, "wv_rollback: the lateral plan was set after the checkpoint (its state has no copy to go back to)");
+    StagedPlan* const p = staged();
+    if (p && ckpt_.plan[p->kind].generation != p->generation)
+        return fail(WV_E_STATE, std::string("wv_rollback: the ") + p->name + " plan was set after the checkpoint (" + p->lost + " no copy to go back to)");
     WV_HIP(hipMemcpyAsync(field_[cur_], ckpt_.field[0], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(field_[prv_], ckpt_.field[1], field_bytes_, hipMemcpyDeviceToDevice, stream_));
     WV_HIP(hipMemcpyAsync(fmem_, ckpt_.fmem, fmem_bytes, hipMemcpyDeviceToDevice, stream_));
-    if (spec_.active) {  // sums and count back; what is staged is of abandoned steps
-        const int rc = spectrum_rollback();
-        if (rc) return rc;
-    }
-    if (decay_.active) {  // bins and count back; what is staged is of abandoned steps
-        const int rc = decay_rollback();
-        if (rc) return rc;
-    }
-    if (inten_.active) {  // bins, velocities and count back; what is staged is of abandoned steps
-        const int rc = intensity_rollback();
-        if (rc) return rc;
-    }
-    if (arr_.active) {  // onsets, peaks, sums and count back; what is staged is of abandoned steps
-        const int rc = arrival_rollback();
-        if (rc) return rc;
-    }
-    if (lat_.active) {  // onsets, velocities, sums and count back; what is staged is of abandoned steps
-        const int rc = lateral_rollback();
+    if (p) {  // state and count back; what is staged is of abandoned steps
+        const int rc = staged_rollback(*p);
         if (rc) return rc;
     }
     if (dir_.active) {

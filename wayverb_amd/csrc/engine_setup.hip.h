@@ -543,18 +543,8 @@ void Engine<Real>::release() {
     comm_.reset();
     if (stream_) (void)hipStreamSynchronize(stream_);
     snapshot_release(snap_);
-    spectrum_release(spec_);
-    if (ckpt_.spec_acc) (void)hipFree(ckpt_.spec_acc);
-    decay_release(decay_);
-    intensity_release(inten_);
-    arrival_release(arr_);
-    lateral_release(lat_);
-    if (ckpt_.lat_state) (void)hipFree(ckpt_.lat_state);
-    if (ckpt_.arr_state) (void)hipFree(ckpt_.arr_state);
-    if (ckpt_.inten_bins) (void)hipFree(ckpt_.inten_bins);
-    if (ckpt_.inten_velocity) (void)hipFree(ckpt_.inten_velocity);
-    if (ckpt_.decay_bins) (void)hipFree(ckpt_.decay_bins);
-    if (ckpt_.decay_state) (void)hipFree(ckpt_.decay_state);
+    if (StagedPlan* p = staged()) staged_release(*p);  // (a plan that is not active holds nothing)
+    ckpt_.free_plans();
     for (auto& e : events_) (void)hipEventDestroy(e);
     events_.clear();
     for (auto& e : halo_events_)

@@ -43,16 +43,9 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
         ++snap_.generation;
         return WV_OK;
     }
-    // A slab of a chain would have to cut its batches where its neighbours do, and each rank holds only its part of a box: out of
-    // scope (as for wv_checkpoint), refused rather than half done.
-    if (opt_.ghost_lo || opt_.ghost_hi || (comm_ && comm_->nranks() > 1))
-        return fail(WV_E_STATE, "wv_set_snapshots: not on a slab of a chain (one domain only)");
-    // (a spectrum plan cuts the passes at its own steps: one consumer of capture steps at a time, engine_spectrum.hip.h)
-    if (spec_.active) return fail(WV_E_STATE, "wv_set_snapshots: a spectrum plan is active (wv_set_spectrum(e, NULL, NULL) stops it); the two plans exclude each other");
-    if (decay_.active) return fail(WV_E_STATE, "wv_set_snapshots: a decay plan is active (wv_set_decay(e, NULL) stops it); the plans exclude each other");
-    if (inten_.active) return fail(WV_E_STATE, "wv_set_snapshots: an intensity plan is active (wv_set_intensity(e, NULL) stops it); the plans exclude each other");
-    if (arr_.active) return fail(WV_E_STATE, "wv_set_snapshots: an arrival plan is active (wv_set_arrival(e, NULL, NULL) stops it); the plans exclude each other");
-    if (lat_.active) return fail(WV_E_STATE, "wv_set_snapshots: a lateral plan is active (wv_set_lateral(e, NULL, NULL) stops it); the plans exclude each other");
+    // (a slab of a chain would have to cut its batches where its neighbours do, and each rank holds only its part of a box: out of
+    // scope, as for wv_checkpoint; an accumulating plan cuts the passes at its own steps: engine_staged.hip.h)
+    if (const int rc = plan_refused("wv_set_snapshots", kSnapshotRow)) return rc;
     wv::SnapshotBox box;
     box.x0 = plan->x0, box.y0 = plan->y0, box.z0 = plan->z0;
     box.nx = plan->nx, box.ny = plan->ny, box.nz = plan->nz;
@@ -102,8 +95,8 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
 }
 
 // snapshot_gather_kernel on the compute stream: `box` of the field `current` -> the dense floats at `dst` (`wide`: four nodes per
-// lane, snapshot_kernels.hip.h).  The one launch site of the kernel: a snapshot plan's captures, a spectrum plan's
-// (engine_spectrum.hip.h) and a decay plan's (engine_decay.hip.h) are the same launch.
+// lane, snapshot_kernels.hip.h).  The one launch site of the kernel: a snapshot plan's captures and a spectrum, a decay and
+// an arrival plan's (engine_staged.hip.h: staged_capture) are the same launch.
 template <typename Real>
 int Engine<Real>::launch_snapshot_gather(const wv::SnapshotBox& box, bool wide, float* dst) {
     wv::SnapshotArgs<Real> a{};
@@ -127,7 +120,7 @@ int Engine<Real>::launch_snapshot_gather(const wv::SnapshotBox& box, bool wide, 
 
 // intensity_gather_kernel (intensity_kernels.hip.h) on the compute stream: per node of `box` the pressure and the three float
 // differences of its neighbours' gradients, from the field `current` -> the four dense planes at `dst`.  The one launch site of that
-// kernel (an intensity plan's capture, engine_intensity.hip.h); the box keeps clear of the mesh's faces (intensity_plan.h).
+// kernel (an intensity and a lateral plan's capture, engine_staged.hip.h: staged_capture); the box keeps clear of the mesh's faces (intensity_plan.h).
 template <typename Real>
 int Engine<Real>::launch_intensity_gather(const wv::SnapshotBox& box, double spacing, float* dst) {
     wv::IntensityGatherArgs<Real> a{};

@@ -6,7 +6,7 @@
 //
 // The stage holds kSpectrumStage captures as dense float boxes.  A batch's captures go behind the ones already staged and
 // stay there until commit_batch has said how many of the batch's steps were good; the fold takes all that are staged in one
-// launch and is due only when the stage has no slot left for the next batch (engine_spectrum.hip.h).
+// launch and is due only when the stage has no slot left for the next batch (engine_staged.hip.h).
 // tests/cpp/spectrum_plan_test.cpp covers this file on the CPU.
 #pragma once
 #include <cstdint>
