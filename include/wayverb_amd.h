@@ -711,6 +711,79 @@ int wv_lateral_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
 int wv_fetch_lateral(wv_engine* e, uint32_t* onset, double* pre, double* velocity /* [3][nz][ny][nx] */,
                      double* bins /* [10][n_bins][nz][ny][nx] */, uint64_t* captures);
 
+/* ---- modulation maps: per-band modulation transfer function of a box, on the device ------------- */
+/* How well speech is understood at a seat is the speech transmission index (STI, IEC 60268-16).  Its indirect method derives STI from
+ * an impulse response through Schroeder's modulation transfer function, per octave band k and modulation frequency F:
+ *     m_k(F) = | sum_t h_k(t)^2 e^(-2 pi i F t) | / sum_t h_k(t)^2
+ * with h_k the response filtered into band k.  A decay plan's bins lose the phase this needs, a spectrum plan transforms p and not the
+ * band-filtered p^2, and snapshots at period 1 cross the link at 4 bytes per node and step.  A modulation plan has the engine capture
+ * the box as a snapshot plan would and keep, per node taken and per band, ON THE DEVICE: the energy and the running Fourier sums of the
+ * band-filtered, squared captures at n_freqs modulation frequencies.  8 n_bands (1 + 2 n_freqs) bytes per node cross the link when the
+ * caller fetches them, however long the run.  wayverb_amd/modulation.py turns them into the MTF and the STI.
+ *
+ * Definition.  p_j is the snapshot float of committed capture j (the snapshot block above), n_j its plan step, and x = (double)p_j.
+ * For band k the sections s = 0 .. n_sections - 1 run in series on the node's own state z1[k][s], z2[k][s], which starts at +0.0;
+ * every product and sum is rounded on its own, nothing is contracted, in wv_set_decay_bands' association:
+ *     out = x * b0 + z1
+ *     z1  = (x * b1 - a1 * out) + z2
+ *     z2  = x * b2 - a2 * out
+ *     x   = out                                                     (into the next section)
+ * and with y = x after the last section, in capture order, the sums starting at +0.0:
+ *     e        = y * y                                              (rounded)
+ *     E[k]     = E[k] + e
+ *     (c, s)   = wv_spectrum_twiddle(f_m, n_j)                      m = 0 .. n_freqs - 1, f_m in cycles per STEP, 0 <= f_m <= 0.5
+ *     Re[k][m] = Re[k][m] + e * c                                   (the product is rounded, then the sum)
+ *     Im[k][m] = Im[k][m] - e * s
+ * The twiddles are the spectrum plan's, made on the host by the same exported function: the device evaluates no trigonometric
+ * function.  A loop over the snapshots of the same plan that evaluates these lines on float64 arrays with the twiddles of
+ * wv_spectrum_twiddle (wayverb_amd/modulation.py: modulation_fold) reproduces E, Re and Im BIT FOR BIT; the filter states are
+ * reproduced with them, implicitly: mid-run fetches and checkpoints carry them.
+ *
+ *   - 1 <= n_bands <= 8, 1 <= n_sections <= 4, 1 <= n_freqs <= 16, every coefficient finite; otherwise, and for a NaN or a frequency
+ *     outside [0, 0.5], a box that leaves the mesh, a zero stride or a zero period: WV_E_INVALID_ARGUMENT
+ *   - everything is allocated when the plan is set: the stage (64 bytes per node), 8 n_bands (1 + 2 n_freqs) bytes of sums and
+ *     16 n_sections n_bands bytes of filter state per node, the coefficient table and the two twiddle tables.  With no room the call
+ *     answers WV_E_HIP and leaves the engine and any earlier plan untouched.  A new plan replaces the old one and forgets its sums; a
+ *     NULL plan stops, forgets and frees (as does wv_destroy)
+ *   - box, stride and cadence are the decay plan's; one domain only: a slab of a chain answers WV_E_STATE, and wv_run_group refuses
+ *     an engine with a plan
+ *   - a modulation plan excludes every other plan -- snapshot, spectrum, both kinds of decay plan, intensity, arrival, lateral: every
+ *     setter answers WV_E_STATE while another plan is active, and wv_last_error names the plan to stop
+ *   - after a run that stopped on a flag at step f (an overflow, or keep_going cleared) sums and filter states hold exactly the
+ *     captures of steps <= f: a continued run goes on as if the dropped captures had never been taken
+ *   - wv_step / wv_swap capture nothing; the plan steps they pass are gaps in the series
+ *   - wv_checkpoint folds what is staged and copies sums AND filter states, the capture count and the next plan step aside (the copy
+ *     is allocated by the first checkpoint taken under a plan: WV_E_HIP, engine untouched, when there is no room); wv_rollback puts
+ *     them back, and the re-run is bitwise the same.  A plan set AFTER the checkpoint makes wv_rollback answer WV_E_STATE
+ *   - wv_fetch_modulation may be called any time outside wv_run; it folds what is staged and leaves the plan running, so fetching
+ *     twice during a long run gives two consistent partial sums
+ *   - with no plan nothing is launched, allocated or waited for; with one the fields, receiver rows and flags are bit-identical to
+ *     a run without
+ *
+ * What the caller owns.  The series the filters see is sampled at sample_rate / period: design the sections for THAT rate.  With
+ * period > 1 field content above sample_rate / (2 period) aliases into the bands, so an impulse source needs period = 1, while a
+ * source band-limited below sample_rate / 6 can run at period = 3 and keep three-step passes.  The modulation frequencies are in
+ * cycles per STEP whatever the period: F hertz is F / sample_rate.  Auditory masking, the reception threshold and noise need absolute
+ * levels and are not part of this: it is the level-independent indirect method.
+ *
+ * wv_modulation_count: as wv_decay_count.  wv_fetch_modulation: energy is float64 [n_bands][nz][ny][nx], sums is complex128
+ * [n_bands][n_freqs][nz][ny][nx] (re, im interleaved); EITHER destination may be NULL and is then skipped; *captures (may be NULL) =
+ * how many captures they hold. */
+typedef struct wv_modulation_plan {
+    int32_t x0, y0, z0;    /* first node of the box */
+    int32_t nx, ny, nz;    /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;    /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step;   /* captures at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;       /* >= 1 */
+    uint32_t n_freqs;      /* M, 1 .. 16 */
+    uint32_t reserved;
+} wv_modulation_plan;
+int wv_set_modulation(wv_engine* e, const wv_modulation_plan* plan, const double* cycles_per_step /* [n_freqs] */,
+                      const wv_biquad* sections /* [n_bands][n_sections] */, uint32_t n_bands, uint32_t n_sections);
+int wv_modulation_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
+int wv_fetch_modulation(wv_engine* e, double* energy /* [n_bands][nz][ny][nx] */,
+                        double* sums /* [n_bands][n_freqs][nz][ny][nx][2]: complex128 */, uint64_t* captures);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */
@@ -753,7 +826,8 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *                            timing on, and how many of them that is
  *   WV_QUERY_ARRIVAL_CAPTURES, WV_QUERY_ARRIVAL_FOLDS, WV_QUERY_ARRIVAL_NS   the decay plan's three since wv_set_arrival
  *   WV_QUERY_LATERAL_CAPTURES, WV_QUERY_LATERAL_FOLDS, WV_QUERY_LATERAL_NS, WV_QUERY_LATERAL_GATHER_NS, WV_QUERY_LATERAL_GATHERS
- *                            the intensity plan's five since wv_set_lateral */
+ *                            the intensity plan's five since wv_set_lateral
+ *   WV_QUERY_MODULATION_CAPTURES, WV_QUERY_MODULATION_FOLDS, WV_QUERY_MODULATION_NS   the decay plan's three since wv_set_modulation */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -776,7 +850,8 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
        WV_QUERY_INTENSITY_GATHER_NS = 35, WV_QUERY_INTENSITY_GATHERS = 36,
        WV_QUERY_ARRIVAL_CAPTURES = 37, WV_QUERY_ARRIVAL_FOLDS = 38, WV_QUERY_ARRIVAL_NS = 39,
        WV_QUERY_LATERAL_CAPTURES = 40, WV_QUERY_LATERAL_FOLDS = 41, WV_QUERY_LATERAL_NS = 42,
-       WV_QUERY_LATERAL_GATHER_NS = 43, WV_QUERY_LATERAL_GATHERS = 44 };
+       WV_QUERY_LATERAL_GATHER_NS = 43, WV_QUERY_LATERAL_GATHERS = 44,
+       WV_QUERY_MODULATION_CAPTURES = 45, WV_QUERY_MODULATION_FOLDS = 46, WV_QUERY_MODULATION_NS = 47 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

@@ -109,6 +109,20 @@ def main():
     ap.add_argument("--lateral-out", default="lateral.npz",
                     help="the maps go here: lf, diffuseness [ny, nx], direct_direction, lateral_axis [3, ny, nx], onset, pre [ny, nx], "
                          "velocity [3, ny, nx], bins [10, 3, ny, nx], edges, captures, period, sample_rate, plane, origin, spacing")
+    ap.add_argument("--modulation-map", nargs="?", const="", default=None, metavar="z=METRES",
+                    help="keep, per node of one horizontal plane (default: the receiver's height) and on the device, the energy of "
+                         "octave bands and the Fourier sums of their squared signal at the 14 modulation frequencies of IEC 60268-16 "
+                         "(Engine.set_modulation; single-band runs, no other plan): the modulation transfer function and the "
+                         "modulation transfer index per band, and with --sti-rest the speech transmission index")
+    ap.add_argument("--modulation-bands", default="125,250,500", metavar="HZ,HZ,...",
+                    help="octave centres the mesh carries (default 125,250,500; up to 8); their upper edges belong below a quarter of the sample rate")
+    ap.add_argument("--modulation-every", type=int, default=1, help="capture every N-th step (the band filters then run at sample rate / N)")
+    ap.add_argument("--sti-rest", default=None, metavar="HZ:MTI,...",
+                    help="the modulation transfer index of the octave bands the mesh does not carry, from a geometric method or a "
+                         "measurement, e.g. 1000:0.55,2000:0.5,4000:0.5,8000:0.45; with all seven bands known the file holds sti")
+    ap.add_argument("--modulation-out", default="modulation.npz",
+                    help="the maps go here: mtf [K, 14, ny, nx], mti [K, ny, nx], sti [ny, nx] (with --sti-rest), energy, bands_hz, "
+                         "freqs_hz, captures, period, sample_rate, plane, origin, spacing")
     args = ap.parse_args()
 
     bands = None
@@ -240,11 +254,28 @@ def main():
             ap.error("--lateral-every must be >= 1 and --lateral-threshold >= 0 and finite")
         lateral = dict(plane=float(args.lateral_plane[2:]) if args.lateral_plane else args.receiver[2], every=args.lateral_every,
                        threshold=args.lateral_threshold, edges_ms=(0.0, 5.0, 80.0))
+    modulation = None
+    if args.modulation_map is not None:
+        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None or lateral is not None:
+            ap.error("--modulation-map: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map, --clarity-map or --lateral-map")
+        if args.modulation_map and not args.modulation_map.startswith("z="):
+            ap.error("--modulation-map takes z=<metres>")
+        try:
+            modulation_centres = [float(c) for c in args.modulation_bands.split(",")]
+            sti_rest = {float(item.split(":")[0]): float(item.split(":")[1]) for item in args.sti_rest.split(",")} if args.sti_rest else None
+        except (ValueError, IndexError):
+            ap.error("--modulation-bands takes octave centres in Hz, e.g. 125,250,500, and --sti-rest HZ:MTI pairs, e.g. 1000:0.55,2000:0.5")
+        if not 1 <= len(modulation_centres) <= 8 or any(not c > 0 for c in modulation_centres) or args.modulation_every < 1:
+            ap.error("--modulation-bands: 1 .. 8 positive centre frequencies; --modulation-every must be >= 1")
+        modulation = dict(plane=float(args.modulation_map[2:]) if args.modulation_map else args.receiver[2], every=args.modulation_every,
+                          bands_hz=modulation_centres)
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
     if len(receivers) > 1:
-        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None or lateral is not None:
-            ap.error("several --receiver: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map, --clarity-map or --lateral-map")
+        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None or lateral is not None or \
+                modulation is not None:
+            ap.error("several --receiver: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map, --clarity-map, --lateral-map "
+                     "or --modulation-map")
         audios, per, positions, vm = W.impulse_responses(v, t, absorptions, args.source, receivers, args.cutoff, args.usable_portion,
                                                          args.seconds, args.rate, method=method, pointing=args.pointing,
                                                          shape=args.mic_shape or 0.0, precision=args.precision)
@@ -260,6 +291,8 @@ def main():
         return
     if bands and (intensity is not None or arrival is not None or lateral is not None):
         ap.error("--intensity-map, --clarity-map, --lateral-map: single-band runs only")
+    if bands and modulation is not None:
+        ap.error("--modulation-map: single-band runs only")
     if bands:   # multiple_band_constant_spacing: one run per band with flat per-band walls
         env = W.Environment()
         vm = W.compute_voxels_and_mesh(v, t, absorptions, args.receiver,
@@ -272,7 +305,33 @@ def main():
                                        args.usable_portion, args.seconds, args.rate, method=method,
                                        pointing=args.pointing, shape=args.mic_shape or 0.0,
                                        precision=args.precision, snapshots=snapshots, spectrum=spectrum, decay=decay, intensity=intensity,
-                                       arrival=arrival, lateral=lateral)
+                                       arrival=arrival, lateral=lateral, modulation=modulation)
+        if modulation is not None:
+            import warnings
+            from wayverb_amd import modulation as MOD
+            env, mesh = W.Environment(), audio_etc[2].mesh
+            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")   # (canonical has said it already)
+                plan = W.modulation_plan_arguments(modulation, mesh, rate)
+            (energy, sums), captures = audio_etc[3]
+            energy, sums = energy[:, 0], sums[:, :, 0]   # the one plane: [K, ny, nx], [K, M, ny, nx]
+            transfer = MOD.mtf(energy, sums)
+            index = MOD.mti(transfer)
+            extra = {}
+            carried = {int(round(c)): index[k] for k, c in enumerate(modulation_centres)}
+            if sti_rest is not None and all(c in carried or c in {int(round(r)) for r in sti_rest} for c in MOD.STI_OCTAVE_HZ):
+                extra["sti"] = MOD.sti(carried, rest=sti_rest)
+            elif sti_rest is not None:
+                print("warning: --sti-rest and --modulation-bands leave octave bands of 125 Hz .. 8 kHz out: no sti is written", file=sys.stderr)
+            np.savez(args.modulation_out, mtf=transfer, mti=index, energy=energy, bands_hz=np.array(modulation_centres),
+                     freqs_hz=np.array(MOD.STI_MODULATION_HZ), captures=captures, period=plan["period"], sample_rate=rate,
+                     plane=plan["box"][0][2], spacing=mesh.spacing,
+                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64), **extra)
+            print("wrote modulation maps of plane z=%d (%d bands, %d captures; median MTI per band %s%s) to %s"
+                  % (plan["box"][0][2], len(modulation_centres), captures,
+                     ", ".join("%.3f" % np.nanmedian(m) if np.isfinite(m).any() else "not defined" for m in index),
+                     "; median STI %.3f" % np.nanmedian(extra["sti"]) if "sti" in extra and np.isfinite(extra["sti"]).any() else "", args.modulation_out))
         if lateral is not None:
             from wayverb_amd import lateral as L
             env, mesh = W.Environment(), audio_etc[2].mesh

@@ -20,6 +20,7 @@
 #include "engine_intensity.hip.h"
 #include "engine_arrival.hip.h"
 #include "engine_lateral.hip.h"
+#include "engine_modulation.hip.h"
 #include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
@@ -290,6 +291,19 @@ int wv_lateral_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
 int wv_fetch_lateral(wv_engine* e, uint32_t* onset, double* pre, double* velocity, double* bins, uint64_t* captures) {
     WV_NEED(e);
     return e->fetch_lateral(onset, pre, velocity, bins, captures);
+}
+int wv_set_modulation(wv_engine* e, const wv_modulation_plan* plan, const double* cycles_per_step, const wv_biquad* sections, uint32_t n_bands,
+                      uint32_t n_sections) {
+    WV_NEED(e);
+    return e->set_modulation(plan, cycles_per_step, sections, n_bands, n_sections);
+}
+int wv_modulation_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
+    WV_NEED(e);
+    return e->modulation_count(captures, last_step);
+}
+int wv_fetch_modulation(wv_engine* e, double* energy, double* sums, uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_modulation(energy, sums, captures);
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

@@ -17,10 +17,10 @@
 //                        receivers
 //   engine_snapshot.hip.h  field snapshots taken on the device while a run goes on (wv_set_snapshots): plan, ring, capture, copy stream, held log
 //   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape
-//   engine_staged.hip.h  the life cycle the five accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release
+//   engine_staged.hip.h  the life cycle the six accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release
 //   engine_spectrum.hip.h  field spectra accumulated on the device while a run goes on (wv_set_spectrum): plan, stage, fold, fetch
 //   spectrum_plan.h      (host only, no HIP) free slots of the stage, when a fold is due, which captures survive a stop, sizes
-//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the five accumulating plans
+//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the six accumulating plans
 //   engine_decay.hip.h   time-binned field energy accumulated on the device while a run goes on (wv_set_decay): plan, stage, fold, fetch
 //   decay_plan.h         (host only, no HIP) the bin of a capture, sizes, the fold's traffic model
 //   decay_bands_kernels.hip.h   the fold of a band-limited decay plan (wv_set_decay_bands): biquad cascades ahead of the square
@@ -33,6 +33,9 @@
 //   engine_lateral.hip.h  p^2, p v and v v^T of a box binned from each node's OWN arrival (wv_set_lateral): plan, stage, fold, fetch
 //   lateral_plan.h       (host only, no HIP) what a lateral plan is refused for, sizes and places, the fold's traffic model
 //   lateral_kernels.hip.h     its fold: arrival_fold_kernel's onset and bin around intensity_fold_kernel's integrator
+//   engine_modulation.hip.h  band energies and their Fourier sums at modulation frequencies of a box (wv_set_modulation): plan, stage, fold, fetch
+//   modulation_plan.h    (host only, no HIP) what a modulation plan is refused for, sizes and places, the fold's traffic model
+//   modulation_kernels.hip.h  its fold: decay_bands_fold_kernel's cascade ahead of spectrum_fold_kernel's running Fourier sum
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -45,6 +48,7 @@
 #include "intensity_plan.h"
 #include "arrival_plan.h"
 #include "lateral_plan.h"
+#include "modulation_plan.h"
 #include "capture_stage.h"
 
 #include "boundary_kernels.hip.h"
@@ -58,6 +62,7 @@
 #include "intensity_kernels.hip.h"
 #include "arrival_kernels.hip.h"
 #include "lateral_kernels.hip.h"
+#include "modulation_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -224,6 +229,11 @@ public:
     int lateral_count(uint64_t* captures, uint64_t* last_step) override;
     int fetch_lateral(uint32_t* onset, double* pre, double* velocity, double* bins, uint64_t* captures) override;
     bool lateral_active() const override { return lat_.active; }
+    // ---- engine_modulation.hip.h
+    int set_modulation(const wv_modulation_plan* plan, const double* cycles_per_step, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) override;
+    int modulation_count(uint64_t* captures, uint64_t* last_step) override;
+    int fetch_modulation(double* energy, double* sums, uint64_t* captures) override;
+    bool modulation_active() const override { return mod_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -430,8 +440,8 @@ private:
     void directional_release();
     int directional_enqueue(uint64_t batch);
     std::unique_ptr<wv::SlabComm> comm_;
-    // the five plans that accumulate on the device (engine_staged.hip.h)
-    enum PlanKind { kSpectrumPlan, kDecayPlan, kIntensityPlan, kArrivalPlan, kLateralPlan, kPlanKinds };
+    // the six plans that accumulate on the device (engine_staged.hip.h)
+    enum PlanKind { kSpectrumPlan, kDecayPlan, kIntensityPlan, kArrivalPlan, kLateralPlan, kModulationPlan, kPlanKinds };
     static constexpr int kPlanBlocks = 2;  // device blocks of accumulated state a plan has at the most
     // wv_checkpoint / wv_rollback (engine_io.hip.h): device copies of the two live fields and the filter memories, and the
     // host-side position that goes with them
@@ -504,8 +514,8 @@ private:
     int snapshot_plan_batch();
     int snapshot_begin_run();
     void snapshot_rollback(uint64_t to_step);
-    // ---- engine_staged.hip.h: the five plans that accumulate on the device -- spectrum, decay (plain and banded), intensity, arrival,
-    // lateral -- have ONE life cycle: captures into a device-only stage on the compute stream, committed batch by batch, folded into the
+    // ---- engine_staged.hip.h: the six plans that accumulate on the device -- spectrum, decay (plain and banded), intensity, arrival,
+    // lateral, modulation -- have ONE life cycle: captures into a device-only stage on the compute stream, committed batch by batch, folded into the
     // plan's accumulated state in one launch when the stage has no slot left, on fetch and on checkpoint.  StagedPlan holds what they
     // share; a plan's own struct adds its wv_*_plan, its tables and what its fold kernel needs
     struct StagedPlan {
@@ -617,14 +627,31 @@ private:
         void free_own();
     } lat_;
     int lateral_enqueue(Lateral& d, int b, int t, unsigned blocks);
+    // modulation maps (engine_modulation.hip.h): per band the energy and the Fourier sums of the band-filtered, squared captures at M
+    // modulation frequencies, and the filter states beside them; the coefficient table and two twiddle tables (page-locked, and their
+    // device copies) the host writes in turn, as the spectrum plan's
+    struct Modulation : StagedPlan {
+        Modulation()
+            : StagedPlan(kModulationPlan, "modulation", "wv_set_modulation", "its sums have", "the modulation plan's sums", "the modulation plan's filter states", true, false) {}
+        wv_modulation_plan plan{};
+        std::vector<double> freqs;      // cycles per step, [M]
+        double* sums() const { return reinterpret_cast<double*>(this->block[0]); }   // [n_bands][1 + 2 M][B]: E, then Re, Im per frequency
+        double* state() const { return reinterpret_cast<double*>(this->block[1]); }  // [n_bands][n_sections][2][B]: z1, z2 of every section
+        uint32_t n_bands = 0, n_sections = 0;
+        double* coef = nullptr;         // [n_bands][n_sections][5] on the device
+        double* tw_host[2] = {nullptr, nullptr};
+        double* tw_dev[2] = {nullptr, nullptr};
+        void free_own();
+    } mod_;
+    int modulation_enqueue(Modulation& d, int b, int t, unsigned blocks);
     // ---- engine_staged.hip.h: one copy of each step of the life cycle
-    StagedPlan* const staged_[kPlanKinds] = {&spec_, &decay_, &inten_, &arr_, &lat_};  // by PlanKind
-    StagedPlan* staged() const {  // the active one of the five, or null: they exclude each other (and a snapshot plan)
+    StagedPlan* const staged_[kPlanKinds] = {&spec_, &decay_, &inten_, &arr_, &lat_, &mod_};  // by PlanKind
+    StagedPlan* staged() const {  // the active one of the six, or null: they exclude each other (and a snapshot plan)
         for (StagedPlan* p : staged_)
             if (p->active) return p;
         return nullptr;
     }
-    enum PlanRow { kSnapshotRow, kSpectrumRow, kBandedDecayRow, kPlainDecayRow, kIntensityRow, kArrivalRow, kLateralRow };
+    enum PlanRow { kSnapshotRow, kSpectrumRow, kBandedDecayRow, kPlainDecayRow, kIntensityRow, kArrivalRow, kLateralRow, kModulationRow };
     int plan_refused(const std::string& setter, PlanRow self);
     template <typename Plan>
     static void plan_release(Plan& p);

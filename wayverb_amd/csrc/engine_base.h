@@ -116,6 +116,10 @@ struct wv_engine {
     virtual int lateral_count(uint64_t* captures, uint64_t* last_step) = 0;
     virtual int fetch_lateral(uint32_t* onset, double* pre, double* velocity, double* bins, uint64_t* captures) = 0;
     virtual bool lateral_active() const = 0;
+    virtual int set_modulation(const wv_modulation_plan* plan, const double* cycles_per_step, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) = 0;
+    virtual int modulation_count(uint64_t* captures, uint64_t* last_step) = 0;
+    virtual int fetch_modulation(double* energy, double* sums, uint64_t* captures) = 0;
+    virtual bool modulation_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;
     virtual int set_source(int kind, uint64_t node, const double* signal, uint64_t n) = 0;

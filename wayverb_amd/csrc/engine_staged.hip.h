@@ -1,6 +1,6 @@
-// engine_staged.hip.h -- the life cycle of the five plans that accumulate on the device while wv_run keeps going: field spectra
+// engine_staged.hip.h -- the life cycle of the six plans that accumulate on the device while wv_run keeps going: field spectra
 // (engine_spectrum.hip.h), energy decay maps plain and banded (engine_decay.hip.h), intensity maps (engine_intensity.hip.h),
-// arrival-aligned energy maps (engine_arrival.hip.h) and lateral maps (engine_lateral.hip.h).  One copy of each step; what a plan's own
+// arrival-aligned energy maps (engine_arrival.hip.h), lateral maps (engine_lateral.hip.h) and modulation maps (engine_modulation.hip.h).  One copy of each step; what a plan's own
 // file keeps is its setter's validation, sizes and first contents, the enqueue step of its fold and its fetch.
 //
 // Part of the engine behind the C ABI of include/wayverb_amd.h (engine.hip is the translation unit; see engine.hip.h for the class).
@@ -24,7 +24,8 @@
 
 namespace wv {
 
-static_assert(kDecayStage == kSpectrumStage && kIntensityStage == kSpectrumStage && kArrivalStage == kSpectrumStage && kLateralStage == kSpectrumStage,
+static_assert(kDecayStage == kSpectrumStage && kIntensityStage == kSpectrumStage && kArrivalStage == kSpectrumStage && kLateralStage == kSpectrumStage &&
+                      kModulationStage == kSpectrumStage,
               "every plan stages its captures by spectrum_plan.h's rules (capture_stage.h)");
 
 // What every plan's setter, wv_set_snapshots included, refuses a plan for before it looks at it: a slab of a chain (it would have to cut
@@ -45,6 +46,7 @@ int Engine<Real>::plan_refused(const std::string& setter, PlanRow self) {
         {kIntensityRow, inten_.active, "an intensity plan is active (wv_set_intensity(e, NULL) stops it); the plans exclude each other"},
         {kArrivalRow, arr_.active, "an arrival plan is active (wv_set_arrival(e, NULL, NULL) stops it); the plans exclude each other"},
         {kLateralRow, lat_.active, "a lateral plan is active (wv_set_lateral(e, NULL, NULL) stops it); the plans exclude each other"},
+        {kModulationRow, mod_.active, "a modulation plan is active (wv_set_modulation(e, NULL, NULL, NULL, 0, 0) stops it); the plans exclude each other"},
     };
     for (const auto& r : rows)
         if (r.active && r.row != self) return fail(WV_E_STATE, setter + ": " + r.sentence);
@@ -79,7 +81,8 @@ void Engine<Real>::staged_release(StagedPlan& p) {
         case kDecayPlan: plan_release(static_cast<Decay&>(p)); break;
         case kIntensityPlan: plan_release(static_cast<Intensity&>(p)); break;
         case kArrivalPlan: plan_release(static_cast<Arrival&>(p)); break;
-        default: plan_release(static_cast<Lateral&>(p)); break;
+        case kLateralPlan: plan_release(static_cast<Lateral&>(p)); break;
+        default: plan_release(static_cast<Modulation&>(p)); break;
     }
 }
 
@@ -209,7 +212,8 @@ int Engine<Real>::staged_enqueue(StagedPlan& p, int b, int t, unsigned blocks) {
         case kDecayPlan: return decay_enqueue(static_cast<Decay&>(p), b, t, blocks);
         case kIntensityPlan: return intensity_enqueue(static_cast<Intensity&>(p), b, t, blocks);
         case kArrivalPlan: return arrival_enqueue(static_cast<Arrival&>(p), b, t, blocks);
-        default: return lateral_enqueue(static_cast<Lateral&>(p), b, t, blocks);
+        case kLateralPlan: return lateral_enqueue(static_cast<Lateral&>(p), b, t, blocks);
+        default: return modulation_enqueue(static_cast<Modulation&>(p), b, t, blocks);
     }
 }
 

@@ -43,6 +43,7 @@ EXPORTS = [
     "wv_set_intensity", "wv_intensity_count", "wv_fetch_intensity", "wv_fetch_intensity_velocity", "wv_fetch_directional_velocity",
     "wv_set_arrival", "wv_arrival_count", "wv_fetch_arrival",
     "wv_set_lateral", "wv_lateral_count", "wv_fetch_lateral",
+    "wv_set_modulation", "wv_modulation_count", "wv_fetch_modulation",
 ]
 
 
@@ -111,6 +112,12 @@ class WvLateralPlan(C.Structure):
     the 8 bin edges in captures behind a node's onset, then the three arguments of the reference's directional_receiver constructor."""
     _fields_ = WvDecayPlan._fields_[:11] + [("n_bins", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 8),
                                             ("spacing", C.c_double), ("sample_rate", C.c_double), ("ambient_density", C.c_double)]
+
+
+class WvModulationPlan(C.Structure):
+    """wv_modulation_plan (include/wayverb_amd.h): the spectrum plan's fields -- box, strides, cadence, the number of modulation
+    frequencies."""
+    _fields_ = WvSpectrumPlan._fields_
 
 
 ARRIVAL_NONE = 0xFFFFFFFF   # onset / peak_capture of a node that has none yet
@@ -239,6 +246,9 @@ def load_library():
     lib.wv_set_lateral.argtypes = [C.c_void_p, C.POINTER(WvLateralPlan), C.c_void_p]
     lib.wv_lateral_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.wv_fetch_lateral.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.POINTER(C.c_uint64)]
+    lib.wv_set_modulation.argtypes = [C.c_void_p, C.POINTER(WvModulationPlan), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.wv_modulation_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.wv_fetch_modulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.wv_biquad_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.wv_butterworth_bandpass.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.wv_bandpass_biquad.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
@@ -430,6 +440,7 @@ class Engine:
         self.intensity_shape = None
         self.arrival_shape = None
         self.lateral_shape = None
+        self.modulation_shape = None
 
     @classmethod
     def from_handle(cls, handle, mesh, precision):
@@ -449,6 +460,7 @@ class Engine:
         eng.intensity_shape = None
         eng.arrival_shape = None
         eng.lateral_shape = None
+        eng.modulation_shape = None
         return eng
 
     def close(self):
@@ -863,6 +875,46 @@ class Engine:
         _check(self.lib.wv_fetch_lateral(self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in ("onset", "pre", "velocity", "bins")], C.byref(captures)))
         return out, captures.value
 
+    # ---- modulation maps accumulated on the device while wv_run goes on ------------------------------
+    def set_modulation(self, freqs, bands, box="mesh", stride=1, first_step=0, period=1):
+        """wv_set_modulation.  `freqs`: M <= 16 modulation frequencies in CYCLES PER STEP, 0 .. 0.5 (modulation.cycles_per_step turns
+        hertz into them); `bands`: float64[K][S][5], K <= 8 cascades of S <= 4 biquad sections (wayverb_amd.decay designs them, for the
+        rate of the CAPTURED series: the mesh's rate / period); `box`, `stride`, `first_step`, `period` as for set_snapshots.  At every
+        plan step the engine captures the box as a snapshot would, runs every node's capture through each cascade, squares it and adds
+        the square to the band's energy and, times the twiddles spectrum_twiddle gives, to a running Fourier sum per modulation
+        frequency -- modulation.modulation_fold over the snapshots of the same plan reproduces all of it bit for bit.  Excludes every
+        other plan.  set_modulation(None, None) stops and forgets.  Returns the shape (K, M, nz, ny, nx)."""
+        if freqs is None:
+            _check(self.lib.wv_set_modulation(self.h, None, None, None, 0, 0))
+            self.modulation_shape = None
+            return None
+        f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        sections = np.ascontiguousarray(bands, dtype=np.float64)
+        if sections.ndim != 3 or sections.shape[2] != 5:
+            raise ValueError("set_modulation: bands is float64[K][S][5], got shape %r" % (sections.shape,))
+        plan = WvModulationPlan()
+        taken = self._fill_box(plan, box, stride)
+        plan.first_step, plan.period, plan.n_freqs = int(first_step), int(period), f.shape[0]
+        _check(self.lib.wv_set_modulation(self.h, C.byref(plan), f.ctypes.data_as(C.c_void_p), sections.ctypes.data_as(C.c_void_p), sections.shape[0],
+                                          sections.shape[1]))
+        self.modulation_shape = (sections.shape[0], f.shape[0], taken[2], taken[1], taken[0])
+        return self.modulation_shape
+
+    def modulation_count(self):
+        """wv_modulation_count: (captures of completed steps since the plan was set, the step of the last of them)."""
+        captures, last = C.c_uint64(), C.c_uint64()
+        _check(self.lib.wv_modulation_count(self.h, C.byref(captures), C.byref(last)))
+        return captures.value, last.value
+
+    def fetch_modulation(self):
+        """wv_fetch_modulation: (energy float64[K, nz, ny, nx], sums complex128[K, M, nz, ny, nx]).  They hold every capture
+        modulation_count counts.  The plan keeps running."""
+        shape = tuple(getattr(self, "modulation_shape", None) or (0, 0, 0, 0, 0))   # (no plan: the library says so)
+        energy = np.zeros(shape[:1] + shape[2:], dtype=np.float64)
+        sums = np.zeros(shape, dtype=np.complex128)
+        _check(self.lib.wv_fetch_modulation(self.h, energy.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p), None))
+        return energy, sums
+
     def step_count(self):
         s = C.c_uint64()
         _check(self.lib.wv_step_count(self.h, C.byref(s)))
@@ -898,6 +950,7 @@ class Engine:
     QUERY_INTENSITY_CAPTURES, QUERY_INTENSITY_FOLDS, QUERY_INTENSITY_NS, QUERY_INTENSITY_GATHER_NS, QUERY_INTENSITY_GATHERS = 32, 33, 34, 35, 36
     QUERY_ARRIVAL_CAPTURES, QUERY_ARRIVAL_FOLDS, QUERY_ARRIVAL_NS = 37, 38, 39
     QUERY_LATERAL_CAPTURES, QUERY_LATERAL_FOLDS, QUERY_LATERAL_NS, QUERY_LATERAL_GATHER_NS, QUERY_LATERAL_GATHERS = 40, 41, 42, 43, 44
+    QUERY_MODULATION_CAPTURES, QUERY_MODULATION_FOLDS, QUERY_MODULATION_NS = 45, 46, 47
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

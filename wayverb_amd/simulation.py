@@ -189,9 +189,51 @@ def lateral_plan_arguments(lateral, mesh, sample_rate, environment):
                 period=every, spacing=mesh.spacing, sample_rate=sample_rate / every, ambient_density=environment.ambient_density)
 
 
+def modulation_plan_arguments(modulation, mesh, sample_rate):
+    """canonical's `modulation` dict -> keyword arguments of Engine.set_modulation: dict(plane=z in metres | box=((x0, y0, z0), extent),
+    stride=1, every=1, bands_hz=(125, 250, 500), freqs_hz=modulation.STI_MODULATION_HZ, first_step=0).  `plane`: that whole horizontal
+    plane.  The octave bands around `bands_hz` (decay.octave_band_edges) get a 4th-order Butterworth band-pass each, designed at the rate
+    of the CAPTURED series, sample_rate / every (decay.butterworth_bandpass, which refuses a band at or above that series' Nyquist
+    rate); the modulation frequencies become cycles per step of the mesh.  A band whose upper edge lies above a quarter of the sample
+    rate, where the waveguide is not trusted, or above the captured series' Nyquist rate, where it aliases, is warned about."""
+    import warnings
+    from . import decay as D
+    from . import modulation as MOD
+    unknown = set(modulation) - {"plane", "box", "stride", "every", "bands_hz", "freqs_hz", "first_step"}
+    if unknown or ("plane" in modulation) == ("box" in modulation):
+        raise ValueError("modulation=dict(plane=<z in metres> or box=..., every=, bands_hz=, freqs_hz=, stride=, first_step=)")
+    every = int(modulation.get("every", 1))
+    if every < 1:
+        raise ValueError("modulation: every must be >= 1")
+    centres = [float(c) for c in np.atleast_1d(modulation.get("bands_hz", (125, 250, 500)))]
+    freqs_hz = np.atleast_1d(np.asarray(modulation.get("freqs_hz", MOD.STI_MODULATION_HZ), dtype=np.float64))
+    if not 1 <= len(centres) <= 8 or any(not c > 0 for c in centres):
+        raise ValueError("modulation: bands_hz holds 1 .. 8 positive octave centres")
+    if not 1 <= freqs_hz.shape[0] <= 16:
+        raise ValueError("modulation: freqs_hz holds 1 .. 16 modulation frequencies")
+    if "plane" in modulation:
+        plane = int(round((float(modulation["plane"]) - mesh.min_corner[2]) / mesh.spacing))
+        if not 0 <= plane <= mesh.dims[2] - 1:
+            raise ValueError("modulation: plane z=%g m is outside the mesh" % float(modulation["plane"]))
+        box = ((0, 0, plane), (None, None, 1))
+    else:
+        box = modulation["box"]
+    series_rate = sample_rate / every
+    edges = D.octave_band_edges(centres)
+    for c, (lo, hi) in zip(centres, edges):
+        if hi > 0.25 * sample_rate:
+            warnings.warn("modulation: the %g Hz band reaches %.1f Hz, above a quarter of the sample rate (%.1f Hz): the waveguide is not "
+                          "trusted there" % (c, hi, 0.25 * sample_rate))
+        if hi > 0.5 * series_rate:
+            warnings.warn("modulation: the %g Hz band reaches %.1f Hz, above the Nyquist rate of the captured series (%.1f Hz with "
+                          "every=%d): it aliases" % (c, hi, 0.5 * series_rate, every))
+    return dict(freqs=MOD.cycles_per_step(freqs_hz, sample_rate), bands=np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in edges]),
+                box=box, stride=modulation.get("stride", 1), first_step=int(modulation.get("first_step", 0)), period=every)
+
+
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
               device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None, decay=None, intensity=None,
-              arrival=None, lateral=None):
+              arrival=None, lateral=None, modulation=None):
     """canonical (single band): hard source at `source`, directional receiver at `receiver`, for
     ceil(sample_rate * simulation_time) steps.  Returns [(directional records, sample_rate,
     (0, cutoff))] -- the bandpass_band list waveguide::postprocess takes -- or None when stopped early.
@@ -228,7 +270,15 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     runs the directional receiver's integrator at every node of that plane or box and keeps, on the device and in bins counted from
     the node's OWN arrival, the squared pressure, the intensity and the second moments of the particle velocity (Engine.set_lateral);
     the return value is then (bands, (dict(onset, pre, velocity, bins), captures)), which wayverb_amd.lateral turns into the early
-    lateral energy fraction, the direct sound's direction and the diffuseness.  One domain only, and not together with another plan."""
+    lateral energy fraction, the direct sound's direction and the diffuseness.  One domain only, and not together with another plan.
+    `modulation`: dict(plane=<z in metres> or box=..., every=, bands_hz=(125, 250, 500), freqs_hz=STI_MODULATION_HZ)
+    (modulation_plan_arguments) -- the engine runs every node's captures through an octave band-pass per band and keeps, on the device,
+    the band's energy and the Fourier sums of the squared output at the modulation frequencies (Engine.set_modulation); the return
+    value is then (bands, ((energy float64[K, nz, ny, nx], sums complex128[K, M, nz, ny, nx]), captures)), which wayverb_amd.modulation
+    turns into the modulation transfer function and the speech transmission index.  One domain only, and not together with another
+    plan."""
+    if modulation is not None and slabs > 1:
+        raise ValueError("modulation maps are accumulated on one domain only (slabs=1)")
     if lateral is not None and slabs > 1:
         raise ValueError("lateral maps are accumulated on one domain only (slabs=1)")
     if arrival is not None and slabs > 1:
@@ -253,6 +303,7 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     intensity_plan = intensity_plan_arguments(intensity, mesh, sample_rate, environment, simulation_time) if intensity is not None else None
     arrival_plan = arrival_plan_arguments(arrival, mesh, sample_rate) if arrival is not None else None
     lateral_plan = lateral_plan_arguments(lateral, mesh, sample_rate, environment) if lateral is not None else None
+    modulation_plan = modulation_plan_arguments(modulation, mesh, sample_rate) if modulation is not None else None
 
     def mesh_index(pt):
         idx = vm.compute_index(pt)
@@ -287,6 +338,8 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 eng.set_arrival(**arrival_plan)
             if lateral_plan is not None:
                 eng.set_lateral(**lateral_plan)
+            if modulation_plan is not None:
+                eng.set_modulation(**modulation_plan)
             done, traces = E.run_fast(eng, E.SOURCE_HARD, mesh_index(source), signal, [receiver_index] + list(neighbours),
                                       keep_going=keep_going)
             taken = eng.fetch_snapshots() if snapshots is not None else None
@@ -300,13 +353,15 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 taken = eng.fetch_arrival()
             if lateral_plan is not None:
                 taken = eng.fetch_lateral()
+            if modulation_plan is not None:
+                taken = (eng.fetch_modulation(), eng.modulation_count()[0])
         finally:
             eng.close()
     if done != ideal_steps:
         return None
     directional = P.directional_receiver(traces, mesh.spacing, sample_rate, environment.ambient_density)
     bands = [(directional, sample_rate, (0.0, float(cutoff)))]
-    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None and lateral is None:
+    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None and lateral is None and modulation is None:
         return bands
     return bands, taken
 
@@ -429,7 +484,7 @@ def canonical_multiband(vm, source, receiver, environment, bands, cutoff, usable
 def impulse_response(vertices, triangles, surface_absorptions, source, receiver, cutoff=200.0, usable_portion=0.6,
                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
                      pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None, decay=None,
-                     intensity=None, arrival=None, lateral=None):
+                     intensity=None, arrival=None, lateral=None, modulation=None):
     """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio.
     `snapshots`: a function mesh -> keyword arguments of Engine.set_snapshots (the mesh's size is not known before it is built),
     or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member.
@@ -437,13 +492,14 @@ def impulse_response(vertices, triangles, surface_absorptions, source, receiver,
     `decay`: a function (mesh, sample_rate) -> canonical's `decay` dict, or the dict; the fourth member is then (bins, captures).
     `intensity`: canonical's `intensity` dict; the fourth member is then (bins [4, n_bins, nz, ny, nx], captures).
     `arrival`: canonical's `arrival` dict; the fourth member is then (dict(onset, peak, peak_capture, pre, moment, bins), captures).
-    `lateral`: canonical's `lateral` dict; the fourth member is then (dict(onset, pre, velocity, bins), captures)."""
+    `lateral`: canonical's `lateral` dict; the fourth member is then (dict(onset, pre, velocity, bins), captures).
+    `modulation`: canonical's `modulation` dict; the fourth member is then ((energy, sums), captures)."""
     environment = environment or Environment()
     vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
     if spectrum is not None and snapshots is not None:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
-    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None and lateral is None:
+    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None and lateral is None and modulation is None:
         bands = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device)
         taken = None
     else:
@@ -460,6 +516,8 @@ def impulse_response(vertices, triangles, surface_absorptions, source, receiver,
             plans["arrival"] = arrival
         if lateral is not None:
             plans["lateral"] = lateral
+        if modulation is not None:
+            plans["modulation"] = modulation
         both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, **plans)
         if both is None:
             raise RuntimeError("the waveguide run was stopped early")
