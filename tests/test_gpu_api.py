@@ -360,3 +360,68 @@ def test_checkpoint_and_rollback_reproduce_the_abandoned_steps(built_library, pr
         eng.close()
     finally:
         set_tuning()
+
+
+def test_rollback_refuses_a_source_or_receivers_set_after_the_checkpoint(built_library):
+    """include/wayverb_amd.h: "The source and the receivers must be the ones in place at the checkpoint (WV_E_STATE otherwise)" --
+    ANY call of their setters since, however many steps have run behind it.  (wv_rollback used to compare the position in the signal
+    and the receivers' first step and number: a source set after the checkpoint was rolled back silently as soon as as many steps
+    had run under it as before the checkpoint -- at once after a checkpoint at step 0 -- and the run went on with the NEW signal from
+    the OLD position; receivers replaced at the checkpoint's own step by as many others likewise.)  A refusal changes nothing, and a
+    new checkpoint takes the source and receivers then in place."""
+    mesh = M.box_mesh(12, 10, 9)
+    src, other = mesh.compute_index(5, 5, 4), mesh.compute_index(6, 4, 4)
+    recv = [mesh.compute_index(7, 5, 4)]
+    sig = np.random.default_rng(3).uniform(-1, 1, 64)
+    source_changed = "error -6: wv_rollback: the source was changed after the checkpoint"
+    receivers_changed = "error -6: wv_rollback: the receivers were changed after the checkpoint"
+    eng = E.Engine(mesh, precision="f32")
+    try:
+        eng.set_source(E.SOURCE_HARD, src, sig)
+        eng.set_receivers(recv)
+        assert eng.run_steps(5) == (5, 0)
+        eng.checkpoint()
+        eng.set_source(E.SOURCE_SOFT, other, -sig)
+        with pytest.raises(E.WaveguideError, match=source_changed):      # fewer steps under the new source than before the checkpoint
+            eng.rollback()
+        assert eng.run_steps(5) == (5, 0)
+        with pytest.raises(E.WaveguideError, match=source_changed):      # as many
+            eng.rollback()
+        assert eng.run_steps(3) == (3, 0)
+        before = (eng.step_count(), eng.read_field(E.BUF_CURRENT).tobytes(), eng.read_field(E.BUF_PREVIOUS).tobytes())
+        with pytest.raises(E.WaveguideError, match=source_changed):      # more
+            eng.rollback()
+        assert before == (13, eng.read_field(E.BUF_CURRENT).tobytes(), eng.read_field(E.BUF_PREVIOUS).tobytes()) and eng.step_count() == 13
+        eng.set_source(E.SOURCE_HARD, src, sig)                           # the same source again is still another call
+        with pytest.raises(E.WaveguideError, match=source_changed):
+            eng.rollback()
+        eng.checkpoint()                                                  # ... which a new checkpoint takes as it is
+        assert eng.run_steps(4) == (4, 0)
+        eng.rollback()
+        assert eng.step_count() == 13
+        eng.set_receivers([other])
+        with pytest.raises(E.WaveguideError, match=receivers_changed):
+            eng.rollback()
+        eng.checkpoint()
+        eng.set_receivers(recv)                                           # the checkpoint's step, as many receivers: only the call tells
+        with pytest.raises(E.WaveguideError, match=receivers_changed):
+            eng.rollback()
+        assert eng.run_steps(2) == (2, 0)
+        with pytest.raises(E.WaveguideError, match=receivers_changed):
+            eng.rollback()
+        eng.checkpoint()
+        assert eng.run_steps(2) == (2, 0)
+        eng.rollback()
+        assert eng.step_count() == 15
+    finally:
+        eng.close()
+    # a checkpoint at step 0: the new source's position is never below the checkpoint's
+    eng = E.Engine(mesh, precision="f64")
+    try:
+        eng.set_source(E.SOURCE_HARD, src, sig)
+        eng.checkpoint()
+        eng.set_source(E.SOURCE_HARD, other, sig)
+        with pytest.raises(E.WaveguideError, match=source_changed):
+            eng.rollback()
+    finally:
+        eng.close()

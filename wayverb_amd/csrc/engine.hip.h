@@ -327,6 +327,7 @@ private:
     uint64_t whole_steps_ = 0;                        // steps taken as one launch (WV_QUERY_WHOLE_STEPS)
     uint64_t graph_whole_steps_ = 0;                  // ... by one replay of the captured batch
     uint64_t io_generation_ = 0;                      // bumped by set_source / set_receivers (GraphKey)
+    uint64_t source_generation_ = 0, recv_generation_ = 0;  // bumped by set_source / by set_columns (a checkpoint remembers which it saw)
     bool pair_list_early_ok_ = false;             // ensure_pair
     bool pair_unit_waves_ = false;                // the unit list carries each unit's live waves (build_pair_units)
     bool pair_mid_done_ = false, pair_list_done_ = false;  // part A of the pass in flight has served t+1's source / receivers, the list
@@ -450,6 +451,7 @@ private:
         double* fmem = nullptr;
         bool valid = false;
         uint64_t steps_done = 0, signal_pos = 0, recv_first_step = 0;
+        uint64_t source_generation = 0, recv_generation = 0;  // the source and the receivers in place at the save
         size_t recv_log_size = 0;
         uint32_t n_recv = 0;
         int outside_dirty = 0;

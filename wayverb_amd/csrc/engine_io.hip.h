@@ -36,6 +36,7 @@ int Engine<Real>::set_source(int kind, uint64_t node, const double* signal, uint
     io_unfaced_known_ = io_xclear_known_ = false;
     duties_known_ = false;
     ++io_generation_;
+    ++source_generation_;
     if (kind == WV_SOURCE_NONE) return WV_OK;
     source_node_ = stored_index(node);
     // a source in an outside node keeps writing non-zero values there: no work lists then
@@ -84,6 +85,7 @@ int Engine<Real>::set_columns(const uint64_t* nodes, uint32_t n) {
     io_unfaced_known_ = io_xclear_known_ = false;
     duties_known_ = false;
     ++io_generation_;
+    ++recv_generation_;
     return WV_OK;
 }
 
@@ -406,6 +408,8 @@ int Engine<Real>::checkpoint(int op) {
         ckpt_.dir_generation = dir_.generation;
         ckpt_.steps_done = steps_done;
         ckpt_.signal_pos = signal_pos_;
+        ckpt_.source_generation = source_generation_;
+        ckpt_.recv_generation = recv_generation_;
         ckpt_.recv_first_step = recv_first_step_;
         ckpt_.recv_log_size = recv_log_.size();
         ckpt_.n_recv = n_recv_;
@@ -418,10 +422,12 @@ int Engine<Real>::checkpoint(int op) {
     }
     if (op != 1) return fail(WV_E_INVALID_ARGUMENT, "unknown checkpoint operation");
     if (!ckpt_.valid) return fail(WV_E_STATE, "wv_rollback: no checkpoint has been taken");
-    if (ckpt_.recv_first_step != recv_first_step_ || ckpt_.n_recv != n_recv_ || recv_log_.size() < ckpt_.recv_log_size ||
-        ckpt_.dir_generation != dir_.generation || dir_.log.size() < ckpt_.dir_log_size)
+    // the source and the receivers must be the ones in place at the checkpoint: ANY call of their setters since, whatever it set and
+    // however many steps have run behind it (a position in the signal or a log's length says nothing: both grow back)
+    if (ckpt_.recv_generation != recv_generation_ || ckpt_.recv_first_step != recv_first_step_ || ckpt_.n_recv != n_recv_ ||
+        recv_log_.size() < ckpt_.recv_log_size || ckpt_.dir_generation != dir_.generation || dir_.log.size() < ckpt_.dir_log_size)
         return fail(WV_E_STATE, "wv_rollback: the receivers were changed after the checkpoint");
-    if (signal_pos_ < ckpt_.signal_pos)
+    if (ckpt_.source_generation != source_generation_ || signal_pos_ < ckpt_.signal_pos)
         return fail(WV_E_STATE, "wv_rollback: the source was changed after the checkpoint");
     StagedPlan* const p = staged();
     if (p && ckpt_.plan[p->kind].generation != p->generation)
