@@ -2,6 +2,9 @@
 // runs this).  Every expectation below is derived by hand from the contract in include/wayverb_amd.h, none recorded from the code.
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
+#include <limits>
+#include <string>
 #include <vector>
 
 #include "snapshot_plan.h"
@@ -152,6 +155,68 @@ int main() {
     CHECK(snapshot_bytes(box(0, 0, 7, 512, 512, 1)) == (1u << 20));            // a 512^2 plane: 1 MiB
     CHECK(snapshot_bytes(box(0, 0, 0, 2048, 2048, 2048)) == (32ull << 30));  // no 32-bit overflow
     CHECK(snapshot_elements(box(0, 0, 0, 0, 3, 2)) == 0);
+
+    // ---- what every setter checks (plan_refusal): the first of the four shared refusals, with the setter's name; asked in parts by the
+    // setters that have checks of their own between them
+    {
+        struct Plan {
+            int32_t x0, y0, z0, nx, ny, nz, sx, sy, sz;
+            uint64_t first_step, period;
+        };
+        static const PlanSentences says = WV_PLAN_SENTENCES("wv_set_thing");
+        const Plan good{1, 2, 3, 4, 3, 2, 2, 1, 3, 0, 1};
+        const SnapshotBox b = plan_box(good);
+        CHECK(b.x0 == 1 && b.y0 == 2 && b.z0 == 3 && b.nx == 4 && b.ny == 3 && b.nz == 2 && b.sx == 2 && b.sy == 1 && b.sz == 3);
+        CHECK(plan_refusal(good, 8, 5, 7, says) == nullptr);
+        const std::string strides = "wv_set_thing: strides must be >= 1", period = "wv_set_thing: period must be >= 1",
+                          leaves = "wv_set_thing: the box leaves the mesh", plane = "wv_set_thing: more than 2^31 nodes per plane of the box";
+        Plan p = good;
+        p.sy = 0, p.period = 0, p.nx = 5;                                   // three faults: the first in the setters' order is said
+        CHECK(plan_refusal(p, 8, 5, 7, says) == strides);
+        CHECK(plan_refusal(p, 8, 5, 7, says, kPlanPeriod) == period);
+        CHECK(plan_refusal(p, 8, 5, 7, says, kPlanLeavesMesh, kPlanLeavesMesh) == leaves);
+        CHECK(plan_refusal(p, 8, 5, 7, says, kPlanStrides, kPlanStrides) == strides);
+        p = good, p.sz = -1;
+        CHECK(plan_refusal(p, 8, 5, 7, says) == strides);
+        p = good, p.period = 0;
+        CHECK(plan_refusal(p, 8, 5, 7, says) == period && plan_refusal(p, 8, 5, 7, says, kPlanLeavesMesh) == nullptr);
+        p = good, p.nz = 3;                                                 // 3 + 2 * 3 = 9 > 6
+        CHECK(plan_refusal(p, 8, 5, 7, says) == leaves && plan_refusal(p, 8, 5, 10, says) == nullptr);
+        // a plane of 2^31 nodes is refused, one of 2^31 - 65536 is not: no mesh that fits a device reaches this, so it is held here
+        const Plan wide{0, 0, 0, 65536, 32768, 1, 1, 1, 1, 0, 1};
+        CHECK(plan_refusal(wide, 65536, 32768, 1, says) == plane);
+        CHECK(plan_refusal(wide, 65536, 32768, 1, says, kPlanStrides, kPlanLeavesMesh) == nullptr);
+        CHECK(plan_refusal(wide, 65536, 32768, 1, says, kPlanPlaneSize, kPlanPlaneSize) == plane);
+        p = wide, p.ny = 32767;
+        CHECK(plan_refusal(p, 65536, 32768, 1, says) == nullptr);
+        p = wide, p.nx = 65537;                                             // leaves the mesh AND too large a plane: the former is said
+        CHECK(plan_refusal(p, 65536, 32768, 1, says) == leaves);
+        CHECK(gather_wide(box(4, 1, 0, 8, 3, 2)) && !gather_wide(box(2, 0, 0, 8, 3, 2)) && !gather_wide(box(4, 0, 0, 6, 3, 2)) && !gather_wide(box(4, 0, 0, 8, 3, 2, 2)));
+    }
+    // ---- the checks more than one setter has
+    {
+        const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN(), big = std::numeric_limits<double>::max();
+        CHECK(frequency_valid(0.0) && frequency_valid(-0.0) && frequency_valid(0.5) && !frequency_valid(0.5000000000000001) && !frequency_valid(-1e-300));
+        CHECK(!frequency_valid(nan) && !frequency_valid(inf) && !frequency_valid(-inf));
+        CHECK(physical_constants_valid(0.01, 44100.0, 1.2) && physical_constants_valid(big, 5e-324, 1.0));
+        for (int which = 0; which < 3; ++which)
+            for (double bad : {0.0, -0.0, -1.0, inf, -inf, nan}) {
+                double v[3] = {0.01, 44100.0, 1.2};
+                v[which] = bad;
+                CHECK(!physical_constants_valid(v[0], v[1], v[2]));
+            }
+        struct Biquad {
+            double b0, b1, b2, a1, a2;
+        };
+        Biquad sections[3] = {{1, 2, 3, 4, 5}, {big, -big, 0, -0.0, 5e-324}, {1, 1, 1, 1, 1}};
+        CHECK(biquads_finite(sections, 3) && biquads_finite(sections, 0));
+        for (int field = 0; field < 5; ++field)
+            for (double bad : {inf, -inf, nan}) {
+                Biquad s2[3] = {sections[0], sections[1], sections[2]};
+                (&s2[2].b0)[field] = bad;
+                CHECK(!biquads_finite(s2, 3) && biquads_finite(s2, 2));
+            }
+    }
 
     if (g_failures) {
         std::printf("%d check(s) failed\n", g_failures);

@@ -15,9 +15,8 @@
 // The product of two converted floats is exact in double, so every line rounds once and a NumPy loop over the snapshots
 // (wayverb_amd/arrival.py: arrival_fold) reproduces all of it bit for bit.  This is decay_fold_kernel's fold with a bin that differs
 // from lane to lane:
-//   - lanes run along the dense node index; a lane reads its t staged floats once (the j loop is unrolled over the T slots behind a
-//     wave-uniform `j < t`), loads its state, walks the captures in order and stores what changed.  No LDS, no atomics, no scratch;
-//     the tail of B is a bounds check on the lane
+//   - lanes run along the dense node index; a lane reads its t staged floats once (fold_parts.hip.h: stage_read; the onset rule is
+//     its onset_update), loads its state, walks the captures in order and stores what changed; the tail of B is a bounds check on the lane
 //   - the edge table and `first` are kernel ARGUMENTS (the table by value): they live in the kernel argument segment, every index into
 //     the table is a loop counter (arrival_plan.h: arrival_bin counts the edges at or below rel), so the compiler fetches them through
 //     the scalar path and keeps them in scalar registers; nothing is indexed by a lane's value, so nothing goes to scratch
@@ -34,6 +33,7 @@
 #include <cstdint>
 
 #include "arrival_plan.h"
+#include "fold_parts.hip.h"
 
 namespace wv {
 
@@ -51,10 +51,8 @@ __global__ void __launch_bounds__(256)
                         const uint32_t first, const uint64_t nodes, const int32_t t) {
     const uint64_t node = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (node >= nodes || t < 1) return;
-    float p[kArrivalStage];
-#pragma unroll
-    for (int j = 0; j < kArrivalStage; ++j)
-        if (j < t) p[j] = stage[(uint64_t)j * nodes + node];
+    float p[kArrivalStage][1];
+    stage_read(stage, nodes, node, t, p);
     const float thr = threshold_map ? threshold_map[node] : threshold;
     const uint32_t onset_was = onset[node];
     const uint32_t peak_capture_was = peak_capture[node];
@@ -68,13 +66,13 @@ __global__ void __launch_bounds__(256)
     for (int j = 0; j < kArrivalStage; ++j) {
         if (j < t) {
             const uint32_t c = first + (uint32_t)j;  // (no lane in it)
-            const float a = __builtin_fabsf(p[j]);
+            const float a = __builtin_fabsf(p[j][0]);
             if (a > pk) {  // strict: the first occurrence; false for a NaN
                 pk = a;
                 pc = c;
             }
-            if (on == kArrivalNone && a >= thr) on = c;
-            const double sq = (double)p[j] * (double)p[j];
+            on = onset_update(on, a, thr, c, kArrivalNone);
+            const double sq = (double)p[j][0] * (double)p[j][0];
             if (on == kArrivalNone) {
                 pr = pr + sq;
             } else {

@@ -15,7 +15,7 @@
 //   state  double[n_bands][S][2][B]       z1, z2 of every section, planar: a wave reads and writes 512 contiguous bytes per plane
 //   bins   double[n_bands][n_bins][B]     planar, as the plain plan's
 //
-// A lane reads its t staged floats once (unrolled over the T slots behind the wave-uniform `j < t`), loads its 2 S state doubles,
+// A lane reads its t staged floats once (fold_parts.hip.h: stage_read), loads its 2 S state doubles,
 // walks the captures in order through the sections with ONE bin accumulator (store and reload when bin[j] changes), and stores the
 // state and the held bin.  S is a template parameter and the section loop is unrolled, so the state stays in registers.  No LDS, no
 // atomics, no scratch; the tail of B is a bounds check on the lane.  One node per lane: with up to 8 bands the grid is already 8 times
@@ -28,6 +28,7 @@
 
 #include <cstdint>
 
+#include "fold_parts.hip.h"
 #include "decay_plan.h"
 
 namespace wv {
@@ -43,10 +44,8 @@ __global__ void __launch_bounds__(256) decay_bands_fold_kernel(const float* __re
     const uint64_t node = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (node >= nodes || t < 1) return;
     const uint32_t band = blockIdx.y;
-    float p[kDecayStage];
-#pragma unroll
-    for (int j = 0; j < kDecayStage; ++j)
-        if (j < t) p[j] = stage[(uint64_t)j * nodes + node];
+    float p[kDecayStage][1];
+    stage_read(stage, nodes, node, t, p);
     const double* c = coef + (uint64_t)band * (S * 5);
     double b0[S], b1[S], b2[S], a1[S], a2[S];
 #pragma unroll
@@ -67,7 +66,7 @@ __global__ void __launch_bounds__(256) decay_bands_fold_kernel(const float* __re
                 held = b;
                 e = planes[(uint64_t)held * nodes];
             }
-            double x = (double)p[j];
+            double x = (double)p[j][0];
 #pragma unroll
             for (int s = 0; s < S; ++s) {
                 const double out = x * b0[s] + z1[s];

@@ -12,9 +12,9 @@
 // argument with indices that depend on the unrolled loop counter only, never on the lane, so the compiler fetches it through the
 // scalar path and every branch on it is wave-uniform.
 //
-// Lanes run along the dense node index.  A lane reads its t staged floats once (the j loop is unrolled over the T slots behind a
-// wave-uniform `j < t`), then walks the captures in order with ONE accumulator: when bin[j] differs from the bin it holds, it stores
-// the sum and loads the new bin's.  No LDS, no atomics, no scratch; the tail of B is a bounds check on the lane.
+// Lanes run along the dense node index.  A lane reads its t staged floats once (fold_parts.hip.h: stage_read), then walks the captures
+// in order with ONE accumulator: when bin[j] differs from the bin it holds, it stores the sum and loads the new bin's.  The tail of B
+// is a bounds check on the lane.
 //
 //   WIDE   (B even; the engine decides) two nodes per lane: 8-byte loads from the stage, 16-byte loads and stores on the bins
 //          (every plane of the stage and of the bins then starts on a 16-byte boundary: hipMalloc's alignment plus a multiple of
@@ -28,6 +28,7 @@
 #include <cstdint>
 
 #include "decay_plan.h"
+#include "fold_parts.hip.h"
 
 namespace wv {
 
@@ -38,58 +39,27 @@ template <bool WIDE>
 __global__ void __launch_bounds__(256) decay_fold_kernel(const float* __restrict__ stage, double* __restrict__ bins, const int32_t* __restrict__ bin,
                                                          const uint64_t nodes, const int32_t t) {
     constexpr int N = WIDE ? 2 : 1;  // nodes per lane
-    typedef float FloatV2 __attribute__((ext_vector_type(2)));
-    typedef double DoubleV2 __attribute__((ext_vector_type(2)));
-    const uint64_t item = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint64_t node = item * N;
+    const uint64_t node = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * N;
     if (node >= nodes || t < 1) return;  // (WIDE: B is even, so a lane has both its nodes or none)
     float p[kDecayStage][N];
-#pragma unroll
-    for (int j = 0; j < kDecayStage; ++j) {
-        if (j < t) {
-            const float* src = stage + (uint64_t)j * nodes + node;
-            if (WIDE) {
-                const FloatV2 v = *reinterpret_cast<const FloatV2*>(src);
-                p[j][0] = v.x;
-                p[j][N - 1] = v.y;
-            } else {
-                p[j][0] = *src;
-            }
-        }
-    }
-    auto load = [&](int32_t b, double (&e)[N]) {
-        const double* plane = bins + (uint64_t)b * nodes + node;
-        if (WIDE) {
-            const DoubleV2 v = *reinterpret_cast<const DoubleV2*>(plane);
-            e[0] = v.x, e[N - 1] = v.y;
-        } else {
-            e[0] = plane[0];
-        }
-    };
-    auto store = [&](int32_t b, const double (&e)[N]) {
-        double* plane = bins + (uint64_t)b * nodes + node;
-        if (WIDE)
-            *reinterpret_cast<DoubleV2*>(plane) = DoubleV2{e[0], e[N - 1]};
-        else
-            plane[0] = e[0];
-    };
+    stage_read(stage, nodes, node, t, p);
     int32_t held = bin[0];
     double e[N];
-    load(held, e);
+    plane_load<N, FoldDouble2>(bins + (uint64_t)held * nodes + node, e);
 #pragma unroll
     for (int j = 0; j < kDecayStage; ++j) {
         if (j < t) {
             const int32_t b = bin[j];  // (no lane in it)
             if (b != held) {
-                store(held, e);
+                plane_store<N, FoldDouble2>(bins + (uint64_t)held * nodes + node, e);
                 held = b;
-                load(held, e);
+                plane_load<N, FoldDouble2>(bins + (uint64_t)held * nodes + node, e);
             }
 #pragma unroll
             for (int n = 0; n < N; ++n) e[n] = e[n] + (double)p[j][n] * (double)p[j][n];
         }
     }
-    store(held, e);
+    plane_store<N, FoldDouble2>(bins + (uint64_t)held * nodes + node, e);
 }
 
 }  // namespace wv

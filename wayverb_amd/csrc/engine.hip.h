@@ -16,8 +16,11 @@
 //   engine_io.hip.h      everything a caller reads or writes: values, fields, planes, filter memories, source,
 //                        receivers
 //   engine_snapshot.hip.h  field snapshots taken on the device while a run goes on (wv_set_snapshots): plan, ring, capture, copy stream, held log
-//   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape
-//   engine_staged.hip.h  the life cycle the six accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release
+//   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape; what every
+//                        plan's setter checks: the box of a plan, the four shared refusals, frequencies, coefficients, physical constants
+//   engine_staged.hip.h  the life cycle the six accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release;
+//                        the host-written tables of a fold (bins, twiddles), the threshold map, the fetch of complex sums
+//   fold_parts.hip.h     the device pieces more than one fold kernel has and that leave its assembly alone: stage read, integrator step, onset rule
 //   engine_spectrum.hip.h  field spectra accumulated on the device while a run goes on (wv_set_spectrum): plan, stage, fold, fetch
 //   spectrum_plan.h      (host only, no HIP) free slots of the stage, when a fold is due, which captures survive a stop, sizes
 //   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the six accumulating plans
@@ -203,35 +206,35 @@ public:
     bool snapshots_active() const override { return snap_.active; }
     // ---- engine_spectrum.hip.h
     int set_spectrum(const wv_spectrum_plan* plan, const double* cycles_per_step) override;
-    int spectrum_count(uint64_t* captures, uint64_t* last_step) override;
+    int spectrum_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(spec_, captures, last_step); }
     int fetch_spectrum(double* dst, uint64_t* captures) override;
     bool spectrum_active() const override { return spec_.active; }
     // ---- engine_decay.hip.h
     int set_decay(const wv_decay_plan* plan) override;
-    int decay_count(uint64_t* captures, uint64_t* last_step) override;
+    int decay_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(decay_, captures, last_step); }
     int fetch_decay(double* dst, uint64_t* captures) override;
     int set_decay_bands(const wv_decay_plan* plan, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) override;
     int fetch_decay_bands(double* dst, uint64_t* captures) override;
     bool decay_active() const override { return decay_.active; }
     // ---- engine_intensity.hip.h
     int set_intensity(const wv_intensity_plan* plan) override;
-    int intensity_count(uint64_t* captures, uint64_t* last_step) override;
+    int intensity_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(inten_, captures, last_step); }
     int fetch_intensity(double* dst, uint64_t* captures) override;
     int fetch_intensity_velocity(double* dst) override;
     bool intensity_active() const override { return inten_.active; }
     // ---- engine_arrival.hip.h
     int set_arrival(const wv_arrival_plan* plan, const float* threshold_map) override;
-    int arrival_count(uint64_t* captures, uint64_t* last_step) override;
+    int arrival_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(arr_, captures, last_step); }
     int fetch_arrival(uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) override;
     bool arrival_active() const override { return arr_.active; }
     // ---- engine_lateral.hip.h
     int set_lateral(const wv_lateral_plan* plan, const float* threshold_map) override;
-    int lateral_count(uint64_t* captures, uint64_t* last_step) override;
+    int lateral_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(lat_, captures, last_step); }
     int fetch_lateral(uint32_t* onset, double* pre, double* velocity, double* bins, uint64_t* captures) override;
     bool lateral_active() const override { return lat_.active; }
     // ---- engine_modulation.hip.h
     int set_modulation(const wv_modulation_plan* plan, const double* cycles_per_step, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) override;
-    int modulation_count(uint64_t* captures, uint64_t* last_step) override;
+    int modulation_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(mod_, captures, last_step); }
     int fetch_modulation(double* energy, double* sums, uint64_t* captures) override;
     bool modulation_active() const override { return mod_.active; }
     // ---- engine_batch.hip.h
@@ -535,7 +538,7 @@ private:
             : kind(kind), name(name), setter(setter), lost(lost), block_name{block0, block1}, host_table(host_table), gradients(gradients),
               max_captures(max_captures) {}
         bool active = false;
-        bool gather_wide = false;       // the capture takes four nodes per lane (as engine_snapshot.hip.h decides it)
+        bool gather_wide = false;       // the capture takes four nodes per lane (snapshot_plan.h: gather_wide)
         bool fold_wide = false;         // the fold takes two nodes per lane
         wv::SnapshotBox box;
         double spacing = 0;             // of the mesh (gradients only)
@@ -557,15 +560,26 @@ private:
         double gather_ms = 0;           // capture kernels' time (kernel timing on), over gathers_timed of them
         uint64_t gathers_timed = 0;
     };
-    // the staged captures' bins, int32[t], which the host writes into one of two page-locked tables in turn (two, so that it never rewrites
-    // a table a queued copy still reads) and copies ahead of the fold: the decay and the intensity plan's (engine_decay.hip.h)
-    struct BinTable {
-        int32_t* host[2] = {nullptr, nullptr};
-        int32_t* dev[2] = {nullptr, nullptr};
+    // a table of the staged captures which the host writes into one of two page-locked buffers in turn (two, so that it never rewrites a
+    // table a queued copy still reads) and copies ahead of the fold: the bins int32[t] of the decay and the intensity plan (BinTable,
+    // engine_decay.hip.h), the twiddles double[t][n_freqs][2] of the spectrum and the modulation plan (TwiddleTable, engine_staged.hip.h)
+    template <typename T>
+    struct HostTable {
+        T* host[2] = {nullptr, nullptr};
+        T* dev[2] = {nullptr, nullptr};
     };
-    hipError_t bin_table_allocate(BinTable& table);
-    static void bin_table_free(BinTable& table);
+    using BinTable = HostTable<int32_t>;
+    using TwiddleTable = HostTable<double>;
+    template <typename T>
+    static hipError_t host_table_allocate(HostTable<T>& table, size_t bytes);
+    template <typename T>
+    static void host_table_free(HostTable<T>& table);
     int bin_table_write(BinTable& table, const StagedPlan& p, int b, int t, uint32_t bin_captures, uint32_t n_bins);
+    int twiddle_table_write(TwiddleTable& table, const StagedPlan& p, int b, int t, const std::vector<double>& freqs);
+    int fetch_interleaved(const double* re_plane, uint64_t nodes, double* out, std::vector<double>& planes);  // Re, Im planes -> [B][2] on the host
+    // the per-node thresholds float[B] of an arrival or a lateral plan: every entry checked, then uploaded beside the candidate's state
+    int threshold_map_refused(const char* setter, const float* map, uint64_t nodes);
+    hipError_t threshold_map_upload(float*& dev, const float* map, uint64_t nodes);
     // field spectra (engine_spectrum.hip.h): the planar sums the fold kernel accumulates, two twiddle tables (page-locked, and their device
     // copies) the host writes in turn
     struct Spectrum : StagedPlan {
@@ -573,9 +587,8 @@ private:
         wv_spectrum_plan plan{};
         std::vector<double> freqs;      // cycles per step, [K]
         double* acc() const { return reinterpret_cast<double*>(this->block[0]); }  // [K][2][B]
-        double* tw_host[2] = {nullptr, nullptr};
-        double* tw_dev[2] = {nullptr, nullptr};
-        void free_own();
+        TwiddleTable tw;
+        void free_own() { host_table_free(tw); }
     } spec_;
     int spectrum_enqueue(Spectrum& s, int b, int t, unsigned blocks);
     // energy decay maps (engine_decay.hip.h): the time-binned energies the fold kernel accumulates; a banded plan's filter states and
@@ -641,8 +654,7 @@ private:
         double* state() const { return reinterpret_cast<double*>(this->block[1]); }  // [n_bands][n_sections][2][B]: z1, z2 of every section
         uint32_t n_bands = 0, n_sections = 0;
         double* coef = nullptr;         // [n_bands][n_sections][5] on the device
-        double* tw_host[2] = {nullptr, nullptr};
-        double* tw_dev[2] = {nullptr, nullptr};
+        TwiddleTable tw;
         void free_own();
     } mod_;
     int modulation_enqueue(Modulation& d, int b, int t, unsigned blocks);

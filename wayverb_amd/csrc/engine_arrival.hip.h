@@ -34,33 +34,22 @@ int Engine<Real>::set_arrival(const wv_arrival_plan* plan, const float* threshol
     if (!wv::arrival_edges_valid(plan->edges, plan->n_bins))
         return fail(WV_E_INVALID_ARGUMENT, "wv_set_arrival: edges[0] must be 0 and the edges strictly increasing");
     if (!wv::arrival_threshold_valid(plan->threshold)) return fail(WV_E_INVALID_ARGUMENT, "wv_set_arrival: the threshold must be >= 0 and finite");
-    wv::SnapshotBox box;
-    box.x0 = plan->x0, box.y0 = plan->y0, box.z0 = plan->z0;
-    box.nx = plan->nx, box.ny = plan->ny, box.nz = plan->nz;
-    box.sx = plan->sx, box.sy = plan->sy, box.sz = plan->sz;
-    if (plan->sx < 1 || plan->sy < 1 || plan->sz < 1) return fail(WV_E_INVALID_ARGUMENT, "wv_set_arrival: strides must be >= 1");
-    if (plan->period < 1) return fail(WV_E_INVALID_ARGUMENT, "wv_set_arrival: period must be >= 1");
-    if (!wv::snapshot_box_valid(box, nx_, ny_, nz_)) return fail(WV_E_INVALID_ARGUMENT, "wv_set_arrival: the box leaves the mesh");
-    // (the capture kernel indexes a dense plane with 32 bits)
-    if ((uint64_t)box.nx * (uint64_t)box.ny >= (1ull << 31)) return fail(WV_E_INVALID_ARGUMENT, "wv_set_arrival: more than 2^31 nodes per plane of the box");
+    static const wv::PlanSentences says = WV_PLAN_SENTENCES("wv_set_arrival");
+    if (const char* why = wv::plan_refusal(*plan, nx_, ny_, nz_, says)) return fail(WV_E_INVALID_ARGUMENT, why);
+    const wv::SnapshotBox box = wv::plan_box(*plan);
     const uint64_t nodes = wv::decay_nodes(box.nx, box.ny, box.nz);
-    if (threshold_map)
-        for (uint64_t i = 0; i < nodes; ++i)
-            if (!wv::arrival_threshold_valid(threshold_map[i]))
-                return fail(WV_E_INVALID_ARGUMENT, "wv_set_arrival: every entry of the threshold map must be >= 0 and finite");
+    if (const int rc = threshold_map_refused("wv_set_arrival", threshold_map, nodes)) return rc;
     Arrival d;
     d.plan = *plan;
     d.box = box;
     d.nodes = nodes;
-    d.gather_wide = box.sx == 1 && box.x0 % 4 == 0 && box.nx % 4 == 0;  // (as engine_snapshot.hip.h decides it)
-    const uint64_t map_bytes = wv::arrival_map_bytes(nodes);
+    d.gather_wide = wv::gather_wide(box);
     hipError_t rc = staged_allocate(d, wv::arrival_stage_bytes(nodes), wv::arrival_state_bytes(nodes, plan->n_bins));
-    if (threshold_map && rc == hipSuccess && (rc = hipMalloc((void**)&d.threshold_map, (size_t)map_bytes)) != hipSuccess) d.threshold_map = nullptr;
     // +0.0 / +0.0f everywhere, then NONE (all bits set) into the onsets and the peak captures
     if (rc == hipSuccess) rc = hipMemsetAsync(d.state(), 0, d.block_bytes[0], stream_);
     if (rc == hipSuccess) rc = hipMemsetAsync(d.state() + wv::arrival_onset_offset(nodes, plan->n_bins), 0xFF, (size_t)nodes * 4, stream_);
     if (rc == hipSuccess) rc = hipMemsetAsync(d.state() + wv::arrival_peak_capture_offset(nodes, plan->n_bins), 0xFF, (size_t)nodes * 4, stream_);
-    if (threshold_map && rc == hipSuccess) rc = hipMemcpyAsync(d.threshold_map, threshold_map, (size_t)map_bytes, hipMemcpyHostToDevice, stream_);
+    if (rc == hipSuccess) rc = threshold_map_upload(d.threshold_map, threshold_map, nodes);
     return staged_install(arr_, d, rc, "wv_set_arrival: no room for the stage and the state", plan->first_step, plan->period);
 }
 
@@ -81,11 +70,6 @@ int Engine<Real>::arrival_enqueue(Arrival& d, int b, int t, unsigned blocks) {
                        reinterpret_cast<uint32_t*>(state + wv::arrival_peak_capture_offset(d.nodes, n_bins)), (const float*)d.threshold_map, d.plan.threshold,
                        edges, n_bins, (uint32_t)d.st.folded, d.nodes, (int32_t)t);
     return WV_OK;
-}
-
-template <typename Real>
-int Engine<Real>::arrival_count(uint64_t* captures, uint64_t* last_step) {
-    return staged_count(arr_, captures, last_step);
 }
 
 // Folds what is staged, then every part the caller gave a destination for -> the host as it lies.  The plan keeps running.

@@ -21,31 +21,6 @@
 
 namespace wv {
 
-template <typename Real>
-hipError_t Engine<Real>::bin_table_allocate(BinTable& table) {
-    const size_t bytes = (size_t)wv::decay_table_bytes();
-    for (int i = 0; i < 2; ++i) {
-        hipError_t rc = hipMalloc((void**)&table.dev[i], bytes);
-        if (rc != hipSuccess) {
-            table.dev[i] = nullptr;
-            return rc;
-        }
-        if ((rc = hipHostMalloc((void**)&table.host[i], bytes, hipHostMallocDefault)) != hipSuccess) {
-            table.host[i] = nullptr;
-            return rc;
-        }
-    }
-    return hipSuccess;
-}
-
-template <typename Real>
-void Engine<Real>::bin_table_free(BinTable& table) {
-    for (int i = 0; i < 2; ++i) {
-        if (table.dev[i]) (void)hipFree(table.dev[i]);
-        if (table.host[i]) (void)hipHostFree(table.host[i]);
-    }
-}
-
 // Turn b's table for a fold of plan p's t staged captures: staged capture j is capture number folded + j since the plan was set.
 template <typename Real>
 int Engine<Real>::bin_table_write(BinTable& table, const StagedPlan& p, int b, int t, uint32_t bin_captures, uint32_t n_bins) {
@@ -57,7 +32,7 @@ int Engine<Real>::bin_table_write(BinTable& table, const StagedPlan& p, int b, i
 template <typename Real>
 void Engine<Real>::Decay::free_own() {
     if (coef) (void)hipFree(coef);
-    bin_table_free(table);
+    host_table_free(table);
 }
 
 template <typename Real>
@@ -84,29 +59,19 @@ int Engine<Real>::decay_set(const wv_decay_plan* plan, const wv_biquad* sections
     if (banded) {
         if (!wv::decay_bands_valid(n_bands, n_sections)) return fail(WV_E_INVALID_ARGUMENT, "wv_set_decay_bands: n_bands must be 1 .. 8 and n_sections 1 .. 4");
         if (!sections) return fail(WV_E_INVALID_ARGUMENT, "null argument");
-        for (uint32_t i = 0; i < n_bands * n_sections; ++i) {
-            const wv_biquad& c = sections[i];
-            if (!std::isfinite(c.b0) || !std::isfinite(c.b1) || !std::isfinite(c.b2) || !std::isfinite(c.a1) || !std::isfinite(c.a2))
-                return fail(WV_E_INVALID_ARGUMENT, "wv_set_decay_bands: every coefficient must be finite");
-        }
+        if (!wv::biquads_finite(sections, n_bands * n_sections)) return fail(WV_E_INVALID_ARGUMENT, "wv_set_decay_bands: every coefficient must be finite");
     }
     if (plan->n_bins < 1 || plan->n_bins > wv::kDecayMaxBins) return fail(WV_E_INVALID_ARGUMENT, who + ": n_bins must be 1 .. 4096");
     if (plan->bin_captures < 1) return fail(WV_E_INVALID_ARGUMENT, who + ": bin_captures must be >= 1");
-    wv::SnapshotBox box;
-    box.x0 = plan->x0, box.y0 = plan->y0, box.z0 = plan->z0;
-    box.nx = plan->nx, box.ny = plan->ny, box.nz = plan->nz;
-    box.sx = plan->sx, box.sy = plan->sy, box.sz = plan->sz;
-    if (plan->sx < 1 || plan->sy < 1 || plan->sz < 1) return fail(WV_E_INVALID_ARGUMENT, who + ": strides must be >= 1");
-    if (plan->period < 1) return fail(WV_E_INVALID_ARGUMENT, who + ": period must be >= 1");
-    if (!wv::snapshot_box_valid(box, nx_, ny_, nz_)) return fail(WV_E_INVALID_ARGUMENT, who + ": the box leaves the mesh");
-    // (the capture kernel indexes a dense plane with 32 bits)
-    if ((uint64_t)box.nx * (uint64_t)box.ny >= (1ull << 31)) return fail(WV_E_INVALID_ARGUMENT, who + ": more than 2^31 nodes per plane of the box");
+    static const wv::PlanSentences says[2] = {WV_PLAN_SENTENCES("wv_set_decay"), WV_PLAN_SENTENCES("wv_set_decay_bands")};
+    if (const char* why = wv::plan_refusal(*plan, nx_, ny_, nz_, says[banded])) return fail(WV_E_INVALID_ARGUMENT, why);
+    const wv::SnapshotBox box = wv::plan_box(*plan);
     Decay d;
     d.plan = *plan;
     d.box = box;
     d.nodes = wv::decay_nodes(box.nx, box.ny, box.nz);
-    d.gather_wide = box.sx == 1 && box.x0 % 4 == 0 && box.nx % 4 == 0;  // (as engine_snapshot.hip.h decides it)
-    d.fold_wide = !banded && d.nodes % 2 == 0;                           // two nodes per lane, 16-byte accesses on the bins
+    d.gather_wide = wv::gather_wide(box);
+    d.fold_wide = !banded && d.nodes % 2 == 0;  // two nodes per lane, 16-byte accesses on the bins
     d.n_bands = banded ? n_bands : 0;
     d.n_sections = banded ? n_sections : 0;
     const uint64_t bins_bytes = banded ? wv::decay_band_bins_bytes(d.nodes, plan->n_bins, n_bands) : wv::decay_bins_bytes(d.nodes, plan->n_bins);
@@ -115,7 +80,7 @@ int Engine<Real>::decay_set(const wv_decay_plan* plan, const wv_biquad* sections
     static_assert(sizeof(wv_biquad) == wv::kBiquadDoubles * sizeof(double), "wv_biquad is five doubles: the coefficient table is the caller's array as it lies");
     hipError_t rc = staged_allocate(d, wv::decay_stage_bytes(d.nodes), bins_bytes, state_bytes);
     if (banded && rc == hipSuccess && (rc = hipMalloc((void**)&d.coef, coef_bytes)) != hipSuccess) d.coef = nullptr;
-    if (rc == hipSuccess) rc = bin_table_allocate(d.table);
+    if (rc == hipSuccess) rc = host_table_allocate(d.table, (size_t)wv::decay_table_bytes());
     if (rc == hipSuccess) rc = hipMemsetAsync(d.bins(), 0, d.block_bytes[0], stream_);  // (+0.0 everywhere)
     if (banded && rc == hipSuccess) rc = hipMemsetAsync(d.state(), 0, d.block_bytes[1], stream_);
     if (banded && rc == hipSuccess) rc = hipMemcpyAsync(d.coef, sections, coef_bytes, hipMemcpyHostToDevice, stream_);
@@ -144,11 +109,6 @@ int Engine<Real>::decay_enqueue(Decay& d, int b, int t, unsigned blocks) {
     else
         hipLaunchKernelGGL((wv::decay_fold_kernel<false>), dim3(blocks), dim3(256), 0, stream_, d.stage, d.bins(), d.table.dev[b], d.nodes, (int32_t)t);
     return WV_OK;
-}
-
-template <typename Real>
-int Engine<Real>::decay_count(uint64_t* captures, uint64_t* last_step) {
-    return staged_count(decay_, captures, last_step);
 }
 
 // Folds what is staged, then the bins -> the host as they lie: [n_bins][nz][ny][nx].  The plan keeps running.

@@ -21,7 +21,7 @@ namespace wv {
 
 template <typename Real>
 void Engine<Real>::Intensity::free_own() {
-    bin_table_free(table);
+    host_table_free(table);
 }
 
 template <typename Real>
@@ -33,12 +33,12 @@ int Engine<Real>::set_intensity(const wv_intensity_plan* plan) {
     if (wv::intensity_plan_check(*plan, nx_, ny_, nz_, &why)) return fail(WV_E_INVALID_ARGUMENT, why);
     Intensity d;
     d.plan = *plan;
-    d.box = wv::intensity_box(*plan);
+    d.box = wv::plan_box(*plan);
     d.spacing = plan->spacing;
     d.nodes = wv::decay_nodes(d.box.nx, d.box.ny, d.box.nz);
     d.k = plan->ambient_density * plan->sample_rate;
     hipError_t rc = staged_allocate(d, wv::intensity_stage_bytes(d.nodes), wv::intensity_bins_bytes(d.nodes, plan->n_bins), wv::intensity_velocity_bytes(d.nodes));
-    if (rc == hipSuccess) rc = bin_table_allocate(d.table);
+    if (rc == hipSuccess) rc = host_table_allocate(d.table, (size_t)wv::decay_table_bytes());
     if (rc == hipSuccess) rc = hipMemsetAsync(d.bins(), 0, d.block_bytes[0], stream_);  // (+0.0 everywhere)
     if (rc == hipSuccess) rc = hipMemsetAsync(d.velocity(), 0, d.block_bytes[1], stream_);
     return staged_install(inten_, d, rc, "wv_set_intensity: no room for the stage, the velocities and the bins", plan->first_step, plan->period);
@@ -52,11 +52,6 @@ int Engine<Real>::intensity_enqueue(Intensity& d, int b, int t, unsigned blocks)
     hipLaunchKernelGGL(wv::intensity_fold_kernel, dim3(blocks), dim3(256), 0, stream_, d.stage, d.velocity(), d.bins(), d.table.dev[b], d.nodes,
                        d.plan.n_bins, d.k, (int32_t)t);
     return WV_OK;
-}
-
-template <typename Real>
-int Engine<Real>::intensity_count(uint64_t* captures, uint64_t* last_step) {
-    return staged_count(inten_, captures, last_step);
 }
 
 // Folds what is staged, then the bins -> the host as they lie: [4][n_bins][nz][ny][nx].  The plan keeps running.

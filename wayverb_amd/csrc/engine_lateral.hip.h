@@ -31,25 +31,20 @@ int Engine<Real>::set_lateral(const wv_lateral_plan* plan, const float* threshol
     if (const int rc = plan_refused("wv_set_lateral", kLateralRow)) return rc;
     const char* why = nullptr;
     if (wv::lateral_plan_check(*plan, nx_, ny_, nz_, &why)) return fail(WV_E_INVALID_ARGUMENT, why);
-    const wv::SnapshotBox box = wv::lateral_box(*plan);
+    const wv::SnapshotBox box = wv::plan_box(*plan);
     const uint64_t nodes = wv::decay_nodes(box.nx, box.ny, box.nz);
-    if (threshold_map)
-        for (uint64_t i = 0; i < nodes; ++i)
-            if (!wv::arrival_threshold_valid(threshold_map[i]))
-                return fail(WV_E_INVALID_ARGUMENT, "wv_set_lateral: every entry of the threshold map must be >= 0 and finite");
+    if (const int rc = threshold_map_refused("wv_set_lateral", threshold_map, nodes)) return rc;
     Lateral d;
     d.plan = *plan;
     d.box = box;
     d.spacing = plan->spacing;
     d.nodes = nodes;
     d.k = plan->ambient_density * plan->sample_rate;
-    const uint64_t map_bytes = wv::lateral_map_bytes(nodes);
     hipError_t rc = staged_allocate(d, wv::lateral_stage_bytes(nodes), wv::lateral_state_bytes(nodes, plan->n_bins));
-    if (threshold_map && rc == hipSuccess && (rc = hipMalloc((void**)&d.threshold_map, (size_t)map_bytes)) != hipSuccess) d.threshold_map = nullptr;
     // +0.0 everywhere, then NONE (all bits set) into the onsets
     if (rc == hipSuccess) rc = hipMemsetAsync(d.state(), 0, d.block_bytes[0], stream_);
     if (rc == hipSuccess) rc = hipMemsetAsync(d.state() + wv::lateral_onset_offset(nodes, plan->n_bins), 0xFF, (size_t)nodes * 4, stream_);
-    if (threshold_map && rc == hipSuccess) rc = hipMemcpyAsync(d.threshold_map, threshold_map, (size_t)map_bytes, hipMemcpyHostToDevice, stream_);
+    if (rc == hipSuccess) rc = threshold_map_upload(d.threshold_map, threshold_map, nodes);
     return staged_install(lat_, d, rc, "wv_set_lateral: no room for the stage and the state", plan->first_step, plan->period);
 }
 
@@ -69,11 +64,6 @@ int Engine<Real>::lateral_enqueue(Lateral& d, int b, int t, unsigned blocks) {
                        reinterpret_cast<uint32_t*>(state + wv::lateral_onset_offset(d.nodes, n_bins)), (const float*)d.threshold_map, d.plan.threshold, edges,
                        n_bins, (uint32_t)d.st.folded, d.nodes, d.k, (int32_t)t);
     return WV_OK;
-}
-
-template <typename Real>
-int Engine<Real>::lateral_count(uint64_t* captures, uint64_t* last_step) {
-    return staged_count(lat_, captures, last_step);
 }
 
 // Folds what is staged, then every part the caller gave a destination for -> the host as it lies.  The plan keeps running.

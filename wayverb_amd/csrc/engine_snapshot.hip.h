@@ -46,13 +46,9 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
     // (a slab of a chain would have to cut its batches where its neighbours do, and each rank holds only its part of a box: out of
     // scope, as for wv_checkpoint; an accumulating plan cuts the passes at its own steps: engine_staged.hip.h)
     if (const int rc = plan_refused("wv_set_snapshots", kSnapshotRow)) return rc;
-    wv::SnapshotBox box;
-    box.x0 = plan->x0, box.y0 = plan->y0, box.z0 = plan->z0;
-    box.nx = plan->nx, box.ny = plan->ny, box.nz = plan->nz;
-    box.sx = plan->sx, box.sy = plan->sy, box.sz = plan->sz;
-    if (plan->sx < 1 || plan->sy < 1 || plan->sz < 1) return fail(WV_E_INVALID_ARGUMENT, "wv_set_snapshots: strides must be >= 1");
-    if (plan->period < 1) return fail(WV_E_INVALID_ARGUMENT, "wv_set_snapshots: period must be >= 1");
-    if (!wv::snapshot_box_valid(box, nx_, ny_, nz_)) return fail(WV_E_INVALID_ARGUMENT, "wv_set_snapshots: the box leaves the mesh");
+    static const wv::PlanSentences says = WV_PLAN_SENTENCES("wv_set_snapshots");
+    if (const char* why = wv::plan_refusal(*plan, nx_, ny_, nz_, says)) return fail(WV_E_INVALID_ARGUMENT, why);
+    const wv::SnapshotBox box = wv::plan_box(*plan);
     // everything is allocated here, aside, and only a complete set takes the old plan's place: no room -> WV_E_HIP, engine untouched
     Snapshots s;
     s.generation = snap_.generation + 1;
@@ -60,11 +56,8 @@ int Engine<Real>::set_snapshots(const wv_snapshot_plan* plan) {
     s.box = box;
     s.elems = wv::snapshot_elements(box);
     const size_t bytes = (size_t)wv::snapshot_bytes(box);
-    // (the capture kernel indexes a dense plane with 32 bits)
-    if ((uint64_t)box.nx * (uint64_t)box.ny >= (1ull << 31)) return fail(WV_E_INVALID_ARGUMENT, "wv_set_snapshots: more than 2^31 nodes per plane of the box");
     s.slots = bytes > (64ull << 20) ? 2 : kSnapSlots;
-    // four nodes per lane where the rows allow 16-byte accesses on both sides (snapshot_kernels.hip.h)
-    s.wide = box.sx == 1 && box.x0 % 4 == 0 && box.nx % 4 == 0;
+    s.wide = wv::gather_wide(box);
     hipError_t rc = hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking);
     for (int i = 0; i < s.slots && rc == hipSuccess; ++i) {
         if ((rc = hipMalloc((void**)&s.dev[i], bytes)) != hipSuccess) {

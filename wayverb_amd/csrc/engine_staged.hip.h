@@ -1,7 +1,9 @@
 // engine_staged.hip.h -- the life cycle of the six plans that accumulate on the device while wv_run keeps going: field spectra
 // (engine_spectrum.hip.h), energy decay maps plain and banded (engine_decay.hip.h), intensity maps (engine_intensity.hip.h),
 // arrival-aligned energy maps (engine_arrival.hip.h), lateral maps (engine_lateral.hip.h) and modulation maps (engine_modulation.hip.h).  One copy of each step; what a plan's own
-// file keeps is its setter's validation, sizes and first contents, the enqueue step of its fold and its fetch.
+// file keeps is its setter's validation, sizes and first contents, the enqueue step of its fold and its fetch -- and
+// of those the pieces more than one plan has are here too: the host-written tables of a fold (HostTable: bins, twiddles), the threshold
+// map of the plans that find an onset, the fetch of complex sums.
 //
 // Part of the engine behind the C ABI of include/wayverb_amd.h (engine.hip is the translation unit; see engine.hip.h for the class).
 //
@@ -20,6 +22,8 @@
 // In-order execution is what keeps a slot from being overwritten before the fold has read it: captures of the next batch are
 // enqueued behind the fold.  The state is only ever touched by a fold, and a fold only ever sees committed captures.
 #pragma once
+#include <cmath>
+
 #include "engine.hip.h"
 
 namespace wv {
@@ -125,6 +129,91 @@ hipError_t Engine<Real>::staged_allocate(StagedPlan& c, uint64_t stage_bytes, ui
         if ((rc = hipEventCreate(&c.gather_done[i])) != hipSuccess) return rc;
     }
     return hipSuccess;
+}
+
+// Both buffers of a host-written table and their device copies (a candidate's: what is missing stays null and plan_release frees the rest).
+template <typename Real>
+template <typename T>
+hipError_t Engine<Real>::host_table_allocate(HostTable<T>& table, size_t bytes) {
+    for (int i = 0; i < 2; ++i) {
+        hipError_t rc = hipMalloc((void**)&table.dev[i], bytes);
+        if (rc != hipSuccess) {
+            table.dev[i] = nullptr;
+            return rc;
+        }
+        if ((rc = hipHostMalloc((void**)&table.host[i], bytes, hipHostMallocDefault)) != hipSuccess) {
+            table.host[i] = nullptr;
+            return rc;
+        }
+    }
+    return hipSuccess;
+}
+
+template <typename Real>
+template <typename T>
+void Engine<Real>::host_table_free(HostTable<T>& table) {
+    for (int i = 0; i < 2; ++i) {
+        if (table.dev[i]) (void)hipFree(table.dev[i]);
+        if (table.host[i]) (void)hipHostFree(table.host[i]);
+    }
+}
+
+// x = f * step, its fractional part, cos and sin of 2 pi x: three rounded operations ahead of libm, so that NumPy evaluating the
+// same three gives the same argument (include/wayverb_amd.h: wv_spectrum_twiddle)
+inline void spectrum_twiddle(double cycles_per_step, uint64_t step, double* c, double* s) {
+    double x = cycles_per_step * (double)step;
+    x -= std::floor(x);
+    const double angle = 6.283185307179586476925286766559 * x;
+    *c = std::cos(angle);
+    *s = std::sin(angle);
+}
+
+// Turn b's twiddles for a fold of plan p's t staged captures, double[t][K][2]: cos and sin of capture j's step at each of the K
+// frequencies, and the copy.
+template <typename Real>
+int Engine<Real>::twiddle_table_write(TwiddleTable& table, const StagedPlan& p, int b, int t, const std::vector<double>& freqs) {
+    const uint32_t K = (uint32_t)freqs.size();
+    for (int j = 0; j < t; ++j)
+        for (uint32_t k = 0; k < K; ++k) {
+            double* w = table.host[b] + wv::spectrum_table_index((uint32_t)j, k, K);
+            wv::spectrum_twiddle(freqs[k], p.st.steps[(size_t)j], w, w + 1);
+        }
+    WV_HIP(hipMemcpyAsync(table.dev[b], table.host[b], (size_t)t * K * 2 * sizeof(double), hipMemcpyHostToDevice, stream_));
+    return WV_OK;
+}
+
+// A fetch of complex sums: the Re plane at `re_plane` on the device and the Im plane behind it -> out[B][2], by way of the caller's
+// `planes` (2 B doubles, allocated once per fetch).
+template <typename Real>
+int Engine<Real>::fetch_interleaved(const double* re_plane, uint64_t nodes, double* out, std::vector<double>& planes) {
+    WV_HIP(hipMemcpy(planes.data(), re_plane, planes.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const double *re = planes.data(), *im = planes.data() + nodes;
+    for (uint64_t i = 0; i < nodes; ++i) {
+        out[2 * i] = re[i];
+        out[2 * i + 1] = im[i];
+    }
+    return WV_OK;
+}
+
+// A setter's threshold map (NULL: none): refused for an entry that the plan's scalar would be refused for ...
+template <typename Real>
+int Engine<Real>::threshold_map_refused(const char* setter, const float* map, uint64_t nodes) {
+    for (uint64_t i = 0; map && i < nodes; ++i)
+        if (!wv::arrival_threshold_valid(map[i])) return fail(WV_E_INVALID_ARGUMENT, std::string(setter) + ": every entry of the threshold map must be >= 0 and finite");
+    return WV_OK;
+}
+
+// ... and allocated and copied to the device beside a candidate's state.
+template <typename Real>
+hipError_t Engine<Real>::threshold_map_upload(float*& dev, const float* map, uint64_t nodes) {
+    if (!map) return hipSuccess;
+    const size_t bytes = (size_t)wv::arrival_map_bytes(nodes);
+    const hipError_t rc = hipMalloc((void**)&dev, bytes);
+    if (rc != hipSuccess) {
+        dev = nullptr;
+        return rc;
+    }
+    return hipMemcpyAsync(dev, map, bytes, hipMemcpyHostToDevice, stream_);
 }
 
 // The end of a setter: `rc` is what allocating and filling the candidate came to.  The candidate's first contents are on the device

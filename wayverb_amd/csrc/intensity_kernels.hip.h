@@ -35,6 +35,7 @@
 
 #include <cstdint>
 
+#include "fold_parts.hip.h"
 #include "intensity_plan.h"
 
 namespace wv {
@@ -115,8 +116,7 @@ __global__ void __launch_bounds__(256) intensity_fold_kernel(const float* __rest
             const double p = (double)pressure;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const double m = (double)g[a] * 0.5;
-                v[a] = v[a] - m / k;
+                v[a] = integrate(v[a], g[a], k);
                 e[a] = e[a] + v[a] * p;
             }
             e[3] = e[3] + p * p;

@@ -5,7 +5,6 @@
 // are plan steps and whether a box lies inside the mesh is snapshot_plan.h's.
 // tests/cpp/intensity_plan_test.cpp covers this file on the CPU.
 #pragma once
-#include <cmath>
 #include <cstdint>
 
 #include "../../include/wayverb_amd.h"
@@ -20,37 +19,32 @@ constexpr uint32_t kIntensityPlanes = 4;       // per staged capture: pressure, 
 // the reference's sentence for a node with a neighbour off the grid (directional_receiver.cpp:18-22), as wv_set_directional_receivers says it
 constexpr const char* kIntensityEdge = "Can't place directional_receiver at this node as it is adjacent to a boundary.";
 
-inline SnapshotBox intensity_box(const wv_intensity_plan& p) {
-    SnapshotBox b;
-    b.x0 = p.x0, b.y0 = p.y0, b.z0 = p.z0;
-    b.nx = p.nx, b.ny = p.ny, b.nz = p.nz;
-    b.sx = p.sx, b.sy = p.sy, b.sz = p.sz;
-    return b;
-}
-
 // one axis of a valid box: every taken node has both neighbours on the grid
 inline bool intensity_axis_inside(int64_t first, int64_t count, int64_t stride, int64_t mesh) {
     return first >= 1 && first + (count - 1) * stride <= mesh - 2;
 }
 
+// What a plan that captures gradients (this one, and the lateral plan) is refused for behind its own counts, in the order both setters
+// ask: the shared refusals of snapshot_plan.h with the physical constants between period and box and the mesh's faces ahead of the plane's
+// size.  `says`, `constants`: the sentences with the setter's name.
+template <typename Plan>
+inline const char* gradient_plan_refusal(const Plan& p, int32_t mesh_nx, int32_t mesh_ny, int32_t mesh_nz, const PlanSentences& says, const char* constants) {
+    if (const char* w = plan_refusal(p, mesh_nx, mesh_ny, mesh_nz, says, kPlanStrides, kPlanPeriod)) return w;
+    if (!physical_constants_valid(p.spacing, p.sample_rate, p.ambient_density)) return constants;
+    if (const char* w = plan_refusal(p, mesh_nx, mesh_ny, mesh_nz, says, kPlanLeavesMesh, kPlanLeavesMesh)) return w;
+    if (!intensity_axis_inside(p.x0, p.nx, p.sx, mesh_nx) || !intensity_axis_inside(p.y0, p.ny, p.sy, mesh_ny) || !intensity_axis_inside(p.z0, p.nz, p.sz, mesh_nz))
+        return kIntensityEdge;
+    return plan_refusal(p, mesh_nx, mesh_ny, mesh_nz, says, kPlanPlaneSize, kPlanPlaneSize);
+}
+
 // WV_OK, or WV_E_INVALID_ARGUMENT with *why (never NULL then) = what is wrong, in the order wv_set_decay checks what the two share
 inline int intensity_plan_check(const wv_intensity_plan& p, int32_t mesh_nx, int32_t mesh_ny, int32_t mesh_nz, const char** why) {
+    static const PlanSentences says = WV_PLAN_SENTENCES("wv_set_intensity");
     const char* dummy = nullptr;
     const char*& w = why ? *why : dummy;
-    w = nullptr;
     if (p.n_bins < 1 || p.n_bins > kDecayMaxBins) w = "wv_set_intensity: n_bins must be 1 .. 4096";
     else if (p.bin_captures < 1) w = "wv_set_intensity: bin_captures must be >= 1";
-    else if (p.sx < 1 || p.sy < 1 || p.sz < 1) w = "wv_set_intensity: strides must be >= 1";
-    else if (p.period < 1) w = "wv_set_intensity: period must be >= 1";
-    else if (!(p.spacing > 0) || !(p.sample_rate > 0) || !(p.ambient_density > 0) || !std::isfinite(p.spacing) || !std::isfinite(p.sample_rate) ||
-             !std::isfinite(p.ambient_density))
-        w = "wv_set_intensity: spacing, sample rate and ambient density must be positive and finite";
-    else if (!snapshot_box_valid(intensity_box(p), mesh_nx, mesh_ny, mesh_nz)) w = "wv_set_intensity: the box leaves the mesh";
-    else if (!intensity_axis_inside(p.x0, p.nx, p.sx, mesh_nx) || !intensity_axis_inside(p.y0, p.ny, p.sy, mesh_ny) ||
-             !intensity_axis_inside(p.z0, p.nz, p.sz, mesh_nz))
-        w = kIntensityEdge;
-    // (the capture kernel indexes a dense plane with 32 bits)
-    else if ((uint64_t)p.nx * (uint64_t)p.ny >= (1ull << 31)) w = "wv_set_intensity: more than 2^31 nodes per plane of the box";
+    else w = gradient_plan_refusal(p, mesh_nx, mesh_ny, mesh_nz, says, "wv_set_intensity: spacing, sample rate and ambient density must be positive and finite");
     return w ? WV_E_INVALID_ARGUMENT : WV_OK;
 }
 

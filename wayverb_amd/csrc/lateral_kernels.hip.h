@@ -31,6 +31,7 @@
 #include <cstdint>
 
 #include "arrival_kernels.hip.h"
+#include "fold_parts.hip.h"
 #include "lateral_plan.h"
 
 namespace wv {
@@ -71,11 +72,10 @@ __global__ void __launch_bounds__(256)
             const float g[3] = {src[nodes], src[2 * nodes], src[3 * nodes]};
             const uint32_t c = first + (uint32_t)j;  // (no lane in it)
             const float a = __builtin_fabsf(pressure);
-            if (on == kLateralNone && a >= thr) on = c;  // (false for a NaN)
+            on = onset_update(on, a, thr, c, kLateralNone);
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                const double m = (double)g[i] * 0.5;
-                v[i] = v[i] - m / k;
+                v[i] = integrate(v[i], g[i], k);
             }
             const double p = (double)pressure;
             if (on == kLateralNone) {

@@ -6,7 +6,6 @@
 // bookkeeping is capture_stage.h's.
 // tests/cpp/lateral_plan_test.cpp covers this file on the CPU.
 #pragma once
-#include <cmath>
 #include <cstdint>
 
 #include "arrival_plan.h"
@@ -22,34 +21,18 @@ constexpr uint64_t kLateralMaxCaptures = kArrivalMaxCaptures;
 
 static_assert(kLateralMaxBins <= kArrivalMaxBins, "arrival_bin counts the edges of a lateral plan");
 
-inline SnapshotBox lateral_box(const wv_lateral_plan& p) {
-    SnapshotBox b;
-    b.x0 = p.x0, b.y0 = p.y0, b.z0 = p.z0;
-    b.nx = p.nx, b.ny = p.ny, b.nz = p.nz;
-    b.sx = p.sx, b.sy = p.sy, b.sz = p.sz;
-    return b;
-}
+inline SnapshotBox lateral_box(const wv_lateral_plan& p) { return plan_box(p); }
 
 // WV_OK, or WV_E_INVALID_ARGUMENT with *why (never NULL then) = what is wrong, in the order wv_set_arrival and wv_set_intensity
 // check what they share with this plan
 inline int lateral_plan_check(const wv_lateral_plan& p, int32_t mesh_nx, int32_t mesh_ny, int32_t mesh_nz, const char** why) {
+    static const PlanSentences says = WV_PLAN_SENTENCES("wv_set_lateral");
     const char* dummy = nullptr;
     const char*& w = why ? *why : dummy;
-    w = nullptr;
     if (p.n_bins < 1 || p.n_bins > kLateralMaxBins) w = "wv_set_lateral: n_bins must be 1 .. 8";
     else if (!arrival_edges_valid(p.edges, p.n_bins)) w = "wv_set_lateral: edges[0] must be 0 and the edges strictly increasing";
     else if (!arrival_threshold_valid(p.threshold)) w = "wv_set_lateral: the threshold must be >= 0 and finite";
-    else if (p.sx < 1 || p.sy < 1 || p.sz < 1) w = "wv_set_lateral: strides must be >= 1";
-    else if (p.period < 1) w = "wv_set_lateral: period must be >= 1";
-    else if (!(p.spacing > 0) || !(p.sample_rate > 0) || !(p.ambient_density > 0) || !std::isfinite(p.spacing) || !std::isfinite(p.sample_rate) ||
-             !std::isfinite(p.ambient_density))
-        w = "wv_set_lateral: spacing, sample rate and ambient density must be positive and finite";
-    else if (!snapshot_box_valid(lateral_box(p), mesh_nx, mesh_ny, mesh_nz)) w = "wv_set_lateral: the box leaves the mesh";
-    else if (!intensity_axis_inside(p.x0, p.nx, p.sx, mesh_nx) || !intensity_axis_inside(p.y0, p.ny, p.sy, mesh_ny) ||
-             !intensity_axis_inside(p.z0, p.nz, p.sz, mesh_nz))
-        w = kIntensityEdge;
-    // (the capture kernel indexes a dense plane with 32 bits)
-    else if ((uint64_t)p.nx * (uint64_t)p.ny >= (1ull << 31)) w = "wv_set_lateral: more than 2^31 nodes per plane of the box";
+    else w = gradient_plan_refusal(p, mesh_nx, mesh_ny, mesh_nz, says, "wv_set_lateral: spacing, sample rate and ambient density must be positive and finite");
     return w ? WV_E_INVALID_ARGUMENT : WV_OK;
 }
 

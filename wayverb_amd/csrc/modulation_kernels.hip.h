@@ -18,7 +18,7 @@
 //   state  double[n_bands][S][2][B]          z1, z2 of every section, planar: a wave reads and writes 512 contiguous bytes per plane
 //   sums   double[n_bands][1 + 2 M][B]       E, then Re, Im per frequency, planar
 //
-// A lane reads its t staged floats once (unrolled over the T slots behind the wave-uniform `j < t`), loads its 2 S state doubles and
+// A lane reads its t staged floats once (fold_parts.hip.h: stage_read, as doubles), loads its 2 S state doubles and
 // runs the cascade over the captures in order; e_j takes p_j's place in registers, E is added and E and the state are stored.  Then
 // it walks the frequencies in chunks of kModulationChunk, as spectrum_fold_kernel does: load Re and Im of the chunk, apply the t values
 // of e in order, store.  S is a template parameter and the section loop is unrolled, so the state stays in registers.  No LDS, no
@@ -32,6 +32,7 @@
 
 #include <cstdint>
 
+#include "fold_parts.hip.h"
 #include "modulation_plan.h"
 
 namespace wv {
@@ -51,10 +52,8 @@ __global__ void __launch_bounds__(256) modulation_fold_kernel(const float* __res
     if (node >= nodes || t < 1) return;
     const uint32_t band = blockIdx.y;
     const int M = n_freqs;
-    double e[kModulationStage];  // the captures, then their filtered squares
-#pragma unroll
-    for (int j = 0; j < kModulationStage; ++j)
-        if (j < t) e[j] = (double)stage[(uint64_t)j * nodes + node];
+    double e[kModulationStage][1];  // the captures, then their filtered squares
+    stage_read(stage, nodes, node, t, e);
     const double* c = coef + (uint64_t)band * (S * 5);
     double b0[S], b1[S], b2[S], a1[S], a2[S];
 #pragma unroll
@@ -68,7 +67,7 @@ __global__ void __launch_bounds__(256) modulation_fold_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < kModulationStage; ++j) {
         if (j < t) {
-            double x = e[j];
+            double x = e[j][0];
 #pragma unroll
             for (int s = 0; s < S; ++s) {
                 const double out = x * b0[s] + z1[s];
@@ -76,8 +75,8 @@ __global__ void __launch_bounds__(256) modulation_fold_kernel(const float* __res
                 z2[s] = x * b2[s] - a2[s] * out;
                 x = out;
             }
-            e[j] = x * x;
-            energy = energy + e[j];
+            e[j][0] = x * x;
+            energy = energy + e[j][0];
         }
     }
     planes[0] = energy;
@@ -100,8 +99,8 @@ __global__ void __launch_bounds__(256) modulation_fold_kernel(const float* __res
                 for (int mm = 0; mm < kModulationChunk; ++mm) {
                     if (m0 + mm < M) {
                         const double* w = tw + ((int64_t)j * M + (m0 + mm)) * 2;  // (no lane in it)
-                        re[mm] = re[mm] + e[j] * w[0];
-                        im[mm] = im[mm] - e[j] * w[1];
+                        re[mm] = re[mm] + e[j][0] * w[0];
+                        im[mm] = im[mm] - e[j][0] * w[1];
                     }
                 }
             }

@@ -433,14 +433,7 @@ class Engine:
         self.h = handle
         self.n_recv = 0
         self.n_directional = 0
-        self.snapshot_shape = None
-        self.spectrum_shape = None
-        self.decay_shape = None
-        self.decay_banded = False
-        self.intensity_shape = None
-        self.arrival_shape = None
-        self.lateral_shape = None
-        self.modulation_shape = None
+        self._plan_state()
 
     @classmethod
     def from_handle(cls, handle, mesh, precision):
@@ -453,15 +446,14 @@ class Engine:
         eng.h = handle
         eng.n_recv = 0
         eng.n_directional = 0
-        eng.snapshot_shape = None
-        eng.spectrum_shape = None
-        eng.decay_shape = None
-        eng.decay_banded = False
-        eng.intensity_shape = None
-        eng.arrival_shape = None
-        eng.lateral_shape = None
-        eng.modulation_shape = None
+        eng._plan_state()
         return eng
+
+    def _plan_state(self):
+        """What this layer remembers of the capture plans: the shape a fetch returns, None while the plan is not set."""
+        self.snapshot_shape = self.spectrum_shape = self.decay_shape = self.intensity_shape = None
+        self.arrival_shape = self.lateral_shape = self.modulation_shape = None
+        self.decay_banded = False
 
     def close(self):
         if getattr(self, "h", None):
@@ -601,9 +593,7 @@ class Engine:
         update).  set_snapshots(None) stops recording and forgets what is held.  Returns the shape
         (nz, ny, nx) of one snapshot."""
         if box is None:
-            _check(self.lib.wv_set_snapshots(self.h, None))
-            self.snapshot_shape = None
-            return None
+            return self._stop_plan("snapshot", self.lib.wv_set_snapshots, None)
         plan = WvSnapshotPlan()
         taken = self._fill_box(plan, box, stride)
         plan.first_step, plan.period, plan.keep = int(first_step), int(period), int(keep)
@@ -627,11 +617,49 @@ class Engine:
         plan.sx, plan.sy, plan.sz = (int(v) for v in stride)
         return taken
 
+    def _stop_plan(self, name, setter, *nulls):
+        """A setter given None: the plan stops and its state is forgotten, here and in the library."""
+        _check(setter(self.h, *nulls))
+        setattr(self, name + "_shape", None)
+
+    def _count(self, fn):
+        """A wv_*_count call: its two uint64 results."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(fn(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _interior_box(self):
+        """The mesh without its faces: every node of it has its six neighbours on the grid."""
+        return ((1, 1, 1), tuple(d - 2 for d in self.mesh.dims))
+
+    @staticmethod
+    def _fill_edges(plan, edges, most, who):
+        """The bin edges counted from a node's own onset -> the plan's n_bins and edges; returns n_bins."""
+        edges = [int(v) for v in edges]
+        if len(edges) > most:
+            raise ValueError("%s: %d bins at the most" % (who, most))
+        plan.n_bins = len(edges)
+        for k, v in enumerate(edges):
+            plan.edges[k] = v
+        return len(edges)
+
+    @staticmethod
+    def _fill_constants(plan, spacing, sample_rate, ambient_density):
+        plan.spacing, plan.sample_rate, plan.ambient_density = float(spacing), float(sample_rate), float(ambient_density)
+
+    @staticmethod
+    def _threshold_map(threshold_map, taken, who):
+        """A per-node threshold map as the library takes it: (the float32 array, which has to outlive the call; its pointer) or (None, None)."""
+        if threshold_map is None:
+            return None, None
+        threshold_map = np.ascontiguousarray(threshold_map, dtype=np.float32)
+        if threshold_map.shape != (taken[2], taken[1], taken[0]):
+            raise ValueError("%s: the threshold map must have the box's shape %r" % (who, (taken[2], taken[1], taken[0])))
+        return threshold_map, threshold_map.ctypes.data_as(C.c_void_p)
+
     def snapshot_count(self):
         """wv_snapshot_count: (snapshots taken since the plan was set, index of the oldest one still held)."""
-        taken, first = C.c_uint64(), C.c_uint64()
-        _check(self.lib.wv_snapshot_count(self.h, C.byref(taken), C.byref(first)))
-        return taken.value, first.value
+        return self._count(self.lib.wv_snapshot_count)
 
     def fetch_snapshots(self, first=None, n=None):
         """wv_fetch_snapshots: snapshots [first, first + n) as (float32[n, nz, ny, nx], steps uint64[n]); by default all that are held."""
@@ -652,9 +680,7 @@ class Engine:
         the twiddles spectrum_twiddle gives -- a NumPy loop over the snapshots of the same plan reproduces it bit for bit.  No window.
         Excludes a snapshot plan.  set_spectrum(None) stops and forgets.  Returns the shape (K, nz, ny, nx)."""
         if freqs is None:
-            _check(self.lib.wv_set_spectrum(self.h, None, None))
-            self.spectrum_shape = None
-            return None
+            return self._stop_plan("spectrum", self.lib.wv_set_spectrum, None, None)
         f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
         plan = WvSpectrumPlan()
         taken = self._fill_box(plan, box, stride)
@@ -665,9 +691,7 @@ class Engine:
 
     def spectrum_count(self):
         """wv_spectrum_count: (captures of completed steps since the plan was set, the step of the last of them)."""
-        captures, last = C.c_uint64(), C.c_uint64()
-        _check(self.lib.wv_spectrum_count(self.h, C.byref(captures), C.byref(last)))
-        return captures.value, last.value
+        return self._count(self.lib.wv_spectrum_count)
 
     def fetch_spectrum(self):
         """wv_fetch_spectrum: (complex128[K, nz, ny, nx], captures in it).  The plan keeps running."""
@@ -690,8 +714,7 @@ class Engine:
         its own (decay.banded_bins is the same in NumPy, bit for bit).  The series the filters see is sampled every `period` steps:
         design the sections for sample_rate / period.  Returns the shape (K, n_bins, nz, ny, nx).  None: the plain plan."""
         if n_bins is None:
-            _check(self.lib.wv_set_decay(self.h, None))   # (stops either kind of plan)
-            self.decay_shape = None
+            self._stop_plan("decay", self.lib.wv_set_decay, None)   # (stops either kind of plan)
             self.decay_banded = False
             return None
         if bands is not None:
@@ -715,9 +738,7 @@ class Engine:
 
     def decay_count(self):
         """wv_decay_count: (captures of completed steps since the plan was set, the step of the last of them)."""
-        captures, last = C.c_uint64(), C.c_uint64()
-        _check(self.lib.wv_decay_count(self.h, C.byref(captures), C.byref(last)))
-        return captures.value, last.value
+        return self._count(self.lib.wv_decay_count)
 
     def fetch_decay(self, banded=None):
         """wv_fetch_decay: (float64[n_bins, nz, ny, nx], captures in it); under a banded plan wv_fetch_decay_bands:
@@ -725,7 +746,7 @@ class Engine:
         plan (the library refuses the wrong one)."""
         out = np.zeros(tuple(self.decay_shape or (0, 0, 0, 0)), dtype=np.float64)   # (no plan: the library says so)
         captures = C.c_uint64()
-        if getattr(self, "decay_banded", False) if banded is None else banded:
+        if self.decay_banded if banded is None else banded:
             _check(self.lib.wv_fetch_decay_bands(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
         else:
             _check(self.lib.wv_fetch_decay(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
@@ -742,35 +763,31 @@ class Engine:
         reproduces bins and velocities bit for bit.  Excludes every other plan.  set_intensity(None) stops and forgets.  Returns the
         shape (4, n_bins, nz, ny, nx): Ix, Iy, Iz, E."""
         if n_bins is None:
-            _check(self.lib.wv_set_intensity(self.h, None))
-            self.intensity_shape = None
-            return None
+            return self._stop_plan("intensity", self.lib.wv_set_intensity, None)
         if box is None:
-            box = ((1, 1, 1), tuple(d - 2 for d in self.mesh.dims))
+            box = self._interior_box()
         plan = WvIntensityPlan()
         taken = self._fill_box(plan, box, stride)
         plan.first_step, plan.period, plan.n_bins, plan.bin_captures = int(first_step), int(period), int(n_bins), int(bin_captures)
-        plan.spacing, plan.sample_rate, plan.ambient_density = float(spacing), float(sample_rate), float(ambient_density)
+        self._fill_constants(plan, spacing, sample_rate, ambient_density)
         _check(self.lib.wv_set_intensity(self.h, C.byref(plan)))
         self.intensity_shape = (4, int(n_bins), taken[2], taken[1], taken[0])
         return self.intensity_shape
 
     def intensity_count(self):
         """wv_intensity_count: (captures of completed steps since the plan was set, the step of the last of them)."""
-        captures, last = C.c_uint64(), C.c_uint64()
-        _check(self.lib.wv_intensity_count(self.h, C.byref(captures), C.byref(last)))
-        return captures.value, last.value
+        return self._count(self.lib.wv_intensity_count)
 
     def fetch_intensity(self):
         """wv_fetch_intensity: (float64[4, n_bins, nz, ny, nx] = Ix, Iy, Iz, E, captures in it).  The plan keeps running."""
-        out = np.zeros(tuple(getattr(self, "intensity_shape", None) or (0, 0, 0, 0, 0)), dtype=np.float64)   # (no plan: the library says so)
+        out = np.zeros(tuple(self.intensity_shape or (0, 0, 0, 0, 0)), dtype=np.float64)   # (no plan: the library says so)
         captures = C.c_uint64()
         _check(self.lib.wv_fetch_intensity(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
         return out, captures.value
 
     def fetch_intensity_velocity(self):
         """wv_fetch_intensity_velocity: float64[3, nz, ny, nx], the velocities the integrator carries, after the captures folded so far."""
-        shape = getattr(self, "intensity_shape", None)
+        shape = self.intensity_shape
         out = np.zeros((3,) + tuple(shape[2:]) if shape else (0, 0, 0, 0), dtype=np.float64)
         _check(self.lib.wv_fetch_intensity_velocity(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
@@ -790,35 +807,24 @@ class Engine:
         reproduces all of it bit for bit.  Excludes every other plan.  set_arrival(None) stops and forgets.  Returns the shape of the
         bins, (n_bins, nz, ny, nx)."""
         if edges is None:
-            _check(self.lib.wv_set_arrival(self.h, None, None))
-            self.arrival_shape = None
-            return None
-        edges = [int(v) for v in edges]
-        if len(edges) > 16:
-            raise ValueError("set_arrival: 16 bins at the most")
+            return self._stop_plan("arrival", self.lib.wv_set_arrival, None, None)
         plan = WvArrivalPlan()
+        n_bins = self._fill_edges(plan, edges, 16, "set_arrival")
         taken = self._fill_box(plan, box, stride)
-        plan.first_step, plan.period, plan.n_bins, plan.threshold = int(first_step), int(period), len(edges), float(threshold)
-        for k, v in enumerate(edges):
-            plan.edges[k] = v
-        if threshold_map is not None:
-            threshold_map = np.ascontiguousarray(threshold_map, dtype=np.float32)
-            if threshold_map.shape != (taken[2], taken[1], taken[0]):
-                raise ValueError("set_arrival: the threshold map must have the box's shape %r" % ((taken[2], taken[1], taken[0]),))
-        _check(self.lib.wv_set_arrival(self.h, C.byref(plan), threshold_map.ctypes.data_as(C.c_void_p) if threshold_map is not None else None))
-        self.arrival_shape = (len(edges), taken[2], taken[1], taken[0])
+        plan.first_step, plan.period, plan.threshold = int(first_step), int(period), float(threshold)
+        threshold_map, map_pointer = self._threshold_map(threshold_map, taken, "set_arrival")
+        _check(self.lib.wv_set_arrival(self.h, C.byref(plan), map_pointer))
+        self.arrival_shape = (n_bins, taken[2], taken[1], taken[0])
         return self.arrival_shape
 
     def arrival_count(self):
         """wv_arrival_count: (captures of completed steps since the plan was set, the step of the last of them)."""
-        captures, last = C.c_uint64(), C.c_uint64()
-        _check(self.lib.wv_arrival_count(self.h, C.byref(captures), C.byref(last)))
-        return captures.value, last.value
+        return self._count(self.lib.wv_arrival_count)
 
     def fetch_arrival(self):
         """wv_fetch_arrival: (dict(onset=uint32[nz, ny, nx], peak=float32, peak_capture=uint32, pre=float64, moment=float64,
         bins=float64[n_bins, nz, ny, nx]), captures in them).  ARRIVAL_NONE marks a node without an onset.  The plan keeps running."""
-        shape = tuple(getattr(self, "arrival_shape", None) or (0, 0, 0, 0))   # (no plan: the library says so)
+        shape = tuple(self.arrival_shape or (0, 0, 0, 0))   # (no plan: the library says so)
         out = dict(onset=np.zeros(shape[1:], np.uint32), peak=np.zeros(shape[1:], np.float32), peak_capture=np.zeros(shape[1:], np.uint32),
                    pre=np.zeros(shape[1:], np.float64), moment=np.zeros(shape[1:], np.float64), bins=np.zeros(shape, np.float64))
         captures = C.c_uint64()
@@ -837,38 +843,25 @@ class Engine:
         reproduces all of it bit for bit.  Excludes every other plan.  set_lateral(None) stops and forgets.  Returns the shape of the
         bins, (10, n_bins, nz, ny, nx): E, Ix, Iy, Iz, Qxx, Qyy, Qzz, Qxy, Qxz, Qyz."""
         if edges is None:
-            _check(self.lib.wv_set_lateral(self.h, None, None))
-            self.lateral_shape = None
-            return None
-        edges = [int(v) for v in edges]
-        if len(edges) > 8:
-            raise ValueError("set_lateral: 8 bins at the most")
-        if box is None:
-            box = ((1, 1, 1), tuple(d - 2 for d in self.mesh.dims))
+            return self._stop_plan("lateral", self.lib.wv_set_lateral, None, None)
         plan = WvLateralPlan()
-        taken = self._fill_box(plan, box, stride)
-        plan.first_step, plan.period, plan.n_bins, plan.threshold = int(first_step), int(period), len(edges), float(threshold)
-        for k, v in enumerate(edges):
-            plan.edges[k] = v
-        plan.spacing, plan.sample_rate, plan.ambient_density = float(spacing), float(sample_rate), float(ambient_density)
-        if threshold_map is not None:
-            threshold_map = np.ascontiguousarray(threshold_map, dtype=np.float32)
-            if threshold_map.shape != (taken[2], taken[1], taken[0]):
-                raise ValueError("set_lateral: the threshold map must have the box's shape %r" % ((taken[2], taken[1], taken[0]),))
-        _check(self.lib.wv_set_lateral(self.h, C.byref(plan), threshold_map.ctypes.data_as(C.c_void_p) if threshold_map is not None else None))
-        self.lateral_shape = (10, len(edges), taken[2], taken[1], taken[0])
+        n_bins = self._fill_edges(plan, edges, 8, "set_lateral")
+        taken = self._fill_box(plan, self._interior_box() if box is None else box, stride)
+        plan.first_step, plan.period, plan.threshold = int(first_step), int(period), float(threshold)
+        self._fill_constants(plan, spacing, sample_rate, ambient_density)
+        threshold_map, map_pointer = self._threshold_map(threshold_map, taken, "set_lateral")
+        _check(self.lib.wv_set_lateral(self.h, C.byref(plan), map_pointer))
+        self.lateral_shape = (10, n_bins, taken[2], taken[1], taken[0])
         return self.lateral_shape
 
     def lateral_count(self):
         """wv_lateral_count: (captures of completed steps since the plan was set, the step of the last of them)."""
-        captures, last = C.c_uint64(), C.c_uint64()
-        _check(self.lib.wv_lateral_count(self.h, C.byref(captures), C.byref(last)))
-        return captures.value, last.value
+        return self._count(self.lib.wv_lateral_count)
 
     def fetch_lateral(self):
         """wv_fetch_lateral: (dict(onset=uint32[nz, ny, nx], pre=float64[nz, ny, nx], velocity=float64[3, nz, ny, nx],
         bins=float64[10, n_bins, nz, ny, nx]), captures in them).  ARRIVAL_NONE marks a node without an onset.  The plan keeps running."""
-        shape = tuple(getattr(self, "lateral_shape", None) or (0, 0, 0, 0, 0))   # (no plan: the library says so)
+        shape = tuple(self.lateral_shape or (0, 0, 0, 0, 0))   # (no plan: the library says so)
         out = dict(onset=np.zeros(shape[2:], np.uint32), pre=np.zeros(shape[2:], np.float64), velocity=np.zeros((3,) + shape[2:], np.float64),
                    bins=np.zeros(shape, np.float64))
         captures = C.c_uint64()
@@ -885,9 +878,7 @@ class Engine:
         frequency -- modulation.modulation_fold over the snapshots of the same plan reproduces all of it bit for bit.  Excludes every
         other plan.  set_modulation(None, None) stops and forgets.  Returns the shape (K, M, nz, ny, nx)."""
         if freqs is None:
-            _check(self.lib.wv_set_modulation(self.h, None, None, None, 0, 0))
-            self.modulation_shape = None
-            return None
+            return self._stop_plan("modulation", self.lib.wv_set_modulation, None, None, None, 0, 0)
         f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
         sections = np.ascontiguousarray(bands, dtype=np.float64)
         if sections.ndim != 3 or sections.shape[2] != 5:
@@ -902,14 +893,12 @@ class Engine:
 
     def modulation_count(self):
         """wv_modulation_count: (captures of completed steps since the plan was set, the step of the last of them)."""
-        captures, last = C.c_uint64(), C.c_uint64()
-        _check(self.lib.wv_modulation_count(self.h, C.byref(captures), C.byref(last)))
-        return captures.value, last.value
+        return self._count(self.lib.wv_modulation_count)
 
     def fetch_modulation(self):
         """wv_fetch_modulation: (energy float64[K, nz, ny, nx], sums complex128[K, M, nz, ny, nx]).  They hold every capture
         modulation_count counts.  The plan keeps running."""
-        shape = tuple(getattr(self, "modulation_shape", None) or (0, 0, 0, 0, 0))   # (no plan: the library says so)
+        shape = tuple(self.modulation_shape or (0, 0, 0, 0, 0))   # (no plan: the library says so)
         energy = np.zeros(shape[:1] + shape[2:], dtype=np.float64)
         sums = np.zeros(shape, dtype=np.complex128)
         _check(self.lib.wv_fetch_modulation(self.h, energy.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p), None))
