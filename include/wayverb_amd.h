@@ -784,6 +784,75 @@ int wv_modulation_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
 int wv_fetch_modulation(wv_engine* e, double* energy /* [n_bands][nz][ny][nx] */,
                         double* sums /* [n_bands][n_freqs][nz][ny][nx][2]: complex128 */, uint64_t* captures);
 
+/* ---- band-limited arrival maps: octave-band clarity, centre time and decay per seat, from one run -- */
+/* ISO 3382-1 quotes its figures per octave band.  A banded decay plan gives EDT / T20 / T30 per band; an arrival plan gives C50 / C80,
+ * D50 and Ts broadband only, with the dispersive top of an impulse-driven mesh's spectrum in both windows; and the plans exclude each
+ * other, so both families cost two runs.  wv_set_arrival_bands is the arrival plan with the banded decay plan's filter bank ahead of
+ * the square, and a bin table that can carry a uniform tail behind the explicit edges: per node the BROADBAND onset and peak, and
+ * per band the energy ahead of the onset, the first time moment and the squares binned from the node's own onset -- the early windows
+ * and the Schroeder curve behind them.  8 + 4 + 8 n_bands (2 + n_bins) bytes per node cross the link when the caller asks.
+ *
+ * Definition.  p_c is the float a snapshot of the same plan holds for the node; c = 0, 1, ... counts the committed captures since the
+ * plan was set; thr as in the arrival plan.  n_bins = n_edges + n_tail.  The state starts as onset = NONE (0xFFFFFFFF), peak = +0.0f,
+ * peak_capture = NONE, every pre[k] = M[k] = E[k][b] = z1 = z2 = +0.0, and per capture, in capture order:
+ *     a = fabsf(p_c);  if (a > peak) { peak = a; peak_capture = c; }      strict: the FIRST occurrence; a NaN changes nothing
+ *     if (onset == NONE && a >= thr) onset = c;                           the BROADBAND onset, one per node, as wv_set_arrival finds it
+ *     for every band k:
+ *         x = (double)p_c;  n_sections sections in series, exactly wv_set_decay_bands' three lines per section, nothing contracted;
+ *         y = x after the last;  sq = y * y                               (rounded)
+ *         if (onset == NONE)  pre[k] = pre[k] + sq;
+ *         else { d = c - onset;  rel = d > lag[k] ? d - lag[k] : 0;
+ *                b = bin(rel);  E[k][b] = E[k][b] + sq;  M[k] = M[k] + (double)rel * sq; }
+ *     bin(rel) = (n_tail > 0 && rel >= tail_first) ? n_edges + min((rel - tail_first) / tail_captures, n_tail - 1)
+ *                                                  : the largest j with edges[j] <= rel
+ * The filters run from capture 0 on every node, before and after its onset.  Windows are counted from the broadband onset, as ISO
+ * practice has it; a causal band filter delivers the direct sound late, so the captures [onset, onset + lag[k]) stay in bin 0 with
+ * rel = 0 -- no early energy is lost to `pre`, and the window's far edge moves by the lag.  lag = 0 is the plain reading.  A NumPy loop
+ * that evaluates these lines (wayverb_amd/arrival.py: banded_arrival_fold; the onset and peak lines on float32, the rest on float64)
+ * reproduces every output AND the filter states BIT FOR BIT.  Two consequences, both bytewise:
+ *   1. identity sections reproduce the arrival plan: with one band, lag = 0, n_tail = 0 and the section b0 = 1, b1 = b2 = a1 = a2 = 0,
+ *      y == x and all six outputs equal wv_set_arrival's with the same edges and threshold
+ *   2. threshold 0 reproduces the banded decay plan: with threshold 0, n_edges = 1, tail_first = tail_captures = W and n_tail = n - 1
+ *      every onset is capture 0 and the bins equal wv_set_decay_bands' with bin_captures = W, n_bins = n
+ *
+ * Refused with WV_E_INVALID_ARGUMENT, in this order: a zero stride, a zero period, a box that leaves the mesh (the shared checks);
+ * n_bands outside 1 .. 8, n_sections outside 1 .. 4, a coefficient that is not finite; n_edges outside 1 .. 16, edges[0] != 0 or
+ * edges not strictly increasing, a threshold (or an entry of the map) that is negative or not finite; n_tail > 4096 - n_edges, with
+ * a tail tail_first <= edges[n_edges - 1] or tail_captures == 0, reserved != 0.  Everything else is the arrival plan's rule, word for
+ * word: everything is allocated when the plan is set (the stage, 64 bytes per node; 12 + 8 n_bands (2 + n_bins) + 4 n_bands bytes of
+ * sums -- every band keeps a copy of the onset -- and 16 n_sections n_bands bytes of filter state per node; the map's copy), and with
+ * no room the call answers WV_E_HIP and leaves the engine and any earlier plan untouched; a NULL plan stops, forgets and frees; one
+ * domain only, and wv_run_group refuses an engine with a plan; the plan excludes every other plan and every other setter answers
+ * WV_E_STATE while it is active; wv_step / wv_swap capture nothing; captures are numbered with 32 bits; after a stop on a flag at step
+ * f nothing of a later step is in any sum OR any filter state; wv_checkpoint folds what is staged and copies sums and filter states
+ * aside, wv_rollback puts them back; with a plan the fields, receiver rows and flags are bit-identical to a run without one.
+ *
+ * wv_arrival_bands_count: as wv_decay_count.  wv_fetch_arrival_bands: onset, peak and peak_capture are [nz][ny][nx], pre and moment
+ * float64 [n_bands][nz][ny][nx], bins float64 [n_bands][n_bins][nz][ny][nx]; ANY destination may be NULL and is then skipped.
+ * The struct is 176 bytes: nine int32 from 0, first_step at 40, period at 48, n_edges at 56, threshold at 60, edges at 64, n_tail at
+ * 128, tail_first at 132, tail_captures at 136, lag at 140, reserved at 172. */
+typedef struct wv_arrival_bands_plan {
+    int32_t x0, y0, z0;      /* first node of the box */
+    int32_t nx, ny, nz;      /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;      /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step;     /* captures at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;         /* >= 1 */
+    uint32_t n_edges;        /* 1 .. 16 explicit bins */
+    float    threshold;      /* >= 0, finite; used where threshold_map is NULL */
+    uint32_t edges[16];      /* edges[0] == 0, strictly increasing over n_edges entries: captures behind the onset */
+    uint32_t n_tail;         /* 0 .. 4096 - n_edges uniform bins behind the explicit ones */
+    uint32_t tail_first;     /* n_tail > 0: first relative capture of tail bin 0, > edges[n_edges - 1] */
+    uint32_t tail_captures;  /* n_tail > 0: W >= 1 captures per tail bin; the LAST bin of the plan is open-ended */
+    uint32_t lag[8];         /* per band: captures by which the band's clock starts late (the filter's delay); entries >= n_bands ignored */
+    uint32_t reserved;       /* 0 */
+} wv_arrival_bands_plan;
+int wv_set_arrival_bands(wv_engine* e, const wv_arrival_bands_plan* plan, const float* threshold_map /* [nz][ny][nx] or NULL */,
+                         const wv_biquad* sections /* [n_bands][n_sections] */, uint32_t n_bands, uint32_t n_sections);
+int wv_arrival_bands_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
+int wv_fetch_arrival_bands(wv_engine* e, uint32_t* onset, float* peak, uint32_t* peak_capture /* [nz][ny][nx] */,
+                           double* pre, double* moment /* [n_bands][nz][ny][nx] */,
+                           double* bins /* [n_bands][n_bins][nz][ny][nx] */, uint64_t* captures);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */
@@ -827,7 +896,8 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *   WV_QUERY_ARRIVAL_CAPTURES, WV_QUERY_ARRIVAL_FOLDS, WV_QUERY_ARRIVAL_NS   the decay plan's three since wv_set_arrival
  *   WV_QUERY_LATERAL_CAPTURES, WV_QUERY_LATERAL_FOLDS, WV_QUERY_LATERAL_NS, WV_QUERY_LATERAL_GATHER_NS, WV_QUERY_LATERAL_GATHERS
  *                            the intensity plan's five since wv_set_lateral
- *   WV_QUERY_MODULATION_CAPTURES, WV_QUERY_MODULATION_FOLDS, WV_QUERY_MODULATION_NS   the decay plan's three since wv_set_modulation */
+ *   WV_QUERY_MODULATION_CAPTURES, WV_QUERY_MODULATION_FOLDS, WV_QUERY_MODULATION_NS   the decay plan's three since wv_set_modulation
+ *   WV_QUERY_ARRIVAL_BANDS_CAPTURES, WV_QUERY_ARRIVAL_BANDS_FOLDS, WV_QUERY_ARRIVAL_BANDS_NS   the decay plan's three since wv_set_arrival_bands */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -851,7 +921,8 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
        WV_QUERY_ARRIVAL_CAPTURES = 37, WV_QUERY_ARRIVAL_FOLDS = 38, WV_QUERY_ARRIVAL_NS = 39,
        WV_QUERY_LATERAL_CAPTURES = 40, WV_QUERY_LATERAL_FOLDS = 41, WV_QUERY_LATERAL_NS = 42,
        WV_QUERY_LATERAL_GATHER_NS = 43, WV_QUERY_LATERAL_GATHERS = 44,
-       WV_QUERY_MODULATION_CAPTURES = 45, WV_QUERY_MODULATION_FOLDS = 46, WV_QUERY_MODULATION_NS = 47 };
+       WV_QUERY_MODULATION_CAPTURES = 45, WV_QUERY_MODULATION_FOLDS = 46, WV_QUERY_MODULATION_NS = 47,
+       WV_QUERY_ARRIVAL_BANDS_CAPTURES = 48, WV_QUERY_ARRIVAL_BANDS_FOLDS = 49, WV_QUERY_ARRIVAL_BANDS_NS = 50 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

@@ -94,6 +94,15 @@ def main():
     ap.add_argument("--arrival-threshold", type=float, default=1e-4,
                     help="the pressure magnitude that counts as the arrival of the direct sound (default 1e-4; the source's impulse is 1)")
     ap.add_argument("--arrival-every", type=int, default=1, help="capture every N-th step (arrival times are then known to N steps)")
+    ap.add_argument("--clarity-bands", default=None, metavar="HZ,HZ,...",
+                    help="with --clarity-map: octave-band centres (8 at the most); the maps are then per band -- every capture goes through "
+                         "a 4th-order Butterworth band-pass ahead of the square (Engine.set_arrival_bands), every band's clock starting "
+                         "late by its filter's group delay -- and --arrival-out holds pre, moment [K, ny, nx], bins [K, n_bins, ny, nx], "
+                         "bands_hz, lag, tail and c50_db, c80_db, d50, ts_s, edt_s, t20_s, t30_s [K, ny, nx]")
+    ap.add_argument("--clarity-tail-ms", type=float, default=None,
+                    help="with --clarity-bands: uniform bins behind the 80 ms edge out to this many milliseconds behind each node's arrival, "
+                         "from which the per-band EDT, T20 and T30 are read (default: none, and those maps are NaN)")
+    ap.add_argument("--clarity-tail-bin-ms", type=float, default=10.0, help="the length of a tail bin (default 10 ms)")
     ap.add_argument("--arrival-out", default="arrival.npz",
                     help="the maps go here: onset, peak, peak_capture, pre, moment [ny, nx], bins [3, ny, nx], edges, arrival_s, direct_db, "
                          "c50_db, c80_db, d50, d80, ts_s, pre_fraction, captures, period, sample_rate, plane, origin, spacing")
@@ -244,6 +253,14 @@ def main():
             ap.error("--arrival-every must be >= 1 and --arrival-threshold >= 0 and finite")
         arrival = dict(plane=float(args.arrival_plane[2:]) if args.arrival_plane else args.receiver[2], every=args.arrival_every,
                        threshold=args.arrival_threshold, early_ms=(50.0, 80.0))
+        if args.clarity_bands:
+            from wayverb_amd import decay as D
+            centres = [float(v) for v in args.clarity_bands.split(",")]
+            if not 1 <= len(centres) <= 8 or any(not c > 0 for c in centres):
+                ap.error("--clarity-bands takes 1 .. 8 positive octave centres")
+            arrival.update(bands=D.octave_band_edges(centres), tail_ms=args.clarity_tail_ms, tail_bin_ms=args.clarity_tail_bin_ms, lag="group-delay")
+    elif args.clarity_bands:
+        ap.error("--clarity-bands goes with --clarity-map")
     lateral = None
     if args.lateral_map:
         if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None:
@@ -353,7 +370,31 @@ def main():
             print("wrote lateral maps of plane z=%d (%d captures; %d of %d nodes heard an arrival; median LF %s) to %s"
                   % (plan["box"][0][2], captures, heard.sum(), heard.size, "%.3f" % np.nanmedian(lf) if np.isfinite(lf).any() else "not defined",
                      args.lateral_out))
-        if arrival is not None:
+        if arrival is not None and "bands" in arrival:
+            from wayverb_amd import arrival as A
+            env, mesh = W.Environment(), audio_etc[2].mesh
+            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
+            plan = W.arrival_bands_plan_arguments(arrival, mesh, rate)
+            out, captures = audio_etc[3]
+            # the one plane: onset, peak, peak_capture [ny, nx]; pre, moment [K, ny, nx]; bins [K, n_bins, ny, nx]
+            out = {k: (v[:, :, 0] if k == "bins" else v[:, 0] if k in ("pre", "moment") else v[0]) for k, v in out.items()}
+            edges, tail, period = plan["edges"], plan["tail"], plan["period"]
+            maps = dict(arrival_s=A.arrival_time(out["onset"], plan["first_step"], period, rate), direct_db=A.direct_level_db(out["peak"]),
+                        c50_db=A.band_clarity(out["bins"], edges, 50.0, period, rate), c80_db=A.band_clarity(out["bins"], edges, 80.0, period, rate),
+                        d50=A.band_definition(out["bins"], edges, 50.0, period, rate), ts_s=A.band_centre_time(out["moment"], out["bins"], period, rate))
+            decays = A.band_decay_maps(out["bins"], edges, tail, period, rate)
+            maps.update({k: decays[k] for k in ("edt_s", "t20_s", "t30_s")})
+            np.savez(args.arrival_out, edges=np.array(edges), tail=np.array(tail or (0, 0, 0)), lag=np.array(plan["lag"]),
+                     bands_hz=np.array([float(v) for v in args.clarity_bands.split(",")]), captures=captures, period=period, sample_rate=rate,
+                     plane=plan["box"][0][2], spacing=mesh.spacing,
+                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64),
+                     **out, **maps)
+            heard = out["onset"] != A.NONE
+            print("wrote arrival maps of plane z=%d in %d bands (%d captures; %d of %d nodes heard an arrival; median C80 per band %s) to %s"
+                  % (plan["box"][0][2], out["bins"].shape[0], captures, heard.sum(), heard.size,
+                     ", ".join("%.1f dB" % np.median(c[np.isfinite(c)]) if np.isfinite(c).any() else "not defined" for c in maps["c80_db"]),
+                     args.arrival_out))
+        elif arrival is not None:
             from wayverb_amd import arrival as A
             env, mesh = W.Environment(), audio_etc[2].mesh
             rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)

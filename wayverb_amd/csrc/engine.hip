@@ -21,6 +21,7 @@
 #include "engine_arrival.hip.h"
 #include "engine_lateral.hip.h"
 #include "engine_modulation.hip.h"
+#include "engine_arrival_bands.hip.h"
 #include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
@@ -304,6 +305,20 @@ int wv_modulation_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
 int wv_fetch_modulation(wv_engine* e, double* energy, double* sums, uint64_t* captures) {
     WV_NEED(e);
     return e->fetch_modulation(energy, sums, captures);
+}
+int wv_set_arrival_bands(wv_engine* e, const wv_arrival_bands_plan* plan, const float* threshold_map, const wv_biquad* sections, uint32_t n_bands,
+                         uint32_t n_sections) {
+    WV_NEED(e);
+    return e->set_arrival_bands(plan, threshold_map, sections, n_bands, n_sections);
+}
+int wv_arrival_bands_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
+    WV_NEED(e);
+    return e->arrival_bands_count(captures, last_step);
+}
+int wv_fetch_arrival_bands(wv_engine* e, uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins,
+                           uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_arrival_bands(onset, peak, peak_capture, pre, moment, bins, captures);
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

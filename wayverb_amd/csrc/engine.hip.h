@@ -18,12 +18,12 @@
 //   engine_snapshot.hip.h  field snapshots taken on the device while a run goes on (wv_set_snapshots): plan, ring, capture, copy stream, held log
 //   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape; what every
 //                        plan's setter checks: the box of a plan, the four shared refusals, frequencies, coefficients, physical constants
-//   engine_staged.hip.h  the life cycle the six accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release;
+//   engine_staged.hip.h  the life cycle the seven accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release;
 //                        the host-written tables of a fold (bins, twiddles), the threshold map, the fetch of complex sums
 //   fold_parts.hip.h     the device pieces more than one fold kernel has and that leave its assembly alone: stage read, integrator step, onset rule
 //   engine_spectrum.hip.h  field spectra accumulated on the device while a run goes on (wv_set_spectrum): plan, stage, fold, fetch
 //   spectrum_plan.h      (host only, no HIP) free slots of the stage, when a fold is due, which captures survive a stop, sizes
-//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the six accumulating plans
+//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the seven accumulating plans
 //   engine_decay.hip.h   time-binned field energy accumulated on the device while a run goes on (wv_set_decay): plan, stage, fold, fetch
 //   decay_plan.h         (host only, no HIP) the bin of a capture, sizes, the fold's traffic model
 //   decay_bands_kernels.hip.h   the fold of a band-limited decay plan (wv_set_decay_bands): biquad cascades ahead of the square
@@ -39,6 +39,9 @@
 //   engine_modulation.hip.h  band energies and their Fourier sums at modulation frequencies of a box (wv_set_modulation): plan, stage, fold, fetch
 //   modulation_plan.h    (host only, no HIP) what a modulation plan is refused for, sizes and places, the fold's traffic model
 //   modulation_kernels.hip.h  its fold: decay_bands_fold_kernel's cascade ahead of spectrum_fold_kernel's running Fourier sum
+//   engine_arrival_bands.hip.h  per octave band, energy of a box binned from each node's OWN arrival, with a uniform tail (wv_set_arrival_bands)
+//   arrival_bands_plan.h  (host only, no HIP) the tail, the bin of a capture behind an onset and a lag, sizes and places, the traffic model
+//   arrival_bands_kernels.hip.h  its fold: decay_bands_fold_kernel's cascade ahead of arrival_fold_kernel's onset and bins
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -52,6 +55,7 @@
 #include "arrival_plan.h"
 #include "lateral_plan.h"
 #include "modulation_plan.h"
+#include "arrival_bands_plan.h"
 #include "capture_stage.h"
 
 #include "boundary_kernels.hip.h"
@@ -66,6 +70,7 @@
 #include "arrival_kernels.hip.h"
 #include "lateral_kernels.hip.h"
 #include "modulation_kernels.hip.h"
+#include "arrival_bands_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -237,6 +242,11 @@ public:
     int modulation_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(mod_, captures, last_step); }
     int fetch_modulation(double* energy, double* sums, uint64_t* captures) override;
     bool modulation_active() const override { return mod_.active; }
+    // ---- engine_arrival_bands.hip.h
+    int set_arrival_bands(const wv_arrival_bands_plan* plan, const float* threshold_map, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) override;
+    int arrival_bands_count(uint64_t* captures, uint64_t* last_step) override;
+    int fetch_arrival_bands(uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) override;
+    bool arrival_bands_active() const override { return arrb_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -444,8 +454,8 @@ private:
     void directional_release();
     int directional_enqueue(uint64_t batch);
     std::unique_ptr<wv::SlabComm> comm_;
-    // the six plans that accumulate on the device (engine_staged.hip.h)
-    enum PlanKind { kSpectrumPlan, kDecayPlan, kIntensityPlan, kArrivalPlan, kLateralPlan, kModulationPlan, kPlanKinds };
+    // the seven plans that accumulate on the device (engine_staged.hip.h)
+    enum PlanKind { kSpectrumPlan, kDecayPlan, kIntensityPlan, kArrivalPlan, kLateralPlan, kModulationPlan, kArrivalBandsPlan, kPlanKinds };
     static constexpr int kPlanBlocks = 2;  // device blocks of accumulated state a plan has at the most
     // wv_checkpoint / wv_rollback (engine_io.hip.h): device copies of the two live fields and the filter memories, and the
     // host-side position that goes with them
@@ -519,8 +529,8 @@ private:
     int snapshot_plan_batch();
     int snapshot_begin_run();
     void snapshot_rollback(uint64_t to_step);
-    // ---- engine_staged.hip.h: the six plans that accumulate on the device -- spectrum, decay (plain and banded), intensity, arrival,
-    // lateral, modulation -- have ONE life cycle: captures into a device-only stage on the compute stream, committed batch by batch, folded into the
+    // ---- engine_staged.hip.h: the seven plans that accumulate on the device -- spectrum, decay (plain and banded), intensity, arrival,
+    // lateral, modulation, banded arrival -- have ONE life cycle: captures into a device-only stage on the compute stream, committed batch by batch, folded into the
     // plan's accumulated state in one launch when the stage has no slot left, on fetch and on checkpoint.  StagedPlan holds what they
     // share; a plan's own struct adds its wv_*_plan, its tables and what its fold kernel needs
     struct StagedPlan {
@@ -658,14 +668,32 @@ private:
         void free_own();
     } mod_;
     int modulation_enqueue(Modulation& d, int b, int t, unsigned blocks);
+    // band-limited arrival maps (engine_arrival_bands.hip.h): block 0 holds what the fold accumulates (arrival_bands_plan.h has the
+    // places): per band pre, moment, bins and a copy of the onset, then peak and peak_capture; block 1 the filter states.  Edges, tail
+    // and lags go to the kernel as arguments: there is no table to copy
+    struct ArrivalBands : StagedPlan {
+        ArrivalBands()
+            : StagedPlan(kArrivalBandsPlan, "banded arrival", "wv_set_arrival_bands", "its state has", "the banded arrival plan's sums",
+                         "the banded arrival plan's filter states", false, false, wv::kArrivalMaxCaptures) {}
+        wv_arrival_bands_plan plan{};
+        wv::ArrivalBandsTable table{};  // edges, tail and lags as the kernel takes them
+        unsigned char* sums() const { return this->block[0]; }                         // double pre[K][B], moment[K][B], bins[K][n_bins][B]; uint32 onset[K][B]; float peak[B]; uint32 peak_capture[B]
+        double* state() const { return reinterpret_cast<double*>(this->block[1]); }  // [n_bands][n_sections][2][B]: z1, z2 of every section
+        uint32_t n_bands = 0, n_sections = 0, n_bins = 0;  // n_bins = n_edges + n_tail
+        double* coef = nullptr;         // [n_bands][n_sections][5] on the device, and behind it ...
+        uint32_t* bin_first() const { return reinterpret_cast<uint32_t*>(coef + (size_t)n_bands * n_sections * wv::kBiquadDoubles); }  // ... [n_bins + 1]: the first rel of every bin, NONE behind the last
+        float* threshold_map = nullptr; // [B], or NULL: the plan's scalar for every node
+        void free_own();
+    } arrb_;
+    int arrival_bands_enqueue(ArrivalBands& d, int b, int t, unsigned blocks);
     // ---- engine_staged.hip.h: one copy of each step of the life cycle
-    StagedPlan* const staged_[kPlanKinds] = {&spec_, &decay_, &inten_, &arr_, &lat_, &mod_};  // by PlanKind
-    StagedPlan* staged() const {  // the active one of the six, or null: they exclude each other (and a snapshot plan)
+    StagedPlan* const staged_[kPlanKinds] = {&spec_, &decay_, &inten_, &arr_, &lat_, &mod_, &arrb_};  // by PlanKind
+    StagedPlan* staged() const {  // the active one of the seven, or null: they exclude each other (and a snapshot plan)
         for (StagedPlan* p : staged_)
             if (p->active) return p;
         return nullptr;
     }
-    enum PlanRow { kSnapshotRow, kSpectrumRow, kBandedDecayRow, kPlainDecayRow, kIntensityRow, kArrivalRow, kLateralRow, kModulationRow };
+    enum PlanRow { kSnapshotRow, kSpectrumRow, kBandedDecayRow, kPlainDecayRow, kIntensityRow, kArrivalRow, kLateralRow, kModulationRow, kArrivalBandsRow };
     int plan_refused(const std::string& setter, PlanRow self);
     template <typename Plan>
     static void plan_release(Plan& p);

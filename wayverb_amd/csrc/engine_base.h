@@ -120,6 +120,10 @@ struct wv_engine {
     virtual int modulation_count(uint64_t* captures, uint64_t* last_step) = 0;
     virtual int fetch_modulation(double* energy, double* sums, uint64_t* captures) = 0;
     virtual bool modulation_active() const = 0;
+    virtual int set_arrival_bands(const wv_arrival_bands_plan* plan, const float* threshold_map, const wv_biquad* sections, uint32_t n_bands, uint32_t n_sections) = 0;
+    virtual int arrival_bands_count(uint64_t* captures, uint64_t* last_step) = 0;
+    virtual int fetch_arrival_bands(uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) = 0;
+    virtual bool arrival_bands_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;
     virtual int set_source(int kind, uint64_t node, const double* signal, uint64_t n) = 0;

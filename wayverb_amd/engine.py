@@ -44,6 +44,7 @@ EXPORTS = [
     "wv_set_arrival", "wv_arrival_count", "wv_fetch_arrival",
     "wv_set_lateral", "wv_lateral_count", "wv_fetch_lateral",
     "wv_set_modulation", "wv_modulation_count", "wv_fetch_modulation",
+    "wv_set_arrival_bands", "wv_arrival_bands_count", "wv_fetch_arrival_bands",
 ]
 
 
@@ -118,6 +119,14 @@ class WvModulationPlan(C.Structure):
     """wv_modulation_plan (include/wayverb_amd.h): the spectrum plan's fields -- box, strides, cadence, the number of modulation
     frequencies."""
     _fields_ = WvSpectrumPlan._fields_
+
+
+class WvArrivalBandsPlan(C.Structure):
+    """wv_arrival_bands_plan (include/wayverb_amd.h): the box and the cadence as wv_decay_plan has them, n_edges, the scalar threshold and
+    the 16 explicit edges as wv_arrival_plan has n_bins and its edges, then the uniform tail, the lag per band and a reserved word."""
+    _fields_ = WvDecayPlan._fields_[:11] + [("n_edges", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 16),
+                                            ("n_tail", C.c_uint32), ("tail_first", C.c_uint32), ("tail_captures", C.c_uint32),
+                                            ("lag", C.c_uint32 * 8), ("reserved", C.c_uint32)]
 
 
 ARRIVAL_NONE = 0xFFFFFFFF   # onset / peak_capture of a node that has none yet
@@ -249,6 +258,9 @@ def load_library():
     lib.wv_set_modulation.argtypes = [C.c_void_p, C.POINTER(WvModulationPlan), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     lib.wv_modulation_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.wv_fetch_modulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.wv_set_arrival_bands.argtypes = [C.c_void_p, C.POINTER(WvArrivalBandsPlan), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.wv_arrival_bands_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.wv_fetch_arrival_bands.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.POINTER(C.c_uint64)]
     lib.wv_biquad_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.wv_butterworth_bandpass.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.wv_bandpass_biquad.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
@@ -452,7 +464,7 @@ class Engine:
     def _plan_state(self):
         """What this layer remembers of the capture plans: the shape a fetch returns, None while the plan is not set."""
         self.snapshot_shape = self.spectrum_shape = self.decay_shape = self.intensity_shape = None
-        self.arrival_shape = self.lateral_shape = self.modulation_shape = None
+        self.arrival_shape = self.lateral_shape = self.modulation_shape = self.arrival_bands_shape = None
         self.decay_banded = False
 
     def close(self):
@@ -904,6 +916,60 @@ class Engine:
         _check(self.lib.wv_fetch_modulation(self.h, energy.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p), None))
         return energy, sums
 
+    # ---- band-limited arrival maps accumulated on the device while wv_run goes on --------------------
+    def set_arrival_bands(self, edges, bands, threshold=0.0, tail=None, lag=0, box="mesh", stride=1, first_step=0, period=1, threshold_map=None,
+                          reserved=0):
+        """wv_set_arrival_bands: set_arrival with set_decay's filter bank ahead of the square.  `edges`, `threshold`, `threshold_map`,
+        `box`, `stride`, `first_step`, `period` as for set_arrival; `bands`: float64[K][S][5] as for set_decay (designed for the rate of
+        the CAPTURED series); `tail`: None or (n_tail, tail_first, tail_captures) -- n_tail uniform bins of tail_captures captures
+        behind the explicit ones, the first at tail_first captures behind the onset, the last open-ended; `lag`: captures by which
+        each band's clock starts late, one integer for all bands or K of them; `reserved` is the plan's reserved word, 0.  Per node the engine keeps the broadband onset, peak and
+        peak_capture, and per band the energy ahead of the onset, the bins and the first time moment; arrival.banded_arrival_fold over
+        the snapshots reproduces all of it bit for bit.  Excludes every other plan.  set_arrival_bands(None, None) stops and forgets.
+        Returns the shape of the bins, (K, n_edges + n_tail, nz, ny, nx)."""
+        if edges is None:
+            return self._stop_plan("arrival_bands", self.lib.wv_set_arrival_bands, None, None, None, 0, 0)
+        sections = np.ascontiguousarray(bands, dtype=np.float64)
+        if sections.ndim != 3 or sections.shape[2] != 5:
+            raise ValueError("set_arrival_bands: bands is float64[K][S][5], got shape %r" % (sections.shape,))
+        plan = WvArrivalBandsPlan()
+        edges = [int(v) for v in edges]
+        if len(edges) > 16:
+            raise ValueError("set_arrival_bands: 16 explicit bins at the most")
+        plan.n_edges = len(edges)
+        for k, v in enumerate(edges):
+            plan.edges[k] = v
+        if tail is not None:
+            plan.n_tail, plan.tail_first, plan.tail_captures = (int(v) for v in tail)
+        lags = [int(lag)] * min(sections.shape[0], 8) if np.isscalar(lag) else [int(v) for v in lag]
+        if len(lags) > 8 or (not np.isscalar(lag) and len(lags) != sections.shape[0]):
+            raise ValueError("set_arrival_bands: one lag, or one per band")
+        for k, v in enumerate(lags):
+            plan.lag[k] = v
+        taken = self._fill_box(plan, box, stride)
+        plan.first_step, plan.period, plan.threshold, plan.reserved = int(first_step), int(period), float(threshold), int(reserved)
+        threshold_map, map_pointer = self._threshold_map(threshold_map, taken, "set_arrival_bands")
+        _check(self.lib.wv_set_arrival_bands(self.h, C.byref(plan), map_pointer, sections.ctypes.data_as(C.c_void_p), sections.shape[0], sections.shape[1]))
+        self.arrival_bands_shape = (sections.shape[0], plan.n_edges + plan.n_tail, taken[2], taken[1], taken[0])
+        return self.arrival_bands_shape
+
+    def arrival_bands_count(self):
+        """wv_arrival_bands_count: (captures of completed steps since the plan was set, the step of the last of them)."""
+        return self._count(self.lib.wv_arrival_bands_count)
+
+    def fetch_arrival_bands(self):
+        """wv_fetch_arrival_bands: (dict(onset=uint32[nz, ny, nx], peak=float32, peak_capture=uint32, pre=float64[K, nz, ny, nx],
+        moment=float64[K, nz, ny, nx], bins=float64[K, n_bins, nz, ny, nx]), captures in them).  ARRIVAL_NONE marks a node without an
+        onset.  The plan keeps running."""
+        shape = tuple(self.arrival_bands_shape or (0, 0, 0, 0, 0))   # (no plan: the library says so)
+        node, band = shape[2:], shape[:1] + shape[2:]
+        out = dict(onset=np.zeros(node, np.uint32), peak=np.zeros(node, np.float32), peak_capture=np.zeros(node, np.uint32),
+                   pre=np.zeros(band, np.float64), moment=np.zeros(band, np.float64), bins=np.zeros(shape, np.float64))
+        captures = C.c_uint64()
+        _check(self.lib.wv_fetch_arrival_bands(self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in ("onset", "peak", "peak_capture", "pre", "moment", "bins")],
+                                               C.byref(captures)))
+        return out, captures.value
+
     def step_count(self):
         s = C.c_uint64()
         _check(self.lib.wv_step_count(self.h, C.byref(s)))
@@ -940,6 +1006,7 @@ class Engine:
     QUERY_ARRIVAL_CAPTURES, QUERY_ARRIVAL_FOLDS, QUERY_ARRIVAL_NS = 37, 38, 39
     QUERY_LATERAL_CAPTURES, QUERY_LATERAL_FOLDS, QUERY_LATERAL_NS, QUERY_LATERAL_GATHER_NS, QUERY_LATERAL_GATHERS = 40, 41, 42, 43, 44
     QUERY_MODULATION_CAPTURES, QUERY_MODULATION_FOLDS, QUERY_MODULATION_NS = 45, 46, 47
+    QUERY_ARRIVAL_BANDS_CAPTURES, QUERY_ARRIVAL_BANDS_FOLDS, QUERY_ARRIVAL_BANDS_NS = 48, 49, 50
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

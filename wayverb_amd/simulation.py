@@ -160,6 +160,33 @@ def arrival_plan_arguments(arrival, mesh, sample_rate):
                 first_step=int(arrival.get("first_step", 0)), period=every)
 
 
+ARRIVAL_BANDS_KEYS = ("bands", "tail_ms", "tail_bin_ms", "lag")
+
+
+def arrival_bands_plan_arguments(arrival, mesh, sample_rate):
+    """canonical's `arrival` dict WITH `bands` -> keyword arguments of Engine.set_arrival_bands: everything arrival_plan_arguments takes,
+    and bands=[(lo_hz, hi_hz), ...] (1 .. 8), tail_ms=None, tail_bin_ms=10, lag="group-delay" | 0.  Every band gets a 4th-order
+    Butterworth band-pass designed at the rate of the CAPTURED series, sample_rate / every (decay.butterworth_bandpass); behind the
+    early edges come uniform bins of tail_bin_ms out to tail_ms behind each node's onset (arrival.band_edges), from which
+    arrival.band_decay_maps reads EDT / T20 / T30; "group-delay" starts every band's clock late by its cascade's group delay at the
+    band's geometric centre, rounded to captures (arrival.lag_captures), 0 counts every band from the broadband onset."""
+    from . import arrival as A
+    from . import decay as D
+    plain = arrival_plan_arguments({k: v for k, v in arrival.items() if k not in ARRIVAL_BANDS_KEYS}, mesh, sample_rate)
+    bands = [(float(lo), float(hi)) for lo, hi in arrival["bands"]]
+    lag = arrival.get("lag", "group-delay")
+    if not 1 <= len(bands) <= 8 or any(not 0 < lo < hi for lo, hi in bands):
+        raise ValueError("arrival: bands holds 1 .. 8 pairs (lo_hz, hi_hz) with 0 < lo < hi")
+    if not (lag == "group-delay" or (not isinstance(lag, str) and int(lag) == 0)):
+        raise ValueError('arrival: lag is "group-delay" or 0')
+    every = plain["period"]
+    series_rate = sample_rate / every
+    sections = np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in bands])
+    edges, tail = A.band_edges(arrival.get("early_ms", (50.0, 80.0)), arrival.get("tail_ms"), arrival.get("tail_bin_ms", 10.0), every, sample_rate)
+    lags = [A.lag_captures(sections[k], math.sqrt(lo * hi), series_rate) if lag == "group-delay" else 0 for k, (lo, hi) in enumerate(bands)]
+    return dict(plain, edges=edges, bands=sections, tail=tail, lag=lags)
+
+
 def lateral_plan_arguments(lateral, mesh, sample_rate, environment):
     """canonical's `lateral` dict -> keyword arguments of Engine.set_lateral: dict(plane=z in metres | box=((x0, y0, z0), extent),
     stride=1, every=1, threshold=, threshold_map=None, edges_ms=(0, 5, 80), first_step=0).  `plane`: that horizontal plane less its
@@ -264,7 +291,9 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     `arrival`: dict(plane=<z in metres> or box=..., every=, threshold=, early_ms=(50, 80)) (arrival_plan_arguments) -- the engine keeps,
     per node of that plane or box and on the device, the capture at which the direct sound arrived, the peak, and the squared pressure
     in bins counted from the node's OWN arrival (Engine.set_arrival); the return value is then (bands, (dict(onset, peak, peak_capture,
-    pre, moment, bins), captures)), which wayverb_amd.arrival turns into arrival time, C50 / C80, D50 and centre time.  One domain
+    pre, moment, bins), captures)), which wayverb_amd.arrival turns into arrival time, C50 / C80, D50 and centre time.  With
+    bands=[(lo_hz, hi_hz), ...] in the dict (and tail_ms=, tail_bin_ms=, lag="group-delay" | 0: arrival_bands_plan_arguments) the plan is
+    Engine.set_arrival_bands: pre, moment and bins per octave band, with a uniform tail for EDT / T20 / T30 from the same run.  One domain
     only, and not together with another plan.
     `lateral`: dict(plane=<z in metres> or box=..., every=, threshold=, edges_ms=(0, 5, 80)) (lateral_plan_arguments) -- the engine
     runs the directional receiver's integrator at every node of that plane or box and keeps, on the device and in bins counted from
@@ -301,7 +330,11 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
         series_rate = sample_rate / int(decay.get("period", 1))
         decay = dict(decay, bands=np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in decay["bands"]]))
     intensity_plan = intensity_plan_arguments(intensity, mesh, sample_rate, environment, simulation_time) if intensity is not None else None
-    arrival_plan = arrival_plan_arguments(arrival, mesh, sample_rate) if arrival is not None else None
+    arrival_banded = arrival is not None and "bands" in arrival
+    if arrival_banded:
+        arrival_plan = arrival_bands_plan_arguments(arrival, mesh, sample_rate)
+    else:
+        arrival_plan = arrival_plan_arguments(arrival, mesh, sample_rate) if arrival is not None else None
     lateral_plan = lateral_plan_arguments(lateral, mesh, sample_rate, environment) if lateral is not None else None
     modulation_plan = modulation_plan_arguments(modulation, mesh, sample_rate) if modulation is not None else None
 
@@ -334,7 +367,9 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
                 eng.set_decay(**decay)
             if intensity_plan is not None:
                 eng.set_intensity(**intensity_plan)
-            if arrival_plan is not None:
+            if arrival_banded:
+                eng.set_arrival_bands(arrival_plan.pop("edges"), arrival_plan.pop("bands"), **arrival_plan)
+            elif arrival_plan is not None:
                 eng.set_arrival(**arrival_plan)
             if lateral_plan is not None:
                 eng.set_lateral(**lateral_plan)
@@ -350,7 +385,7 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
             if intensity_plan is not None:
                 taken = eng.fetch_intensity()
             if arrival_plan is not None:
-                taken = eng.fetch_arrival()
+                taken = eng.fetch_arrival_bands() if arrival_banded else eng.fetch_arrival()
             if lateral_plan is not None:
                 taken = eng.fetch_lateral()
             if modulation_plan is not None:
