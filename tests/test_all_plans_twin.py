@@ -1,9 +1,9 @@
-"""The generator and the reference of tests/test_gpu_all_plan_sequences.py alone, on the CPU: the oracle, no engine.  What the comparison
+"""The generator and the reference of tests/test_gpu_plan_sequences.py's family `all-plans` alone, on the CPU: the oracle, no engine.  What the comparison
 on the GPU needs before it means anything -- every one of the eight kinds of plan fetched with something in it, plans of every kind
 handed over to plans of other kinds, replaced by plans of their own, stopped and followed by others, refused setters and refused
 rollbacks, rollbacks across captures, more captures under one plan than a stage holds, lateral plans with several onsets and bins --
 is counted over all seeds and asserted here; the counts' bounds are the issue's, and the generator's probabilities
-(all_plans_twin.WEIGHTS) were chosen to meet them.  `python tests/test_all_plans_twin.py` prints the table of the counts."""
+(its weights in plan_twin.FAMILIES) were chosen to meet them.  `python tests/test_all_plans_twin.py` prints the table of the counts."""
 import os
 import sys
 
@@ -14,9 +14,11 @@ if __name__ == "__main__":
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests", "golden")]
 
-import all_plans_twin as T
+import plan_twin as T
 from wayverb_amd import lateral as L
 from wayverb_amd import mesh as M
+
+FAMILY = T.FAMILIES["all-plans"]
 
 
 def counts(stats):
@@ -49,7 +51,7 @@ def counts(stats):
 
 @pytest.fixture(scope="module")
 def scripts(oracle, built_library):
-    return [T.build_script(oracle, seed) for seed in range(T.SEEDS)]
+    return [T.build_script(oracle, "all-plans", seed) for seed in range(FAMILY.seeds)]
 
 
 @pytest.fixture(scope="module")
@@ -131,9 +133,9 @@ def test_refusals_hold_the_active_plans_words(scripts):
                 active = None
             elif op["op"] == "refused-plan":
                 seen += 1
-                assert op["plan"]["kind"] != active and op["words"].startswith(T.SETTER[op["plan"]["kind"]] + ": ")
-                assert sum(1 for words in T.ACTIVE.values() if words in op["words"]) == (0 if (active, op["plan"]["kind"]) == ("decay", "banded") else 1)
-                assert T.ACTIVE[active] in op["words"] or "a plain decay plan is active" in op["words"]
+                assert op["plan"]["kind"] != active and op["words"].startswith(T.KINDS[op["plan"]["kind"]].setter + ": ")
+                assert sum(1 for k in T.KINDS.values() if k.active in op["words"]) == (0 if (active, op["plan"]["kind"]) == ("decay", "banded") else 1)
+                assert T.KINDS[active].active in op["words"] or "a plain decay plan is active" in op["words"]
     assert seen >= 8
 
 
@@ -151,7 +153,7 @@ def test_the_pinned_example_of_generic_steps_in_between_for_a_lateral_plan(oracl
     number of links from (5, 5, 4) hold something at step 9 (onset 0), the others at step 12 (onset 1); seven nodes stay below the
     threshold of 0.02 in all three captures, one reaches it only at step 18 (onset 2).  No |p| lies within 5 % of the threshold."""
     mesh = M.box_mesh(12, 10, 9)
-    twin = T.AllPlansTwin(oracle, mesh, np.float32)
+    twin = T.PlanTwin(oracle, mesh, np.float32)
     twin.cur[mesh.compute_index(5, 5, 4)] = np.float32(1.0)
     assert twin.run(9) == 9
     plan = dict(kind="lateral", box=((2, 2, 3), (8, 6, 2)), stride=(1, 1, 1), first_step=0, period=3, edges=[0, 1], threshold=PINNED_THRESHOLD,
@@ -181,6 +183,6 @@ def test_the_pinned_example_of_generic_steps_in_between_for_a_lateral_plan(oracl
 if __name__ == "__main__":
     from oracle.oracle import Oracle
     oracle = Oracle()
-    print("weights", T.WEIGHTS)
-    for name, value in counts([T.build_script(oracle, seed)["stats"] for seed in range(T.SEEDS)]).items():
+    print("weights", FAMILY.weights)
+    for name, value in counts([T.build_script(oracle, "all-plans", seed)["stats"] for seed in range(FAMILY.seeds)]).items():
         print("%-70s %s" % (name, value))

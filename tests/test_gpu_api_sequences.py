@@ -9,45 +9,11 @@ import numpy as np
 import pytest
 
 from helpers import set_tuning
+from plan_twin import Twin
 from wayverb_amd import engine as E
 from wayverb_amd import mesh as M
 
 pytestmark = pytest.mark.gpu
-
-
-class Twin:
-    """The oracle kept in step with an engine."""
-
-    def __init__(self, oracle, mesh, dtype):
-        self.oracle, self.mesh, self.dtype = oracle, mesh, dtype
-        self.prev = np.zeros(mesh.num_nodes, dtype=dtype)
-        self.cur = np.zeros(mesh.num_nodes, dtype=dtype)
-        self.bd = [mesh.boundary_data(d) for d in (1, 2, 3)]
-        self.kind, self.node, self.signal, self.pos = E.SOURCE_NONE, 0, None, 0
-        self.recv, self.rows, self.step_no, self.recv_from = [], [], 0, 0
-
-    def plain_step(self):
-        assert self.oracle.step(self.prev, self.cur, self.mesh, self.bd) == 0
-        self.prev, self.cur = self.cur, self.prev
-        self.step_no += 1
-
-    def run(self, n):
-        done = 0
-        for _ in range(n):
-            if self.kind != E.SOURCE_NONE:
-                if self.pos >= len(self.signal):
-                    break                                            # hard_source.h:18-20: `pre` returns false
-                s = self.dtype(self.signal[self.pos])
-                self.cur[self.node] = s if self.kind == E.SOURCE_HARD else self.dtype(self.cur[self.node] + s)
-                self.pos += 1
-            self.rows.append([float(self.cur[r]) for r in self.recv])
-            self.plain_step()
-            done += 1
-        return done
-
-    def outside_step(self):
-        self.rows.append([float("nan")] * len(self.recv))
-        self.plain_step()
 
 
 def random_room(rng, seed):

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import cases
-from helpers import set_tuning
+from helpers import numpy_bins, set_tuning
 from test_gpu_snapshots import FORMS, make_engine
 from wayverb_amd import decay as D
 from wayverb_amd import engine as E
@@ -27,15 +27,6 @@ def _default_tuning_afterwards(built_library):
     yield
     set_tuning()
 
-
-def numpy_bins(snaps, n_bins, bin_captures):
-    """The definition: capture j goes to bin min(j // W, n_bins - 1); E[b] = E[b] + p_j * p_j in capture order, in double, from +0.0."""
-    out = np.zeros((n_bins,) + tuple(snaps.shape[1:]))
-    for j, p in enumerate(snaps):
-        p = p.astype(np.float64)
-        b = min(j // bin_captures, n_bins - 1)
-        out[b] = out[b] + p * p
-    return out
 
 
 _reference = {}

@@ -8,16 +8,14 @@ The construction is that test's: a 12^3 box in f64, a hard source of zeros, `pre
 as uniform(-1, 1) * scale on the inside nodes, 20 steps, every step captured.  A companion engine with a SNAPSHOT plan of the same
 capture box (the hull, for intensity and lateral plans) supplies the float32 captures; they are first held, bytewise, to NumPy's
 own conversion of the f64 fields an engine without any plan shows step by step, and then fed to the shipped definitions
-(all_plans_twin.AllPlansTwin.expected).  Every output must equal the definition's BYTEWISE; no NaN appears (squares and hull
+(plan_twin.PlanTwin.expected).  Every output must equal the definition's BYTEWISE; no NaN appears (squares and hull
 differences stay finite at 1e30), so no NaN bytes are compared."""
 import numpy as np
 import pytest
 
-import all_plans_twin as T
 import plan_twin as P
-from helpers import set_tuning
-from test_gpu_all_plan_sequences import assert_outputs, set_plan
-from test_gpu_snapshots import FORMS, make_engine, subsample
+from helpers import set_tuning, subsample
+from test_gpu_snapshots import FORMS, make_engine
 from wayverb_amd import decay as D
 from wayverb_amd import engine as E
 from wayverb_amd import lateral as L
@@ -30,6 +28,7 @@ STEPS = 20
 SCALES = (1e-41, 1e30)
 BOX = ((1, 1, 4), (10, 9, 3))          # 270 nodes: two workgroups of a fold, the second one partly idle; its hull reaches three faces of the mesh
 EDGES = [0, 1, 5, 16]
+MAIN = {"snapshots": "snapshots", "spectrum": "spectrum", "modulation": "sums"}     # the output that must not be all zeros; of every other kind `bins`
 TINY32, TINY64 = np.finfo(np.float32).tiny, np.finfo(np.float64).tiny
 
 
@@ -110,7 +109,7 @@ def stepwise_fields(scale):
     return _fields[scale]
 
 
-CASES = [(kind, False) for kind in T.KINDS8 if kind != "banded"] + [("arrival", True), ("lateral", True)]
+CASES = [(kind, False) for kind in P.KINDS8 if kind != "banded"] + [("arrival", True), ("lateral", True)]
 
 
 @pytest.mark.parametrize("scale", SCALES)
@@ -121,10 +120,10 @@ def test_subnormal_and_huge_captures(kind, with_map, scale):
     mesh = case["mesh"]
     plan = plan_of(kind, scale, with_map)
     previous, current, placed = fields_of(mesh, scale)
-    captured = T.capture_box(plan)
+    captured = P.capture_box(plan)
     engines = [make_engine(case, "f64", dict(box=captured["box"], stride=captured["stride"], period=1)), make_engine(case, "f64")]
     try:
-        set_plan(engines[1], plan)
+        P.set_plan(engines[1], plan)
         for eng in engines:
             eng.write_field(previous, E.BUF_PREVIOUS)
             eng.write_field(current, E.BUF_CURRENT)
@@ -144,12 +143,12 @@ def test_subnormal_and_huge_captures(kind, with_map, scale):
             # the negative zeros of capture 0 are the placed ones, all of them that lie in what is captured, and there are some
             here = np.ascontiguousarray(subsample(placed.reshape(mesh.dims[::-1]), captured, mesh.dims))
             assert here.sum() >= 10 and np.array_equal(np.signbit(snaps[0]) & (snaps[0] == 0), here) and np.abs(snaps).max() > 1e29
-        twin = T.AllPlansTwin(None, mesh, np.float64)
+        twin = P.PlanTwin(None, mesh, np.float64)
         twin.set_plan(plan)
         twin.log = [(int(s), a) for s, a in zip(steps, snaps)]
         with np.errstate(under="ignore"):
             want = twin.expected()
-        main = T.main_output(kind, want)
+        main = want[MAIN.get(kind, "bins")]
         assert np.any(main != 0) and all(np.isfinite(v).all() for v in want.values() if isinstance(v, np.ndarray) and v.dtype.kind in "fc")
         if kind in ("arrival", "lateral"):
             heard = want["onset"] != L.NONE
@@ -162,7 +161,7 @@ def test_subnormal_and_huge_captures(kind, with_map, scale):
                 _, _, state = MOD.modulation_fold(snaps, steps, plan["freqs"], plan["bands"], return_state=True)
             state = np.asarray(state)
             assert ((state[0, :2] != 0) & (np.abs(state[0, :2]) < TINY64)).mean() > 0.5
-        assert_outputs(engines[1], kind, want, (kind, with_map, scale))
+        P.assert_outputs(engines[1], kind, want, (kind, with_map, scale))
     finally:
         for eng in engines:
             eng.close()

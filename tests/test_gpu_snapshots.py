@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import cases
-from helpers import initial_fields, set_tuning
+from helpers import initial_fields, set_tuning, subsample
 from test_gpu_parity import _random_case
 from wayverb_amd import engine as E
 from wayverb_amd import mesh as M
@@ -45,15 +45,6 @@ def plan_steps(plan, set_at, upto):
     first, period = plan.get("first_step", 0), plan.get("period", 1)
     return [s for s in range(first, upto + 1, period) if s >= set_at]
 
-
-def subsample(planes, plan, dims):
-    """What the plan takes of a whole field [nz, ny, nx]."""
-    (x0, y0, z0), extent = plan.get("box", "mesh") if plan.get("box", "mesh") != "mesh" else ((0, 0, 0), None)
-    extent = extent or (None, None, None)
-    ex, ey, ez = [dims[a] - o if e is None else e for a, (o, e) in enumerate(zip((x0, y0, z0), extent))]
-    stride = plan.get("stride", 1)
-    sx, sy, sz = (stride,) * 3 if np.isscalar(stride) else stride
-    return planes[z0:z0 + ez:sz, y0:y0 + ey:sy, x0:x0 + ex:sx]
 
 
 def reference_snapshots(case, tag, plan, steps):

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import cases
-from helpers import set_tuning
+from helpers import numpy_fold, set_tuning
 from test_gpu_snapshots import FORMS, make_engine
 from wayverb_amd import engine as E
 from wayverb_amd import mesh as M
@@ -27,20 +27,6 @@ def _default_tuning_afterwards(built_library):
     yield
     set_tuning()
 
-
-def numpy_fold(snaps, steps, freqs):
-    """The definition: re[k] = re[k] + p_j * c(j, k), im[k] = im[k] - p_j * s(j, k), j in capture order, in double."""
-    shape = (len(freqs),) + tuple(snaps.shape[1:])
-    re, im = np.zeros(shape), np.zeros(shape)
-    for p, step in zip(snaps, steps):
-        p = p.astype(np.float64)
-        for k, f in enumerate(freqs):
-            c, s = E.spectrum_twiddle(f, int(step))
-            re[k] = re[k] + p * c
-            im[k] = im[k] - p * s
-    out = np.empty(shape, dtype=np.complex128)
-    out.real, out.imag = re, im
-    return out
 
 
 _reference = {}

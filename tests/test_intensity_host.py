@@ -4,6 +4,7 @@ formula for E, and against itself when a series is fed in pieces.  Everything is
 import numpy as np
 import pytest
 
+from helpers import numpy_bins as decay_bins
 from test_receiver_arrays_host import canonical_parameters
 from wayverb_amd import intensity as I
 from wayverb_amd import postprocess as P
@@ -62,16 +63,6 @@ def test_the_definition_is_the_pinned_integrator(built_library, valued, seed):
     # ... and the whole series at once is the same series
     bins, v_once = I.intensity_bins(hull, box_in_hull, spacing, rate, density, 1, 1, return_velocity=True)
     assert v_once.tobytes() == v.tobytes()
-
-
-def decay_bins(snaps, n_bins, bin_captures):
-    """tests/test_gpu_decay.py numpy_bins' formula (that module needs a GPU to import its neighbours: restated here, line for line)."""
-    out = np.zeros((n_bins,) + tuple(snaps.shape[1:]))
-    for j, p in enumerate(snaps):
-        p = p.astype(np.float64)
-        b = min(j // bin_captures, n_bins - 1)
-        out[b] = out[b] + p * p
-    return out
 
 
 def random_hull(seed, shape=(37, 6, 7, 8)):

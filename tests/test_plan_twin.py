@@ -1,17 +1,38 @@
-"""The generator and the reference of tests/test_gpu_plan_sequences.py alone, on the CPU: the oracle, no engine.  What the comparison
-on the GPU needs before it means anything -- every kind of plan fetched with something in it, captures inside cut runs, rollbacks
-across captures, writes between captures, boxes with outside nodes, nodes with and without an onset -- is counted over all seeds
-and asserted here; the counts' bounds are the issue's, and the generator's probabilities (plan_twin.WEIGHTS) were chosen to meet them."""
+"""The generator and the reference of tests/test_gpu_plan_sequences.py alone, on the CPU: the oracle, no engine.  The scripts of all four
+families are the ones tests/golden/plan_sequence_digests.json pins, and what the comparison on the GPU needs before it means anything
+-- every kind of plan fetched with something in it, captures inside cut runs, rollbacks across captures, writes between captures,
+boxes with outside nodes, nodes with and without an onset -- is counted over all seeds and asserted here, for the families `plans`,
+`modulation` and `arrival-bands` (tests/test_all_plans_twin.py has `all-plans`); the counts' bounds are the issues', and the
+generator's probabilities (the families' weights) were chosen to meet them."""
+import json
+import os
+
 import numpy as np
 import pytest
 
 import plan_twin as P
+from helpers import GOLDEN
 from wayverb_amd import mesh as M
 
 
 @pytest.fixture(scope="module")
-def stats(oracle, built_library):
-    return [P.build_script(oracle, seed)["stats"] for seed in range(P.SEEDS)]
+def scripts(oracle, built_library):
+    return {family: [P.build_script(oracle, family, seed) for seed in range(P.FAMILIES[family].seeds)] for family in P.FAMILIES}
+
+
+@pytest.fixture(scope="module")
+def stats(scripts):
+    return [s["stats"] for s in scripts["plans"]]
+
+
+def test_the_generator_writes_the_pinned_scripts(scripts):
+    """Every script of every family, byte for byte: the digests were recorded from the four generators this one replaced
+    (profiles/r20/README.md).  A draw added, dropped or moved shows here."""
+    with open(os.path.join(GOLDEN, "plan_sequence_digests.json")) as f:
+        pinned = json.load(f)["digests"]
+    assert {family: len(digests) for family, digests in pinned.items()} == {"plans": 40, "all-plans": 32, "modulation": 10, "arrival-bands": 8}
+    for family, digests in pinned.items():
+        assert [P.digest(s) for s in scripts[family]] == digests, family
 
 
 def count(stats, what):
@@ -21,7 +42,7 @@ def count(stats, what):
 
 
 def test_every_kind_of_plan_is_fetched_with_something_in_it(stats):
-    for kind in P.KINDS:
+    for kind in P.KINDS6:
         assert count(stats, lambda s: kind in s["fetched"]) >= 5, kind
 
 
@@ -75,3 +96,29 @@ def test_the_pinned_example_of_generic_steps_in_between(oracle):
     assert twin.run(4) == 4 and [s for s, _ in twin.log] == [9, 12, 18, 21]
     twin.rollback()
     assert twin.step_no == 18 and twin.next == 21 and twin.expected()["snapshots"].tobytes() == want["snapshots"].tobytes()
+
+
+def test_the_modulation_scripts_held_what_the_comparison_needs(scripts):
+    """The four kinds of room, both precisions, captures in every script and more than one stage holds in half of them, sums that
+    were not zeros in seven scripts of ten at the least, a plan replaced mid-sequence and a rollback across captures in three each at
+    the least."""
+    stats = [s["stats"] for s in scripts["modulation"]]
+    assert len(stats) == 10
+    assert {s["room"] for s in stats} == {"box", "L", "blob", "sphere"}
+    assert {s["tag"] for s in scripts["modulation"]} == {"f32", "f64"}
+    assert sum(1 for s in stats if s["fetched_something"]) >= 7
+    assert sum(1 for s in stats if s["replaced"]) >= 3 and sum(1 for s in stats if s["rolled_across"]) >= 3
+    assert all(s["captures"] > 0 for s in stats) and sum(1 for s in stats if s["captures"] > 16) >= 5
+
+
+def test_the_arrival_bands_scripts_held_what_the_comparison_needs(scripts):
+    """The four kinds of room, both precisions, captures in every script and more than one stage holds in three of them at the least,
+    outputs with onsets and without, bins and pre in five scripts of eight at the least, a tail bin that took energy in two, a plan
+    stopped or replaced mid-sequence in three and a rollback across captures in two at the least."""
+    stats = [s["stats"] for s in scripts["arrival-bands"]]
+    assert len(stats) == 8
+    assert {s["room"] for s in stats} == {"box", "L", "blob", "sphere"}
+    assert {s["tag"] for s in scripts["arrival-bands"]} == {"f32", "f64"}
+    assert sum(1 for s in stats if s["fetched_something"]) >= 5 and sum(1 for s in stats if s["tails"]) >= 2
+    assert sum(1 for s in stats if s["stopped"]) >= 2 and sum(1 for s in stats if s["replaced"] or s["stopped"]) >= 3 and sum(1 for s in stats if s["rolled_across"]) >= 2
+    assert all(s["captures"] > 0 for s in stats) and sum(1 for s in stats if s["captures"] > 16) >= 3

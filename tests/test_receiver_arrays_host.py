@@ -4,17 +4,12 @@ receivers uses as its yardstick.  Bitwise, on seeded random traces; spacing and 
 import numpy as np
 import pytest
 
+from helpers import canonical_parameters
 from wayverb_amd import postprocess as P
 from wayverb_amd import simulation as W
 
 STEPS = 500
 
-
-def canonical_parameters():
-    """What canonical() passes on: a float spacing for the 200 Hz / 0.6 waveguide, its sample rate, core::environment's density."""
-    env = W.Environment()
-    spacing = float(np.float32(W.grid_spacing(env.speed_of_sound, 1.0 / W.compute_sampling_frequency(200.0, 0.6))))
-    return spacing, W.compute_sample_rate(spacing, env.speed_of_sound), env.ambient_density
 
 
 def traces(valued, seed):
