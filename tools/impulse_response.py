@@ -35,6 +35,26 @@ def write_wav(path, audio, rate):
     return peak
 
 
+# the flags that set a capture plan, in the order main() looks at them: each excludes the ones ahead of it
+PLAN_FLAGS = ("--snapshots", "--spectrum", "--decay-map", "--intensity-map", "--clarity-map", "--lateral-map", "--modulation-map")
+
+
+def listed(flags):
+    """--a, --b or --c"""
+    return " or ".join(filter(None, [", ".join(flags[:-1]), flags[-1]]))
+
+
+def one_plane(maps):
+    """[..., 1, ny, nx], what a plan of one horizontal plane fetches -> [..., ny, nx]"""
+    return maps[..., 0, :, :]
+
+
+def npz_keys(plan, mesh, rate, captures):
+    """What every plan's npz says of the run: the captures taken, the cadence, the plane and where its first node lies."""
+    return dict(captures=captures, period=plan["period"], sample_rate=rate, plane=plan["box"][0][2], spacing=mesh.spacing,
+                origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--obj")
@@ -163,7 +183,25 @@ def main():
         table[name] = vals * 8 if len(vals) == 1 else vals
     absorptions = way_absorptions if args.way else [table.get(n, [0.05] * 8) for n in names]
 
-    snapshots = None
+    receivers = args.receiver or [[8.0, 20.0, 1.2]]
+    args.receiver = receivers[0]
+    plans = {}   # impulse_response's keyword -> the plan; the flags exclude each other, so it never holds two
+
+    def alone(flag):
+        """The refusal of `flag` beside multi-band runs and the plan flags ahead of it, one of which `plans` then holds already."""
+        if bands or plans:
+            ap.error("%s: single-band runs without %s" % (flag, listed(PLAN_FLAGS[:PLAN_FLAGS.index(flag)])))
+
+    def z_of(value, option):
+        """z=<metres> -> the number's text, which metres() converts once the flag's other checks have passed; not given: None."""
+        if value and not value.startswith("z="):
+            ap.error("%s takes z=<metres>" % option)
+        return value[2:] if value else None
+
+    def metres(z):
+        """The height z_of() found; not given: the receiver's."""
+        return float(z) if z else args.receiver[2]
+
     if args.snapshots:
         if bands:
             ap.error("--snapshots: single-band runs only")
@@ -171,22 +209,11 @@ def main():
         if sorted(want) != ["every", "z"]:
             ap.error("--snapshots takes z=<plane>,every=<k>")
         plane, every = int(want["z"]), int(want["every"])
-
-        def snapshots(mesh):
-            return dict(box=((0, 0, plane), (None, None, 1)), period=every)
-
-    receivers = args.receiver or [[8.0, 20.0, 1.2]]
-    args.receiver = receivers[0]
-    spectrum = None
+        plans["snapshots"] = lambda mesh: dict(box=((0, 0, plane), (None, None, 1)), period=every)
     if args.spectrum:
-        if bands or snapshots is not None:
-            ap.error("--spectrum: single-band runs without --snapshots")
+        alone("--spectrum")
         freqs_hz = [float(x) for x in args.spectrum.split(",")]
-        height = args.receiver[2]
-        if args.spectrum_plane:
-            if not args.spectrum_plane.startswith("z="):
-                ap.error("--spectrum-plane takes z=<metres>")
-            height = float(args.spectrum_plane[2:])
+        height = metres(z_of(args.spectrum_plane, "--spectrum-plane"))
         spectrum_plane = {}
 
         def spectrum(mesh):
@@ -195,16 +222,14 @@ def main():
                 ap.error("--spectrum-plane: z=%g m is outside the mesh" % height)
             spectrum_plane.update(plane=plane, z=mesh.min_corner[2] + plane * mesh.spacing)
             return dict(freqs_hz=freqs_hz, box=((0, 0, plane), (None, None, 1)))
-    decay = None
+        plans["spectrum"] = spectrum
     if args.decay_map is not None:
-        if bands or snapshots is not None or spectrum is not None:
-            ap.error("--decay-map: single-band runs without --snapshots or --spectrum")
-        if args.decay_map and not args.decay_map.startswith("z="):
-            ap.error("--decay-map takes z=<metres>")
+        alone("--decay-map")
+        z = z_of(args.decay_map, "--decay-map")
         if args.decay_every < 1 or not args.decay_bin_ms > 0:
             ap.error("--decay-every must be >= 1 and --decay-bin-ms positive")
-        decay_height = float(args.decay_map[2:]) if args.decay_map else args.receiver[2]
-        decay_plane = {}
+        decay_height = metres(z)
+        decay_plan = {}
         try:
             decay_centres = [float(c) for c in args.decay_bands.split(",")] if args.decay_bands else []
         except ValueError:
@@ -219,64 +244,44 @@ def main():
             captures = int(np.ceil(rate * args.seconds)) // args.decay_every + 1
             per_bin = max(1, int(round(args.decay_bin_ms * 1e-3 * rate / args.decay_every)))
             n_bins = max(1, min(4096, -(-captures // per_bin)))
-            decay_plane.update(plane=plane, rate=rate, per_bin=per_bin,
-                               origin=np.asarray(mesh.min_corner, dtype=np.float64) + np.array([0.0, 0.0, plane * mesh.spacing]))
-            plan = dict(n_bins=n_bins, bin_captures=per_bin, box=((0, 0, plane), (None, None, 1)), period=args.decay_every)
+            decay_plan.update(n_bins=n_bins, bin_captures=per_bin, box=((0, 0, plane), (None, None, 1)), period=args.decay_every)
             if decay_centres:
                 from wayverb_amd import decay as D
-                plan["bands"] = D.octave_band_edges(decay_centres)
-                for c, (lo, hi) in zip(decay_centres, plan["bands"]):
-                    if hi > 0.25 * rate:
-                        print("warning: the %g Hz band reaches %.1f Hz, above a quarter of the sample rate (%.1f Hz): the waveguide "
-                              "is not trusted there" % (c, hi, 0.25 * rate), file=sys.stderr)
-                    if hi > 0.5 * rate / args.decay_every:
-                        print("warning: the %g Hz band reaches %.1f Hz, above the Nyquist rate of the captured series (%.1f Hz with "
-                              "--decay-every %d): it aliases" % (c, hi, 0.5 * rate / args.decay_every, args.decay_every), file=sys.stderr)
-            return plan
-    intensity = None
+                decay_plan["bands"] = D.octave_band_edges(decay_centres)
+                for sentence in W.octave_band_warnings(decay_centres, decay_plan["bands"], rate, args.decay_every, "", "--decay-every %d"):
+                    print("warning: " + sentence, file=sys.stderr)
+            return decay_plan
+        plans["decay"] = decay
     if args.intensity_map:
-        if bands or snapshots is not None or spectrum is not None or decay is not None:
-            ap.error("--intensity-map: single-band runs without --snapshots, --spectrum or --decay-map")
-        if args.intensity_plane and not args.intensity_plane.startswith("z="):
-            ap.error("--intensity-plane takes z=<metres>")
+        alone("--intensity-map")
+        z = z_of(args.intensity_plane, "--intensity-plane")
         if args.intensity_every < 1 or not args.intensity_bin_ms > 0:
             ap.error("--intensity-every must be >= 1 and --intensity-bin-ms positive")
-        intensity = dict(plane=float(args.intensity_plane[2:]) if args.intensity_plane else args.receiver[2], every=args.intensity_every,
-                         bin_seconds=args.intensity_bin_ms * 1e-3)
-    arrival = None
+        plans["intensity"] = dict(plane=metres(z), every=args.intensity_every, bin_seconds=args.intensity_bin_ms * 1e-3)
     if args.clarity_map:
-        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None:
-            ap.error("--clarity-map: single-band runs without --snapshots, --spectrum, --decay-map or --intensity-map")
-        if args.arrival_plane and not args.arrival_plane.startswith("z="):
-            ap.error("--arrival-plane takes z=<metres>")
+        alone("--clarity-map")
+        z = z_of(args.arrival_plane, "--arrival-plane")
         if args.arrival_every < 1 or not (args.arrival_threshold >= 0 and np.isfinite(args.arrival_threshold)):
             ap.error("--arrival-every must be >= 1 and --arrival-threshold >= 0 and finite")
-        arrival = dict(plane=float(args.arrival_plane[2:]) if args.arrival_plane else args.receiver[2], every=args.arrival_every,
-                       threshold=args.arrival_threshold, early_ms=(50.0, 80.0))
+        plans["arrival"] = dict(plane=metres(z), every=args.arrival_every, threshold=args.arrival_threshold, early_ms=(50.0, 80.0))
         if args.clarity_bands:
             from wayverb_amd import decay as D
             centres = [float(v) for v in args.clarity_bands.split(",")]
             if not 1 <= len(centres) <= 8 or any(not c > 0 for c in centres):
                 ap.error("--clarity-bands takes 1 .. 8 positive octave centres")
-            arrival.update(bands=D.octave_band_edges(centres), tail_ms=args.clarity_tail_ms, tail_bin_ms=args.clarity_tail_bin_ms, lag="group-delay")
+            plans["arrival"].update(bands=D.octave_band_edges(centres), tail_ms=args.clarity_tail_ms, tail_bin_ms=args.clarity_tail_bin_ms,
+                                    lag="group-delay")
     elif args.clarity_bands:
         ap.error("--clarity-bands goes with --clarity-map")
-    lateral = None
     if args.lateral_map:
-        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None:
-            ap.error("--lateral-map: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map or --clarity-map")
-        if args.lateral_plane and not args.lateral_plane.startswith("z="):
-            ap.error("--lateral-plane takes z=<metres>")
+        alone("--lateral-map")
+        z = z_of(args.lateral_plane, "--lateral-plane")
         if args.lateral_every < 1 or not (args.lateral_threshold >= 0 and np.isfinite(args.lateral_threshold)):
             ap.error("--lateral-every must be >= 1 and --lateral-threshold >= 0 and finite")
-        lateral = dict(plane=float(args.lateral_plane[2:]) if args.lateral_plane else args.receiver[2], every=args.lateral_every,
-                       threshold=args.lateral_threshold, edges_ms=(0.0, 5.0, 80.0))
-    modulation = None
+        plans["lateral"] = dict(plane=metres(z), every=args.lateral_every, threshold=args.lateral_threshold, edges_ms=(0.0, 5.0, 80.0))
     if args.modulation_map is not None:
-        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None or lateral is not None:
-            ap.error("--modulation-map: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map, --clarity-map or --lateral-map")
-        if args.modulation_map and not args.modulation_map.startswith("z="):
-            ap.error("--modulation-map takes z=<metres>")
+        alone("--modulation-map")
+        z = z_of(args.modulation_map, "--modulation-map")
         try:
             modulation_centres = [float(c) for c in args.modulation_bands.split(",")]
             sti_rest = {float(item.split(":")[0]): float(item.split(":")[1]) for item in args.sti_rest.split(",")} if args.sti_rest else None
@@ -284,15 +289,12 @@ def main():
             ap.error("--modulation-bands takes octave centres in Hz, e.g. 125,250,500, and --sti-rest HZ:MTI pairs, e.g. 1000:0.55,2000:0.5")
         if not 1 <= len(modulation_centres) <= 8 or any(not c > 0 for c in modulation_centres) or args.modulation_every < 1:
             ap.error("--modulation-bands: 1 .. 8 positive centre frequencies; --modulation-every must be >= 1")
-        modulation = dict(plane=float(args.modulation_map[2:]) if args.modulation_map else args.receiver[2], every=args.modulation_every,
-                          bands_hz=modulation_centres)
+        plans["modulation"] = dict(plane=metres(z), every=args.modulation_every, bands_hz=modulation_centres)
     t0 = time.perf_counter()
     method = P.ATTENUATOR_NULL if args.mic_shape is None else P.ATTENUATOR_MICROPHONE
     if len(receivers) > 1:
-        if bands or snapshots is not None or spectrum is not None or decay is not None or intensity is not None or arrival is not None or lateral is not None or \
-                modulation is not None:
-            ap.error("several --receiver: single-band runs without --snapshots, --spectrum, --decay-map, --intensity-map, --clarity-map, --lateral-map "
-                     "or --modulation-map")
+        if bands or plans:
+            ap.error("several --receiver: single-band runs without %s" % listed(PLAN_FLAGS))
         audios, per, positions, vm = W.impulse_responses(v, t, absorptions, args.source, receivers, args.cutoff, args.usable_portion,
                                                          args.seconds, args.rate, method=method, pointing=args.pointing,
                                                          shape=args.mic_shape or 0.0, precision=args.precision)
@@ -306,9 +308,9 @@ def main():
             peak = write_wav(name, audio, args.rate)
             print("wrote %s: receiver at node position (%.3f, %.3f, %.3f) (normalised, peak was %.3e)" % ((name,) + tuple(pos) + (peak,)))
         return
-    if bands and (intensity is not None or arrival is not None or lateral is not None):
+    if bands and any(k in plans for k in ("intensity", "arrival", "lateral")):
         ap.error("--intensity-map, --clarity-map, --lateral-map: single-band runs only")
-    if bands and modulation is not None:
+    if bands and "modulation" in plans:
         ap.error("--modulation-map: single-band runs only")
     if bands:   # multiple_band_constant_spacing: one run per band with flat per-band walls
         env = W.Environment()
@@ -321,18 +323,24 @@ def main():
         audio_etc = W.impulse_response(v, t, absorptions, args.source, args.receiver, args.cutoff,
                                        args.usable_portion, args.seconds, args.rate, method=method,
                                        pointing=args.pointing, shape=args.mic_shape or 0.0,
-                                       precision=args.precision, snapshots=snapshots, spectrum=spectrum, decay=decay, intensity=intensity,
-                                       arrival=arrival, lateral=lateral, modulation=modulation)
-        if modulation is not None:
+                                       precision=args.precision, **plans)
+        kind = next(iter(plans), None)   # the one plan of this run, if any
+        out, captures = audio_etc[3] if kind else (None, None)
+        env, mesh = W.Environment(), audio_etc[2].mesh
+        rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
+        name, positional, plan, shared = kind, (), None, None
+        if kind in ("intensity", "arrival", "lateral", "modulation"):   # the arguments canonical gave Engine.set_<name>, once more
             import warnings
-            from wayverb_amd import modulation as MOD
-            env, mesh = W.Environment(), audio_etc[2].mesh
-            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")   # (canonical has said it already)
-                plan = W.modulation_plan_arguments(modulation, mesh, rate)
-            (energy, sums), captures = audio_etc[3]
-            energy, sums = energy[:, 0], sums[:, :, 0]   # the one plane: [K, ny, nx], [K, M, ny, nx]
+                name, positional, plan = W.plan_call(kind, plans[kind], mesh, rate, env, args.seconds)
+        elif kind == "decay":
+            plan = decay_plan
+        if plan is not None:
+            shared = npz_keys(plan, mesh, rate, captures)
+        if kind == "modulation":
+            from wayverb_amd import modulation as MOD
+            energy, sums = one_plane(out[0]), one_plane(out[1])   # [K, ny, nx], [K, M, ny, nx]
             transfer = MOD.mtf(energy, sums)
             index = MOD.mti(transfer)
             extra = {}
@@ -342,114 +350,81 @@ def main():
             elif sti_rest is not None:
                 print("warning: --sti-rest and --modulation-bands leave octave bands of 125 Hz .. 8 kHz out: no sti is written", file=sys.stderr)
             np.savez(args.modulation_out, mtf=transfer, mti=index, energy=energy, bands_hz=np.array(modulation_centres),
-                     freqs_hz=np.array(MOD.STI_MODULATION_HZ), captures=captures, period=plan["period"], sample_rate=rate,
-                     plane=plan["box"][0][2], spacing=mesh.spacing,
-                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64), **extra)
+                     freqs_hz=np.array(MOD.STI_MODULATION_HZ), **shared, **extra)
             print("wrote modulation maps of plane z=%d (%d bands, %d captures; median MTI per band %s%s) to %s"
-                  % (plan["box"][0][2], len(modulation_centres), captures,
+                  % (shared["plane"], len(modulation_centres), captures,
                      ", ".join("%.3f" % np.nanmedian(m) if np.isfinite(m).any() else "not defined" for m in index),
                      "; median STI %.3f" % np.nanmedian(extra["sti"]) if "sti" in extra and np.isfinite(extra["sti"]).any() else "", args.modulation_out))
-        if lateral is not None:
+        if kind == "lateral":
             from wayverb_amd import lateral as L
-            env, mesh = W.Environment(), audio_etc[2].mesh
-            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
-            plan = W.lateral_plan_arguments(lateral, mesh, rate, env)
-            out, captures = audio_etc[3]
-            out = {k: (v[:, :, 0] if k == "bins" else v[:, 0] if k == "velocity" else v[0]) for k, v in out.items()}   # the one plane
+            out = {k: one_plane(v) for k, v in out.items()}   # onset, pre [ny, nx]; velocity [3, ny, nx]; bins [10, n_bins, ny, nx]
             came_from = L.direct_direction(out)
             axis = L.lateral_axis(came_from)
             # J_LF: the figure-of-eight's energy in 5 - 80 ms over the omni's in 0 - 80 ms, where both edges are bins of the plan
             lf = L.lateral_fraction(out, axis, 1, (0, 1), env.ambient_density, env.speed_of_sound) if len(plan["edges"]) == 3 else \
                 np.full(out["onset"].shape, np.nan)
             diffuse = L.diffuseness(out, env.ambient_density, env.speed_of_sound)
-            np.savez(args.lateral_out, edges=np.array(plan["edges"]), captures=captures, period=plan["period"], sample_rate=rate,
-                     plane=plan["box"][0][2], spacing=mesh.spacing,
-                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64),
-                     lf=lf, direct_direction=came_from, lateral_axis=axis, diffuseness=diffuse, **out)
+            np.savez(args.lateral_out, edges=np.array(plan["edges"]), lf=lf, direct_direction=came_from, lateral_axis=axis, diffuseness=diffuse,
+                     **shared, **out)
             heard = out["onset"] != L.NONE
             print("wrote lateral maps of plane z=%d (%d captures; %d of %d nodes heard an arrival; median LF %s) to %s"
-                  % (plan["box"][0][2], captures, heard.sum(), heard.size, "%.3f" % np.nanmedian(lf) if np.isfinite(lf).any() else "not defined",
+                  % (shared["plane"], captures, heard.sum(), heard.size, "%.3f" % np.nanmedian(lf) if np.isfinite(lf).any() else "not defined",
                      args.lateral_out))
-        if arrival is not None and "bands" in arrival:
+        if kind == "arrival":
             from wayverb_amd import arrival as A
-            env, mesh = W.Environment(), audio_etc[2].mesh
-            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
-            plan = W.arrival_bands_plan_arguments(arrival, mesh, rate)
-            out, captures = audio_etc[3]
-            # the one plane: onset, peak, peak_capture [ny, nx]; pre, moment [K, ny, nx]; bins [K, n_bins, ny, nx]
-            out = {k: (v[:, :, 0] if k == "bins" else v[:, 0] if k in ("pre", "moment") else v[0]) for k, v in out.items()}
-            edges, tail, period = plan["edges"], plan["tail"], plan["period"]
+            # the one plane: onset, peak, peak_capture [ny, nx]; per band pre, moment [K, ny, nx]; bins [n_bins, ny, nx] or [K, n_bins, ny, nx]
+            out = {k: one_plane(v) for k, v in out.items()}
+            heard = out["onset"] != A.NONE
+            period = plan["period"]
+        if name == "arrival_bands":
+            edges, tail = positional[0], plan["tail"]
             maps = dict(arrival_s=A.arrival_time(out["onset"], plan["first_step"], period, rate), direct_db=A.direct_level_db(out["peak"]),
                         c50_db=A.band_clarity(out["bins"], edges, 50.0, period, rate), c80_db=A.band_clarity(out["bins"], edges, 80.0, period, rate),
                         d50=A.band_definition(out["bins"], edges, 50.0, period, rate), ts_s=A.band_centre_time(out["moment"], out["bins"], period, rate))
             decays = A.band_decay_maps(out["bins"], edges, tail, period, rate)
             maps.update({k: decays[k] for k in ("edt_s", "t20_s", "t30_s")})
             np.savez(args.arrival_out, edges=np.array(edges), tail=np.array(tail or (0, 0, 0)), lag=np.array(plan["lag"]),
-                     bands_hz=np.array([float(v) for v in args.clarity_bands.split(",")]), captures=captures, period=period, sample_rate=rate,
-                     plane=plan["box"][0][2], spacing=mesh.spacing,
-                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64),
-                     **out, **maps)
-            heard = out["onset"] != A.NONE
+                     bands_hz=np.array([float(v) for v in args.clarity_bands.split(",")]), **shared, **out, **maps)
             print("wrote arrival maps of plane z=%d in %d bands (%d captures; %d of %d nodes heard an arrival; median C80 per band %s) to %s"
-                  % (plan["box"][0][2], out["bins"].shape[0], captures, heard.sum(), heard.size,
+                  % (shared["plane"], out["bins"].shape[0], captures, heard.sum(), heard.size,
                      ", ".join("%.1f dB" % np.median(c[np.isfinite(c)]) if np.isfinite(c).any() else "not defined" for c in maps["c80_db"]),
                      args.arrival_out))
-        elif arrival is not None:
-            from wayverb_amd import arrival as A
-            env, mesh = W.Environment(), audio_etc[2].mesh
-            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
-            plan = W.arrival_plan_arguments(arrival, mesh, rate)
-            out, captures = audio_etc[3]
-            out = {k: (v[:, 0] if k == "bins" else v[0]) for k, v in out.items()}   # the one plane: [ny, nx], bins [3, ny, nx]
-            maps = A.arrival_maps(out, plan["edges"], plan["first_step"], plan["period"], rate)
-            np.savez(args.arrival_out, edges=np.array(plan["edges"]), captures=captures, period=plan["period"], sample_rate=rate,
-                     plane=plan["box"][0][2], spacing=mesh.spacing,
-                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64),
-                     **out, **maps)
-            heard = out["onset"] != A.NONE
+        elif name == "arrival":
+            maps = A.arrival_maps(out, plan["edges"], plan["first_step"], period, rate)
+            np.savez(args.arrival_out, edges=np.array(plan["edges"]), **shared, **out, **maps)
             c80 = maps["c80_db"][np.isfinite(maps["c80_db"])]
             print("wrote arrival maps of plane z=%d (%d captures; %d of %d nodes heard an arrival; median C80 %s) to %s"
-                  % (plan["box"][0][2], captures, heard.sum(), heard.size, "%.1f dB" % np.median(c80) if c80.size else "not defined",
+                  % (shared["plane"], captures, heard.sum(), heard.size, "%.1f dB" % np.median(c80) if c80.size else "not defined",
                      args.arrival_out))
-        if intensity is not None:
+        if kind == "intensity":
             from wayverb_amd import intensity as I
-            env, mesh = W.Environment(), audio_etc[2].mesh
-            rate = W.compute_sample_rate(mesh.spacing, env.speed_of_sound)
-            plan = W.intensity_plan_arguments(intensity, mesh, rate, env, args.seconds)
-            bins, captures = audio_etc[3]
-            bins = bins[:, :, 0]   # the one plane: [4, n_bins, ny, nx]
+            bins = one_plane(out)   # [4, n_bins, ny, nx]
             _, magnitude, direction = I.net_intensity(bins)
             diffuse = I.diffuseness(bins, env.speed_of_sound, env.ambient_density)
             np.savez(args.intensity_out, bins=bins, times=np.arange(bins.shape[1]) * plan["bin_captures"] * plan["period"] / rate,
-                     net_direction=direction, net_magnitude=magnitude, diffuseness=diffuse, captures=captures, bin_captures=plan["bin_captures"],
-                     period=plan["period"], sample_rate=rate, plane=plan["box"][0][2], spacing=mesh.spacing,
-                     origin=np.asarray(mesh.min_corner, dtype=np.float64) + mesh.spacing * np.array(plan["box"][0], dtype=np.float64))
+                     net_direction=direction, net_magnitude=magnitude, diffuseness=diffuse, bin_captures=plan["bin_captures"], **shared)
             print("wrote intensity maps of plane z=%d (%d bins of %d captures, %d captures; median diffuseness %s) to %s"
-                  % (plan["box"][0][2], bins.shape[1], plan["bin_captures"], captures,
+                  % (shared["plane"], bins.shape[1], plan["bin_captures"], captures,
                      "%.3f" % np.nanmedian(diffuse) if np.isfinite(diffuse).any() else "not defined", args.intensity_out))
-        if decay is not None:
+        if kind == "decay":
             from wayverb_amd import decay as D
-            bins, captures = audio_etc[3]
-            bins = bins[..., 0, :, :]   # the one plane: [n_bins, ny, nx], per band [K, n_bins, ny, nx]
+            bins = one_plane(out)   # [n_bins, ny, nx], per band [K, n_bins, ny, nx]
+            per_bin = plan["bin_captures"]
             extra = {}
             if decay_centres:   # per band: every map gets a leading band axis
-                maps = D.band_decay_maps(bins, decay_plane["per_bin"], args.decay_every, decay_plane["rate"])
+                maps = D.band_decay_maps(bins, per_bin, args.decay_every, rate)
                 extra = dict(band_centres_hz=np.array(decay_centres), band_edges_hz=np.array(D.octave_band_edges(decay_centres)))
             else:
-                maps = D.decay_maps(bins, decay_plane["per_bin"], args.decay_every, decay_plane["rate"])
-            np.savez(args.decay_out, bins=bins, sample_rate=decay_plane["rate"], bin_captures=decay_plane["per_bin"],
-                     period=args.decay_every, captures=captures, plane=decay_plane["plane"], origin=decay_plane["origin"],
-                     spacing=audio_etc[2].mesh.spacing, **extra, **maps)
+                maps = D.decay_maps(bins, per_bin, args.decay_every, rate)
+            np.savez(args.decay_out, bins=bins, bin_captures=per_bin, **shared, **extra, **maps)
             t30 = maps["t30_s"][np.isfinite(maps["t30_s"])]
             print("wrote decay maps of plane z=%d (%d bins of %d captures, %d captures; median T30 %s) to %s"
-                  % (decay_plane["plane"], bins.shape[-3], decay_plane["per_bin"], captures,
-                     "%.3f s" % np.median(t30) if t30.size else "not defined", args.decay_out))
-        if spectrum is not None:
-            maps, captures = audio_etc[3]
-            np.savez(args.spectrum_out, spectrum=maps[:, 0], freqs_hz=np.array(freqs_hz), captures=captures,
+                  % (shared["plane"], bins.shape[-3], per_bin, captures, "%.3f s" % np.median(t30) if t30.size else "not defined", args.decay_out))
+        if kind == "spectrum":
+            np.savez(args.spectrum_out, spectrum=one_plane(out), freqs_hz=np.array(freqs_hz), captures=captures,
                      plane=spectrum_plane["plane"], z=spectrum_plane["z"])
-            print("wrote %d complex maps of plane z=%d (%d captures) to %s" % (maps.shape[0], spectrum_plane["plane"], captures, args.spectrum_out))
-        if snapshots is not None:
+            print("wrote %d complex maps of plane z=%d (%d captures) to %s" % (out.shape[0], spectrum_plane["plane"], captures, args.spectrum_out))
+        if kind == "snapshots":
             fields, steps = audio_etc[3]
             os.makedirs(args.snapshot_out, exist_ok=True)
             for field, step in zip(fields, steps):

@@ -74,26 +74,24 @@ class WvOptions(C.Structure):
                 ("tuning", WvTuning)]
 
 
+# what every capture plan begins with: a box of the mesh, a stride per axis, a cadence in steps
+_BOX_AND_CADENCE = [(name, C.c_int32) for name in ("x0", "y0", "z0", "nx", "ny", "nz", "sx", "sy", "sz")] + [("first_step", C.c_uint64), ("period", C.c_uint64)]
+
+
 class WvSnapshotPlan(C.Structure):
     """wv_snapshot_plan (include/wayverb_amd.h): a box of the mesh, a stride per axis, a cadence in steps."""
-    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
-                ("sx", C.c_int32), ("sy", C.c_int32), ("sz", C.c_int32), ("first_step", C.c_uint64), ("period", C.c_uint64),
-                ("keep", C.c_uint32), ("reserved", C.c_uint32)]
+    _fields_ = _BOX_AND_CADENCE + [("keep", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class WvSpectrumPlan(C.Structure):
     """wv_spectrum_plan (include/wayverb_amd.h): the snapshot plan's box, strides and cadence, and the number of frequencies."""
-    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
-                ("sx", C.c_int32), ("sy", C.c_int32), ("sz", C.c_int32), ("first_step", C.c_uint64), ("period", C.c_uint64),
-                ("n_freqs", C.c_uint32), ("reserved", C.c_uint32)]
+    _fields_ = _BOX_AND_CADENCE + [("n_freqs", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class WvDecayPlan(C.Structure):
     """wv_decay_plan (include/wayverb_amd.h): the snapshot plan's box, strides and cadence, the number of time bins and the captures
     per bin."""
-    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
-                ("sx", C.c_int32), ("sy", C.c_int32), ("sz", C.c_int32), ("first_step", C.c_uint64), ("period", C.c_uint64),
-                ("n_bins", C.c_uint32), ("bin_captures", C.c_uint32)]
+    _fields_ = _BOX_AND_CADENCE + [("n_bins", C.c_uint32), ("bin_captures", C.c_uint32)]
 
 
 class WvIntensityPlan(C.Structure):
@@ -105,14 +103,14 @@ class WvIntensityPlan(C.Structure):
 class WvArrivalPlan(C.Structure):
     """wv_arrival_plan (include/wayverb_amd.h): the box and the cadence as wv_decay_plan has them, then n_bins, the scalar threshold
     and the 16 bin edges in captures behind a node's onset."""
-    _fields_ = WvDecayPlan._fields_[:11] + [("n_bins", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 16)]
+    _fields_ = _BOX_AND_CADENCE + [("n_bins", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 16)]
 
 
 class WvLateralPlan(C.Structure):
     """wv_lateral_plan (include/wayverb_amd.h): the box and the cadence as wv_decay_plan has them, n_bins, the scalar threshold and
     the 8 bin edges in captures behind a node's onset, then the three arguments of the reference's directional_receiver constructor."""
-    _fields_ = WvDecayPlan._fields_[:11] + [("n_bins", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 8),
-                                            ("spacing", C.c_double), ("sample_rate", C.c_double), ("ambient_density", C.c_double)]
+    _fields_ = _BOX_AND_CADENCE + [("n_bins", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 8),
+                                   ("spacing", C.c_double), ("sample_rate", C.c_double), ("ambient_density", C.c_double)]
 
 
 class WvModulationPlan(C.Structure):
@@ -124,12 +122,28 @@ class WvModulationPlan(C.Structure):
 class WvArrivalBandsPlan(C.Structure):
     """wv_arrival_bands_plan (include/wayverb_amd.h): the box and the cadence as wv_decay_plan has them, n_edges, the scalar threshold and
     the 16 explicit edges as wv_arrival_plan has n_bins and its edges, then the uniform tail, the lag per band and a reserved word."""
-    _fields_ = WvDecayPlan._fields_[:11] + [("n_edges", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 16),
-                                            ("n_tail", C.c_uint32), ("tail_first", C.c_uint32), ("tail_captures", C.c_uint32),
-                                            ("lag", C.c_uint32 * 8), ("reserved", C.c_uint32)]
+    _fields_ = _BOX_AND_CADENCE + [("n_edges", C.c_uint32), ("threshold", C.c_float), ("edges", C.c_uint32 * 16),
+                                   ("n_tail", C.c_uint32), ("tail_first", C.c_uint32), ("tail_captures", C.c_uint32),
+                                   ("lag", C.c_uint32 * 8), ("reserved", C.c_uint32)]
 
 
 ARRIVAL_NONE = 0xFFFFFFFF   # onset / peak_capture of a node that has none yet
+
+# The capture plans as this layer remembers them (Engine.<name>_shape) and as the library counts them (wv_<name>_count) ...
+PLAN_NAMES = ("snapshot", "spectrum", "decay", "intensity", "arrival", "lateral", "modulation", "arrival_bands")
+# ... and their calls: wv_set_<key>(engine, plan, *what is listed first) and wv_fetch_<key>(engine, *what is listed second)
+_POINTER, _WORD, _RESULT = C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)
+_PLAN_CALLS = {
+    "snapshots": (WvSnapshotPlan, [], [C.c_uint64, C.c_uint64, _POINTER, _POINTER]),
+    "spectrum": (WvSpectrumPlan, [_POINTER], [_POINTER, _RESULT]),
+    "decay": (WvDecayPlan, [], [_POINTER, _RESULT]),
+    "decay_bands": (WvDecayPlan, [_POINTER, _WORD, _WORD], [_POINTER, _RESULT]),
+    "intensity": (WvIntensityPlan, [], [_POINTER, _RESULT]),
+    "arrival": (WvArrivalPlan, [_POINTER], [_POINTER] * 6 + [_RESULT]),
+    "lateral": (WvLateralPlan, [_POINTER], [_POINTER] * 4 + [_RESULT]),
+    "modulation": (WvModulationPlan, [_POINTER, _POINTER, _WORD, _WORD], [_POINTER, _POINTER, _RESULT]),
+    "arrival_bands": (WvArrivalBandsPlan, [_POINTER, _POINTER, _WORD, _WORD], [_POINTER] * 6 + [_RESULT]),
+}
 
 
 # Tuning applied to every engine this module creates unless the call says otherwise: {field of wv_tuning: value}, plus
@@ -231,36 +245,15 @@ def load_library():
     lib.wv_comm_init_local.argtypes = [C.POINTER(C.c_void_p), C.c_int32]
     lib.wv_run_group.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     lib.wv_make_box_nodes.argtypes = [C.c_int32] * 7 + [C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.wv_set_snapshots.argtypes = [C.c_void_p, C.POINTER(WvSnapshotPlan)]
-    lib.wv_snapshot_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.wv_fetch_snapshots.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.wv_set_spectrum.argtypes = [C.c_void_p, C.POINTER(WvSpectrumPlan), C.c_void_p]
-    lib.wv_spectrum_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.wv_fetch_spectrum.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    for key, (plan, beside_the_plan, fetched) in _PLAN_CALLS.items():
+        getattr(lib, "wv_set_" + key).argtypes = [C.c_void_p, C.POINTER(plan)] + beside_the_plan
+        getattr(lib, "wv_fetch_" + key).argtypes = [C.c_void_p] + fetched
+    for name in PLAN_NAMES:
+        getattr(lib, "wv_%s_count" % name).argtypes = [C.c_void_p, _RESULT, _RESULT]
     lib.wv_spectrum_twiddle.argtypes = [C.c_double, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.wv_spectrum_twiddle.restype = None
-    lib.wv_set_decay.argtypes = [C.c_void_p, C.POINTER(WvDecayPlan)]
-    lib.wv_decay_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.wv_fetch_decay.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.wv_set_decay_bands.argtypes = [C.c_void_p, C.POINTER(WvDecayPlan), C.c_void_p, C.c_uint32, C.c_uint32]
-    lib.wv_fetch_decay_bands.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.wv_set_intensity.argtypes = [C.c_void_p, C.POINTER(WvIntensityPlan)]
-    lib.wv_intensity_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.wv_fetch_intensity.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.wv_fetch_intensity_velocity.argtypes = [C.c_void_p, C.c_void_p]
     lib.wv_fetch_directional_velocity.argtypes = [C.c_void_p, C.c_void_p]
-    lib.wv_set_arrival.argtypes = [C.c_void_p, C.POINTER(WvArrivalPlan), C.c_void_p]
-    lib.wv_arrival_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.wv_fetch_arrival.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.POINTER(C.c_uint64)]
-    lib.wv_set_lateral.argtypes = [C.c_void_p, C.POINTER(WvLateralPlan), C.c_void_p]
-    lib.wv_lateral_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.wv_fetch_lateral.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.POINTER(C.c_uint64)]
-    lib.wv_set_modulation.argtypes = [C.c_void_p, C.POINTER(WvModulationPlan), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
-    lib.wv_modulation_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.wv_fetch_modulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.wv_set_arrival_bands.argtypes = [C.c_void_p, C.POINTER(WvArrivalBandsPlan), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
-    lib.wv_arrival_bands_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.wv_fetch_arrival_bands.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.POINTER(C.c_uint64)]
     lib.wv_biquad_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.wv_butterworth_bandpass.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.wv_bandpass_biquad.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
@@ -463,8 +456,8 @@ class Engine:
 
     def _plan_state(self):
         """What this layer remembers of the capture plans: the shape a fetch returns, None while the plan is not set."""
-        self.snapshot_shape = self.spectrum_shape = self.decay_shape = self.intensity_shape = None
-        self.arrival_shape = self.lateral_shape = self.modulation_shape = self.arrival_bands_shape = None
+        for name in PLAN_NAMES:
+            setattr(self, name + "_shape", None)
         self.decay_banded = False
 
     def close(self):
@@ -607,14 +600,14 @@ class Engine:
         if box is None:
             return self._stop_plan("snapshot", self.lib.wv_set_snapshots, None)
         plan = WvSnapshotPlan()
-        taken = self._fill_box(plan, box, stride)
-        plan.first_step, plan.period, plan.keep = int(first_step), int(period), int(keep)
+        taken = self._fill_box(plan, box, stride, first_step, period)
+        plan.keep = int(keep)
         _check(self.lib.wv_set_snapshots(self.h, C.byref(plan)))
         self.snapshot_shape = (taken[2], taken[1], taken[0])
         return self.snapshot_shape
 
-    def _fill_box(self, plan, box, stride):
-        """(origin, extent, stride) -> the plan's first node, nodes taken and strides; returns the nodes taken (x, y, z)."""
+    def _fill_box(self, plan, box, stride, first_step, period):
+        """(origin, extent, stride) -> the plan's first node, nodes taken and strides, and its cadence; returns the nodes taken (x, y, z)."""
         dims = self.mesh.dims
         origin, extent = ((0, 0, 0), None) if isinstance(box, str) and box == "mesh" else box
         extent = tuple(extent) if extent is not None else (None, None, None)
@@ -627,6 +620,7 @@ class Engine:
         plan.x0, plan.y0, plan.z0 = (int(v) for v in origin)
         plan.nx, plan.ny, plan.nz = taken
         plan.sx, plan.sy, plan.sz = (int(v) for v in stride)
+        plan.first_step, plan.period = int(first_step), int(period)
         return taken
 
     def _stop_plan(self, name, setter, *nulls):
@@ -645,15 +639,29 @@ class Engine:
         return ((1, 1, 1), tuple(d - 2 for d in self.mesh.dims))
 
     @staticmethod
-    def _fill_edges(plan, edges, most, who):
-        """The bin edges counted from a node's own onset -> the plan's n_bins and edges; returns n_bins."""
+    def _fill_edges(plan, edges, most, who, count="n_bins", what="bins"):
+        """The bin edges counted from a node's own onset -> the plan's edges and their number, which it calls `count`; returns the number."""
         edges = [int(v) for v in edges]
         if len(edges) > most:
-            raise ValueError("%s: %d bins at the most" % (who, most))
-        plan.n_bins = len(edges)
+            raise ValueError("%s: %d %s at the most" % (who, most, what))
+        setattr(plan, count, len(edges))
         for k, v in enumerate(edges):
             plan.edges[k] = v
         return len(edges)
+
+    @staticmethod
+    def _sections(bands, who):
+        """A filter bank as the library takes it: float64[K][S][5], contiguous."""
+        sections = np.ascontiguousarray(bands, dtype=np.float64)
+        if sections.ndim != 3 or sections.shape[2] != 5:
+            raise ValueError("%s: bands is float64[K][S][5], got shape %r" % (who, sections.shape))
+        return sections
+
+    def _fetch(self, fn, *arrays):
+        """A wv_fetch_* call that fills `arrays` and ends in a word for the captures in them, which is returned."""
+        captures = C.c_uint64()
+        _check(fn(self.h, *[a.ctypes.data_as(C.c_void_p) for a in arrays], C.byref(captures)))
+        return captures.value
 
     @staticmethod
     def _fill_constants(plan, spacing, sample_rate, ambient_density):
@@ -695,8 +703,8 @@ class Engine:
             return self._stop_plan("spectrum", self.lib.wv_set_spectrum, None, None)
         f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
         plan = WvSpectrumPlan()
-        taken = self._fill_box(plan, box, stride)
-        plan.first_step, plan.period, plan.n_freqs = int(first_step), int(period), f.shape[0]
+        taken = self._fill_box(plan, box, stride, first_step, period)
+        plan.n_freqs = f.shape[0]
         _check(self.lib.wv_set_spectrum(self.h, C.byref(plan), f.ctypes.data_as(C.c_void_p)))
         self.spectrum_shape = (f.shape[0], taken[2], taken[1], taken[0])
         return self.spectrum_shape
@@ -708,9 +716,7 @@ class Engine:
     def fetch_spectrum(self):
         """wv_fetch_spectrum: (complex128[K, nz, ny, nx], captures in it).  The plan keeps running."""
         out = np.zeros(tuple(self.spectrum_shape or (0, 0, 0, 0)), dtype=np.complex128)   # (no plan: the library says so)
-        captures = C.c_uint64()
-        _check(self.lib.wv_fetch_spectrum(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
-        return out, captures.value
+        return out, self._fetch(self.lib.wv_fetch_spectrum, out)
 
     # ---- time-binned field energy accumulated on the device while wv_run goes on ----------------------
     def set_decay(self, n_bins, bin_captures=1, box="mesh", stride=1, first_step=0, period=1, bands=None):
@@ -729,23 +735,16 @@ class Engine:
             self._stop_plan("decay", self.lib.wv_set_decay, None)   # (stops either kind of plan)
             self.decay_banded = False
             return None
-        if bands is not None:
-            sections = np.ascontiguousarray(bands, dtype=np.float64)
-            if sections.ndim != 3 or sections.shape[2] != 5:
-                raise ValueError("set_decay: bands is float64[K][S][5], got shape %r" % (sections.shape,))
-            plan = WvDecayPlan()
-            taken = self._fill_box(plan, box, stride)
-            plan.first_step, plan.period, plan.n_bins, plan.bin_captures = int(first_step), int(period), int(n_bins), int(bin_captures)
-            _check(self.lib.wv_set_decay_bands(self.h, C.byref(plan), sections.ctypes.data_as(C.c_void_p), sections.shape[0], sections.shape[1]))
-            self.decay_shape = (sections.shape[0], int(n_bins), taken[2], taken[1], taken[0])
-            self.decay_banded = True
-            return self.decay_shape
+        sections = self._sections(bands, "set_decay") if bands is not None else None
         plan = WvDecayPlan()
-        taken = self._fill_box(plan, box, stride)
-        plan.first_step, plan.period, plan.n_bins, plan.bin_captures = int(first_step), int(period), int(n_bins), int(bin_captures)
-        _check(self.lib.wv_set_decay(self.h, C.byref(plan)))
-        self.decay_shape = (int(n_bins), taken[2], taken[1], taken[0])
-        self.decay_banded = False
+        taken = self._fill_box(plan, box, stride, first_step, period)
+        plan.n_bins, plan.bin_captures = int(n_bins), int(bin_captures)
+        if sections is not None:
+            _check(self.lib.wv_set_decay_bands(self.h, C.byref(plan), sections.ctypes.data_as(C.c_void_p), sections.shape[0], sections.shape[1]))
+        else:
+            _check(self.lib.wv_set_decay(self.h, C.byref(plan)))
+        self.decay_shape = (() if sections is None else sections.shape[:1]) + (int(n_bins), taken[2], taken[1], taken[0])
+        self.decay_banded = sections is not None
         return self.decay_shape
 
     def decay_count(self):
@@ -757,12 +756,8 @@ class Engine:
         (float64[K, n_bins, nz, ny, nx], captures).  The plan keeps running.  `banded` = True / False asks for that call whatever the
         plan (the library refuses the wrong one)."""
         out = np.zeros(tuple(self.decay_shape or (0, 0, 0, 0)), dtype=np.float64)   # (no plan: the library says so)
-        captures = C.c_uint64()
-        if self.decay_banded if banded is None else banded:
-            _check(self.lib.wv_fetch_decay_bands(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
-        else:
-            _check(self.lib.wv_fetch_decay(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
-        return out, captures.value
+        banded = self.decay_banded if banded is None else banded
+        return out, self._fetch(self.lib.wv_fetch_decay_bands if banded else self.lib.wv_fetch_decay, out)
 
     # ---- time-binned sound intensity accumulated on the device while wv_run goes on ------------------
     def set_intensity(self, n_bins, bin_captures=1, box=None, stride=1, first_step=0, period=1, spacing=None, sample_rate=None,
@@ -779,8 +774,8 @@ class Engine:
         if box is None:
             box = self._interior_box()
         plan = WvIntensityPlan()
-        taken = self._fill_box(plan, box, stride)
-        plan.first_step, plan.period, plan.n_bins, plan.bin_captures = int(first_step), int(period), int(n_bins), int(bin_captures)
+        taken = self._fill_box(plan, box, stride, first_step, period)
+        plan.n_bins, plan.bin_captures = int(n_bins), int(bin_captures)
         self._fill_constants(plan, spacing, sample_rate, ambient_density)
         _check(self.lib.wv_set_intensity(self.h, C.byref(plan)))
         self.intensity_shape = (4, int(n_bins), taken[2], taken[1], taken[0])
@@ -793,9 +788,7 @@ class Engine:
     def fetch_intensity(self):
         """wv_fetch_intensity: (float64[4, n_bins, nz, ny, nx] = Ix, Iy, Iz, E, captures in it).  The plan keeps running."""
         out = np.zeros(tuple(self.intensity_shape or (0, 0, 0, 0, 0)), dtype=np.float64)   # (no plan: the library says so)
-        captures = C.c_uint64()
-        _check(self.lib.wv_fetch_intensity(self.h, out.ctypes.data_as(C.c_void_p), C.byref(captures)))
-        return out, captures.value
+        return out, self._fetch(self.lib.wv_fetch_intensity, out)
 
     def fetch_intensity_velocity(self):
         """wv_fetch_intensity_velocity: float64[3, nz, ny, nx], the velocities the integrator carries, after the captures folded so far."""
@@ -822,8 +815,8 @@ class Engine:
             return self._stop_plan("arrival", self.lib.wv_set_arrival, None, None)
         plan = WvArrivalPlan()
         n_bins = self._fill_edges(plan, edges, 16, "set_arrival")
-        taken = self._fill_box(plan, box, stride)
-        plan.first_step, plan.period, plan.threshold = int(first_step), int(period), float(threshold)
+        taken = self._fill_box(plan, box, stride, first_step, period)
+        plan.threshold = float(threshold)
         threshold_map, map_pointer = self._threshold_map(threshold_map, taken, "set_arrival")
         _check(self.lib.wv_set_arrival(self.h, C.byref(plan), map_pointer))
         self.arrival_shape = (n_bins, taken[2], taken[1], taken[0])
@@ -839,10 +832,7 @@ class Engine:
         shape = tuple(self.arrival_shape or (0, 0, 0, 0))   # (no plan: the library says so)
         out = dict(onset=np.zeros(shape[1:], np.uint32), peak=np.zeros(shape[1:], np.float32), peak_capture=np.zeros(shape[1:], np.uint32),
                    pre=np.zeros(shape[1:], np.float64), moment=np.zeros(shape[1:], np.float64), bins=np.zeros(shape, np.float64))
-        captures = C.c_uint64()
-        _check(self.lib.wv_fetch_arrival(self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in ("onset", "peak", "peak_capture", "pre", "moment", "bins")],
-                                         C.byref(captures)))
-        return out, captures.value
+        return out, self._fetch(self.lib.wv_fetch_arrival, *out.values())   # (in the order the library takes them)
 
     # ---- lateral maps accumulated on the device while wv_run goes on ---------------------------------
     def set_lateral(self, edges, threshold=0.0, box=None, stride=1, first_step=0, period=1, threshold_map=None, spacing=None,
@@ -858,8 +848,8 @@ class Engine:
             return self._stop_plan("lateral", self.lib.wv_set_lateral, None, None)
         plan = WvLateralPlan()
         n_bins = self._fill_edges(plan, edges, 8, "set_lateral")
-        taken = self._fill_box(plan, self._interior_box() if box is None else box, stride)
-        plan.first_step, plan.period, plan.threshold = int(first_step), int(period), float(threshold)
+        taken = self._fill_box(plan, self._interior_box() if box is None else box, stride, first_step, period)
+        plan.threshold = float(threshold)
         self._fill_constants(plan, spacing, sample_rate, ambient_density)
         threshold_map, map_pointer = self._threshold_map(threshold_map, taken, "set_lateral")
         _check(self.lib.wv_set_lateral(self.h, C.byref(plan), map_pointer))
@@ -876,9 +866,7 @@ class Engine:
         shape = tuple(self.lateral_shape or (0, 0, 0, 0, 0))   # (no plan: the library says so)
         out = dict(onset=np.zeros(shape[2:], np.uint32), pre=np.zeros(shape[2:], np.float64), velocity=np.zeros((3,) + shape[2:], np.float64),
                    bins=np.zeros(shape, np.float64))
-        captures = C.c_uint64()
-        _check(self.lib.wv_fetch_lateral(self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in ("onset", "pre", "velocity", "bins")], C.byref(captures)))
-        return out, captures.value
+        return out, self._fetch(self.lib.wv_fetch_lateral, *out.values())   # (in the order the library takes them)
 
     # ---- modulation maps accumulated on the device while wv_run goes on ------------------------------
     def set_modulation(self, freqs, bands, box="mesh", stride=1, first_step=0, period=1):
@@ -892,12 +880,10 @@ class Engine:
         if freqs is None:
             return self._stop_plan("modulation", self.lib.wv_set_modulation, None, None, None, 0, 0)
         f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
-        sections = np.ascontiguousarray(bands, dtype=np.float64)
-        if sections.ndim != 3 or sections.shape[2] != 5:
-            raise ValueError("set_modulation: bands is float64[K][S][5], got shape %r" % (sections.shape,))
+        sections = self._sections(bands, "set_modulation")
         plan = WvModulationPlan()
-        taken = self._fill_box(plan, box, stride)
-        plan.first_step, plan.period, plan.n_freqs = int(first_step), int(period), f.shape[0]
+        taken = self._fill_box(plan, box, stride, first_step, period)
+        plan.n_freqs = f.shape[0]
         _check(self.lib.wv_set_modulation(self.h, C.byref(plan), f.ctypes.data_as(C.c_void_p), sections.ctypes.data_as(C.c_void_p), sections.shape[0],
                                           sections.shape[1]))
         self.modulation_shape = (sections.shape[0], f.shape[0], taken[2], taken[1], taken[0])
@@ -929,16 +915,9 @@ class Engine:
         Returns the shape of the bins, (K, n_edges + n_tail, nz, ny, nx)."""
         if edges is None:
             return self._stop_plan("arrival_bands", self.lib.wv_set_arrival_bands, None, None, None, 0, 0)
-        sections = np.ascontiguousarray(bands, dtype=np.float64)
-        if sections.ndim != 3 or sections.shape[2] != 5:
-            raise ValueError("set_arrival_bands: bands is float64[K][S][5], got shape %r" % (sections.shape,))
+        sections = self._sections(bands, "set_arrival_bands")
         plan = WvArrivalBandsPlan()
-        edges = [int(v) for v in edges]
-        if len(edges) > 16:
-            raise ValueError("set_arrival_bands: 16 explicit bins at the most")
-        plan.n_edges = len(edges)
-        for k, v in enumerate(edges):
-            plan.edges[k] = v
+        self._fill_edges(plan, edges, 16, "set_arrival_bands", count="n_edges", what="explicit bins")
         if tail is not None:
             plan.n_tail, plan.tail_first, plan.tail_captures = (int(v) for v in tail)
         lags = [int(lag)] * min(sections.shape[0], 8) if np.isscalar(lag) else [int(v) for v in lag]
@@ -946,8 +925,8 @@ class Engine:
             raise ValueError("set_arrival_bands: one lag, or one per band")
         for k, v in enumerate(lags):
             plan.lag[k] = v
-        taken = self._fill_box(plan, box, stride)
-        plan.first_step, plan.period, plan.threshold, plan.reserved = int(first_step), int(period), float(threshold), int(reserved)
+        taken = self._fill_box(plan, box, stride, first_step, period)
+        plan.threshold, plan.reserved = float(threshold), int(reserved)
         threshold_map, map_pointer = self._threshold_map(threshold_map, taken, "set_arrival_bands")
         _check(self.lib.wv_set_arrival_bands(self.h, C.byref(plan), map_pointer, sections.ctypes.data_as(C.c_void_p), sections.shape[0], sections.shape[1]))
         self.arrival_bands_shape = (sections.shape[0], plan.n_edges + plan.n_tail, taken[2], taken[1], taken[0])
@@ -965,10 +944,7 @@ class Engine:
         node, band = shape[2:], shape[:1] + shape[2:]
         out = dict(onset=np.zeros(node, np.uint32), peak=np.zeros(node, np.float32), peak_capture=np.zeros(node, np.uint32),
                    pre=np.zeros(band, np.float64), moment=np.zeros(band, np.float64), bins=np.zeros(shape, np.float64))
-        captures = C.c_uint64()
-        _check(self.lib.wv_fetch_arrival_bands(self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in ("onset", "peak", "peak_capture", "pre", "moment", "bins")],
-                                               C.byref(captures)))
-        return out, captures.value
+        return out, self._fetch(self.lib.wv_fetch_arrival_bands, *out.values())   # (in the order the library takes them)
 
     def step_count(self):
         s = C.c_uint64()

@@ -107,24 +107,52 @@ def compute_voxels_and_mesh(vertices, triangles, surface_absorptions, anchor, sa
     return VoxelsAndMesh(vox, (c0, c1), side, vertices, triangles, mesh, c0, absorptions)
 
 
+def _keys_and_cadence(plan, who, keys, required=()):
+    """What every plan dict of canonical's is checked for first: no key but `plane`, `box` and `keys`, one of `plane` and `box`, every
+    one of `required` -- or the sentence that lists the keys -- and every >= 1.  Returns `every`."""
+    if set(plan) - {"plane", "box"} - set(keys) or ("plane" in plan) == ("box" in plan) or any(k not in plan for k in required):
+        raise ValueError("%s=dict(plane=<z in metres> or box=..., %s)" % (who, ", ".join(k + "=" for k in keys)))
+    every = int(plan.get("every", 1))
+    if every < 1:
+        raise ValueError("%s: every must be >= 1" % who)
+    return every
+
+
+def _plane_or_box(plan, who, mesh, rimless):
+    """The plan dict's box, or its `plane` (z in metres) as a box of the mesh: the whole horizontal plane, or, `rimless`, that plane less
+    its rim, where every taken node has its six neighbours on the grid."""
+    if "plane" not in plan:
+        return plan["box"]
+    plane = int(round((float(plan["plane"]) - mesh.min_corner[2]) / mesh.spacing))
+    rim = 1 if rimless else 0
+    if not rim <= plane <= mesh.dims[2] - 1 - rim:
+        raise ValueError("%s: plane z=%g m %s" % (who, float(plan["plane"]),
+                                                  "has no node with both neighbours in the mesh" if rimless else "is outside the mesh"))
+    return ((1, 1, plane), (mesh.dims[0] - 2, mesh.dims[1] - 2, 1)) if rimless else ((0, 0, plane), (None, None, 1))
+
+
+def octave_band_warnings(centres, edges, sample_rate, every, who="modulation: ", cadence="every=%d"):
+    """What is to be said about octave bands the run cannot carry: a sentence per band whose upper edge lies above a quarter of the
+    sample rate, where the waveguide is not trusted, and one per band above the Nyquist rate of the series captured every `every` steps,
+    where it aliases.  `who` begins every sentence, `cadence` is how the caller spells `every`."""
+    said = []
+    for c, (lo, hi) in zip(centres, edges):
+        if hi > 0.25 * sample_rate:
+            said.append("%sthe %g Hz band reaches %.1f Hz, above a quarter of the sample rate (%.1f Hz): the waveguide is not trusted there"
+                        % (who, c, hi, 0.25 * sample_rate))
+        if hi > 0.5 * sample_rate / every:
+            said.append("%sthe %g Hz band reaches %.1f Hz, above the Nyquist rate of the captured series (%.1f Hz with %s): it aliases"
+                        % (who, c, hi, 0.5 * sample_rate / every, cadence % every))
+    return said
+
+
 def intensity_plan_arguments(intensity, mesh, sample_rate, environment, simulation_time):
     """canonical's `intensity` dict -> keyword arguments of Engine.set_intensity: dict(plane=z in metres | box=((x0, y0, z0), extent),
     stride=1, every=1, n_bins=None, bin_seconds=None).  `plane`: that horizontal plane less its rim (every taken node needs its six
     neighbours on the grid).  The bins are `bin_seconds` long (default: the run in `n_bins` bins, default 1); spacing, the rate of the
     captured series (sample_rate / every) and the environment's density are filled in."""
-    unknown = set(intensity) - {"plane", "box", "stride", "every", "n_bins", "bin_seconds", "first_step"}
-    if unknown or ("plane" in intensity) == ("box" in intensity):
-        raise ValueError("intensity=dict(plane=<z in metres> or box=..., every=, n_bins=, bin_seconds=, stride=, first_step=)")
-    every = int(intensity.get("every", 1))
-    if every < 1:
-        raise ValueError("intensity: every must be >= 1")
-    if "plane" in intensity:
-        plane = int(round((float(intensity["plane"]) - mesh.min_corner[2]) / mesh.spacing))
-        if not 1 <= plane <= mesh.dims[2] - 2:
-            raise ValueError("intensity: plane z=%g m has no node with both neighbours in the mesh" % float(intensity["plane"]))
-        box = ((1, 1, plane), (mesh.dims[0] - 2, mesh.dims[1] - 2, 1))
-    else:
-        box = intensity["box"]
+    every = _keys_and_cadence(intensity, "intensity", ("every", "n_bins", "bin_seconds", "stride", "first_step"))
+    box = _plane_or_box(intensity, "intensity", mesh, rimless=True)
     captures = int(math.ceil(sample_rate * simulation_time)) // every + 1
     if intensity.get("bin_seconds") is not None:
         bin_captures = max(1, int(round(float(intensity["bin_seconds"]) * sample_rate / every)))
@@ -142,19 +170,8 @@ def arrival_plan_arguments(arrival, mesh, sample_rate):
     bins begin at each node's onset and at every one of `early_ms` milliseconds behind it (arrival.edges_from_ms at the rate of the
     captured series, sample_rate / every); `threshold` is the pressure magnitude that counts as the arrival of the direct sound."""
     from . import arrival as A
-    unknown = set(arrival) - {"plane", "box", "stride", "every", "threshold", "threshold_map", "early_ms", "first_step"}
-    if unknown or ("plane" in arrival) == ("box" in arrival) or "threshold" not in arrival:
-        raise ValueError("arrival=dict(plane=<z in metres> or box=..., threshold=, every=, early_ms=, threshold_map=, stride=, first_step=)")
-    every = int(arrival.get("every", 1))
-    if every < 1:
-        raise ValueError("arrival: every must be >= 1")
-    if "plane" in arrival:
-        plane = int(round((float(arrival["plane"]) - mesh.min_corner[2]) / mesh.spacing))
-        if not 0 <= plane <= mesh.dims[2] - 1:
-            raise ValueError("arrival: plane z=%g m is outside the mesh" % float(arrival["plane"]))
-        box = ((0, 0, plane), (None, None, 1))
-    else:
-        box = arrival["box"]
+    every = _keys_and_cadence(arrival, "arrival", ("threshold", "every", "early_ms", "threshold_map", "stride", "first_step"), required=("threshold",))
+    box = _plane_or_box(arrival, "arrival", mesh, rimless=False)
     return dict(edges=A.edges_from_ms(arrival.get("early_ms", (50.0, 80.0)), every, sample_rate), threshold=float(arrival["threshold"]),
                 threshold_map=arrival.get("threshold_map"), box=box, stride=arrival.get("stride", 1),
                 first_step=int(arrival.get("first_step", 0)), period=every)
@@ -195,22 +212,11 @@ def lateral_plan_arguments(lateral, mesh, sample_rate, environment):
     default, bin 1 over bins 0 and 1 is J_LF's 5 .. 80 ms over 0 .. 80 ms); `threshold` is the pressure magnitude that counts as the
     arrival of the direct sound; spacing, the rate of the captured series and the environment's density are filled in."""
     from . import lateral as L
-    unknown = set(lateral) - {"plane", "box", "stride", "every", "threshold", "threshold_map", "edges_ms", "first_step"}
-    if unknown or ("plane" in lateral) == ("box" in lateral) or "threshold" not in lateral:
-        raise ValueError("lateral=dict(plane=<z in metres> or box=..., threshold=, every=, edges_ms=, threshold_map=, stride=, first_step=)")
-    every = int(lateral.get("every", 1))
-    if every < 1:
-        raise ValueError("lateral: every must be >= 1")
+    every = _keys_and_cadence(lateral, "lateral", ("threshold", "every", "edges_ms", "threshold_map", "stride", "first_step"), required=("threshold",))
     edges_ms = [float(m) for m in lateral.get("edges_ms", (0.0, 5.0, 80.0))]
     if not edges_ms or edges_ms[0] != 0.0 or len(edges_ms) > L.MAX_BINS:
         raise ValueError("lateral: edges_ms begins with 0 and has 8 entries at the most")
-    if "plane" in lateral:
-        plane = int(round((float(lateral["plane"]) - mesh.min_corner[2]) / mesh.spacing))
-        if not 1 <= plane <= mesh.dims[2] - 2:
-            raise ValueError("lateral: plane z=%g m has no node with both neighbours in the mesh" % float(lateral["plane"]))
-        box = ((1, 1, plane), (mesh.dims[0] - 2, mesh.dims[1] - 2, 1))
-    else:
-        box = lateral["box"]
+    box = _plane_or_box(lateral, "lateral", mesh, rimless=True)
     return dict(edges=L.edges_from_ms(edges_ms[1:], every, sample_rate), threshold=float(lateral["threshold"]),
                 threshold_map=lateral.get("threshold_map"), box=box, stride=lateral.get("stride", 1), first_step=int(lateral.get("first_step", 0)),
                 period=every, spacing=mesh.spacing, sample_rate=sample_rate / every, ambient_density=environment.ambient_density)
@@ -226,36 +232,60 @@ def modulation_plan_arguments(modulation, mesh, sample_rate):
     import warnings
     from . import decay as D
     from . import modulation as MOD
-    unknown = set(modulation) - {"plane", "box", "stride", "every", "bands_hz", "freqs_hz", "first_step"}
-    if unknown or ("plane" in modulation) == ("box" in modulation):
-        raise ValueError("modulation=dict(plane=<z in metres> or box=..., every=, bands_hz=, freqs_hz=, stride=, first_step=)")
-    every = int(modulation.get("every", 1))
-    if every < 1:
-        raise ValueError("modulation: every must be >= 1")
+    every = _keys_and_cadence(modulation, "modulation", ("every", "bands_hz", "freqs_hz", "stride", "first_step"))
     centres = [float(c) for c in np.atleast_1d(modulation.get("bands_hz", (125, 250, 500)))]
     freqs_hz = np.atleast_1d(np.asarray(modulation.get("freqs_hz", MOD.STI_MODULATION_HZ), dtype=np.float64))
     if not 1 <= len(centres) <= 8 or any(not c > 0 for c in centres):
         raise ValueError("modulation: bands_hz holds 1 .. 8 positive octave centres")
     if not 1 <= freqs_hz.shape[0] <= 16:
         raise ValueError("modulation: freqs_hz holds 1 .. 16 modulation frequencies")
-    if "plane" in modulation:
-        plane = int(round((float(modulation["plane"]) - mesh.min_corner[2]) / mesh.spacing))
-        if not 0 <= plane <= mesh.dims[2] - 1:
-            raise ValueError("modulation: plane z=%g m is outside the mesh" % float(modulation["plane"]))
-        box = ((0, 0, plane), (None, None, 1))
-    else:
-        box = modulation["box"]
+    box = _plane_or_box(modulation, "modulation", mesh, rimless=False)
     series_rate = sample_rate / every
     edges = D.octave_band_edges(centres)
-    for c, (lo, hi) in zip(centres, edges):
-        if hi > 0.25 * sample_rate:
-            warnings.warn("modulation: the %g Hz band reaches %.1f Hz, above a quarter of the sample rate (%.1f Hz): the waveguide is not "
-                          "trusted there" % (c, hi, 0.25 * sample_rate))
-        if hi > 0.5 * series_rate:
-            warnings.warn("modulation: the %g Hz band reaches %.1f Hz, above the Nyquist rate of the captured series (%.1f Hz with "
-                          "every=%d): it aliases" % (c, hi, 0.5 * series_rate, every))
+    for sentence in octave_band_warnings(centres, edges, sample_rate, every):
+        warnings.warn(sentence)
     return dict(freqs=MOD.cycles_per_step(freqs_hz, sample_rate), bands=np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in edges]),
                 box=box, stride=modulation.get("stride", 1), first_step=int(modulation.get("first_step", 0)), period=every)
+
+
+def _decay_plan(decay, mesh, sample_rate, environment, simulation_time):
+    if decay.get("bands") is not None:
+        from . import decay as D
+        series_rate = sample_rate / int(decay.get("period", 1))
+        decay = dict(decay, bands=np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in decay["bands"]]))
+    return "decay", (), decay
+
+
+def _arrival_plan(arrival, mesh, sample_rate, environment, simulation_time):
+    if "bands" not in arrival:
+        return "arrival", (), arrival_plan_arguments(arrival, mesh, sample_rate)
+    plan = arrival_bands_plan_arguments(arrival, mesh, sample_rate)
+    return "arrival_bands", (plan.pop("edges"), plan.pop("bands")), plan
+
+
+# canonical's plan keywords in the order their plans are set and fetched: how (the caller's value, mesh, sample_rate, environment,
+# simulation_time) becomes (<name>, positional, keyword arguments) of Engine.set_<name>, whose fetch is Engine.fetch_<name>
+PLANS = (
+    ("snapshots", lambda plan, *_: ("snapshots", (), plan)),
+    ("spectrum", lambda plan, mesh, sample_rate, *_: ("spectrum", (), spectrum_plan_arguments(plan, sample_rate))),
+    ("decay", _decay_plan),
+    ("intensity", lambda plan, *run: ("intensity", (), intensity_plan_arguments(plan, *run))),
+    ("arrival", _arrival_plan),
+    ("lateral", lambda plan, mesh, sample_rate, environment, _: ("lateral", (), lateral_plan_arguments(plan, mesh, sample_rate, environment))),
+    ("modulation", lambda plan, mesh, sample_rate, *_: ("modulation", (), modulation_plan_arguments(plan, mesh, sample_rate))),
+)
+
+
+def plan_call(keyword, plan, mesh, sample_rate, environment, simulation_time):
+    """What canonical does with the value of one plan keyword: (name, positional, keyword arguments) -- Engine.set_<name>(*positional,
+    **keyword arguments) sets the plan, Engine.fetch_<name>() fetches it.  A banded arrival plan's bin edges are positional[0]."""
+    return dict(PLANS)[keyword](plan, mesh, sample_rate, environment, simulation_time)
+
+
+# what the refusal of slabs > 1 calls each of them, in the order it looks
+SLABS_REFUSALS = {"modulation": "modulation maps are accumulated", "lateral": "lateral maps are accumulated", "arrival": "arrival maps are accumulated",
+                  "intensity": "intensity bins are accumulated", "decay": "decay bins are accumulated", "snapshots": "snapshots are taken",
+                  "spectrum": "a spectrum is accumulated"}
 
 
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
@@ -306,37 +336,17 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     value is then (bands, ((energy float64[K, nz, ny, nx], sums complex128[K, M, nz, ny, nx]), captures)), which wayverb_amd.modulation
     turns into the modulation transfer function and the speech transmission index.  One domain only, and not together with another
     plan."""
-    if modulation is not None and slabs > 1:
-        raise ValueError("modulation maps are accumulated on one domain only (slabs=1)")
-    if lateral is not None and slabs > 1:
-        raise ValueError("lateral maps are accumulated on one domain only (slabs=1)")
-    if arrival is not None and slabs > 1:
-        raise ValueError("arrival maps are accumulated on one domain only (slabs=1)")
-    if intensity is not None and slabs > 1:
-        raise ValueError("intensity bins are accumulated on one domain only (slabs=1)")
-    if decay is not None and slabs > 1:
-        raise ValueError("decay bins are accumulated on one domain only (slabs=1)")
-    if snapshots is not None and slabs > 1:
-        raise ValueError("snapshots are taken on one domain only (slabs=1)")
-    if spectrum is not None and slabs > 1:
-        raise ValueError("a spectrum is accumulated on one domain only (slabs=1)")
-    if spectrum is not None and snapshots is not None:
+    asked = {keyword: plan for keyword, plan in (("snapshots", snapshots), ("spectrum", spectrum), ("decay", decay), ("intensity", intensity),
+                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation)) if plan is not None}
+    for keyword in SLABS_REFUSALS:
+        if keyword in asked and slabs > 1:
+            raise ValueError("%s on one domain only (slabs=1)" % SLABS_REFUSALS[keyword])
+    if "spectrum" in asked and "snapshots" in asked:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
     mesh = vm.mesh
     sample_rate = compute_sample_rate(mesh.spacing, environment.speed_of_sound)
-    spectrum_plan = spectrum_plan_arguments(spectrum, sample_rate) if spectrum is not None else None
-    if decay is not None and decay.get("bands") is not None:
-        from . import decay as D
-        series_rate = sample_rate / int(decay.get("period", 1))
-        decay = dict(decay, bands=np.stack([D.butterworth_bandpass(lo, hi, series_rate) for lo, hi in decay["bands"]]))
-    intensity_plan = intensity_plan_arguments(intensity, mesh, sample_rate, environment, simulation_time) if intensity is not None else None
-    arrival_banded = arrival is not None and "bands" in arrival
-    if arrival_banded:
-        arrival_plan = arrival_bands_plan_arguments(arrival, mesh, sample_rate)
-    else:
-        arrival_plan = arrival_plan_arguments(arrival, mesh, sample_rate) if arrival is not None else None
-    lateral_plan = lateral_plan_arguments(lateral, mesh, sample_rate, environment) if lateral is not None else None
-    modulation_plan = modulation_plan_arguments(modulation, mesh, sample_rate) if modulation is not None else None
+    # (name of the Engine's plan, positional and keyword arguments of its set_*), in PLANS' order
+    plans = [plan_call(keyword, asked[keyword], mesh, sample_rate, environment, simulation_time) for keyword, _ in PLANS if keyword in asked]
 
     def mesh_index(pt):
         idx = vm.compute_index(pt)
@@ -359,46 +369,19 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     else:
         eng = E.Engine(mesh, precision=precision, device=device)
         try:
-            if snapshots is not None:
-                eng.set_snapshots(**snapshots)
-            if spectrum_plan is not None:
-                eng.set_spectrum(**spectrum_plan)
-            if decay is not None:
-                eng.set_decay(**decay)
-            if intensity_plan is not None:
-                eng.set_intensity(**intensity_plan)
-            if arrival_banded:
-                eng.set_arrival_bands(arrival_plan.pop("edges"), arrival_plan.pop("bands"), **arrival_plan)
-            elif arrival_plan is not None:
-                eng.set_arrival(**arrival_plan)
-            if lateral_plan is not None:
-                eng.set_lateral(**lateral_plan)
-            if modulation_plan is not None:
-                eng.set_modulation(**modulation_plan)
+            for name, positional, keywords in plans:
+                getattr(eng, "set_" + name)(*positional, **keywords)
             done, traces = E.run_fast(eng, E.SOURCE_HARD, mesh_index(source), signal, [receiver_index] + list(neighbours),
                                       keep_going=keep_going)
-            taken = eng.fetch_snapshots() if snapshots is not None else None
-            if spectrum_plan is not None:
-                taken = eng.fetch_spectrum()
-            if decay is not None:
-                taken = eng.fetch_decay()
-            if intensity_plan is not None:
-                taken = eng.fetch_intensity()
-            if arrival_plan is not None:
-                taken = eng.fetch_arrival_bands() if arrival_banded else eng.fetch_arrival()
-            if lateral_plan is not None:
-                taken = eng.fetch_lateral()
-            if modulation_plan is not None:
-                taken = (eng.fetch_modulation(), eng.modulation_count()[0])
+            for name, _, _ in plans:   # (of two plans the later one's is returned)
+                taken = (eng.fetch_modulation(), eng.modulation_count()[0]) if name == "modulation" else getattr(eng, "fetch_" + name)()
         finally:
             eng.close()
     if done != ideal_steps:
         return None
     directional = P.directional_receiver(traces, mesh.spacing, sample_rate, environment.ambient_density)
     bands = [(directional, sample_rate, (0.0, float(cutoff)))]
-    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None and lateral is None and modulation is None:
-        return bands
-    return bands, taken
+    return (bands, taken) if asked else bands
 
 
 def spectrum_plan_arguments(spectrum, sample_rate):
@@ -534,29 +517,17 @@ def impulse_response(vertices, triangles, surface_absorptions, source, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
     if spectrum is not None and snapshots is not None:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
-    if snapshots is None and spectrum is None and decay is None and intensity is None and arrival is None and lateral is None and modulation is None:
-        bands = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device)
-        taken = None
-    else:
-        plans = {}
-        for which, plan in (("snapshots", snapshots), ("spectrum", spectrum)):
-            if plan is not None:
-                plans[which] = plan(vm.mesh) if callable(plan) else plan
-        if decay is not None:
-            rate = compute_sample_rate(vm.mesh.spacing, environment.speed_of_sound)
-            plans["decay"] = decay(vm.mesh, rate) if callable(decay) else decay
-        if intensity is not None:
-            plans["intensity"] = intensity
-        if arrival is not None:
-            plans["arrival"] = arrival
-        if lateral is not None:
-            plans["lateral"] = lateral
-        if modulation is not None:
-            plans["modulation"] = modulation
-        both = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, **plans)
-        if both is None:
-            raise RuntimeError("the waveguide run was stopped early")
-        bands, taken = both
+    plans = {keyword: plan for keyword, plan in (("snapshots", snapshots), ("spectrum", spectrum), ("decay", decay), ("intensity", intensity),
+                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation)) if plan is not None}
+    for keyword in ("snapshots", "spectrum"):
+        if callable(plans.get(keyword)):
+            plans[keyword] = plans[keyword](vm.mesh)
+    if callable(plans.get("decay")):
+        plans["decay"] = decay(vm.mesh, compute_sample_rate(vm.mesh.spacing, environment.speed_of_sound))
+    got = canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision, device, **plans)
+    if plans and got is None:
+        raise RuntimeError("the waveguide run was stopped early")
+    bands, taken = got if plans else (got, None)
     audio = P.postprocess(bands, method, pointing, shape, environment.acoustic_impedance, output_sample_rate)
     return (audio, bands, vm) if taken is None else (audio, bands, vm, taken)
 
