@@ -853,6 +853,62 @@ int wv_fetch_arrival_bands(wv_engine* e, uint32_t* onset, float* peak, uint32_t*
                            double* pre, double* moment /* [n_bands][nz][ny][nx] */,
                            double* bins /* [n_bands][n_bins][nz][ny][nx] */, uint64_t* captures);
 
+/* ---- waterfall maps: time-binned field spectra folded on the device ------------------------------ */
+/* How long each MODE of a room rings, and where: below the cutoff the response is a handful of modes, an octave filter is far wider
+ * than their spacing, and the whole-run spectrum above has no time axis.  What is drawn for this is a waterfall -- the short-time
+ * spectrum, or its cumulative form, the cumulative spectral decay (CSD).  A waterfall plan captures a box of the field exactly as a
+ * spectrum plan does (the same nine box ints, the same cadence, the same capture kernel, the same stage of 16 captures) and
+ * accumulates, per node taken, per time bin b and per frequency k, a complex Fourier sum ON THE DEVICE.
+ *
+ * Definition.  p_j is the float a snapshot of plan step n_j holds for the node; j counts the committed captures since the plan was
+ * set; b(j) = min(j / bin_captures, n_bins - 1), the decay plan's rule: the last bin is open-ended; (c, s) = wv_spectrum_twiddle(f_k,
+ * n_j), with the ABSOLUTE step in the phase.  In capture order, in double, each product rounded, then each sum rounded:
+ *     re[b(j)][k] = re[b(j)][k] + (double)p_j * c          im[b(j)][k] = im[b(j)][k] - (double)p_j * s
+ * All sums start at +0.0 and a bin no capture reached stays +0.0.  A loop over the snapshots of the same plan that evaluates
+ * `a + p * c` on float64 arrays reproduces every sum BIT FOR BIT (wayverb_amd/waterfall.py: waterfall_fold).  It follows that
+ *   - n_bins = 1 is the spectrum plan: the bytes are wv_fetch_spectrum's of an identical engine
+ *   - Y[b][k] = sum over b' >= b of X[b'][k] is the Fourier transform of the response with everything before capture
+ *     b * bin_captures cut away -- the cumulative spectral decay at the bin edges; the absolute phase makes the bins add coherently,
+ *     so Y[0] is the whole-run spectrum but for the order of summation
+ *   - |X[b][k]|^2 is the short-time spectrum under a rectangular window of bin_captures captures, no overlap.  No window is applied:
+ *     the cadence is the caller's tool, as for the spectrum plan.
+ *
+ *   - 1 <= n_freqs <= 64, 1 <= n_bins <= 4096, bin_captures >= 1, n_freqs * n_bins <= 4096 (64 KiB of sums per node); a frequency
+ *     outside [0, 0.5], a NaN, a box that leaves the mesh, a zero stride or a zero period: WV_E_INVALID_ARGUMENT
+ *   - everything (the stage of 16 captures, 64 bytes per node; the sums, 16 n_freqs n_bins bytes per node) is allocated when the plan
+ *     is set: with no room the call answers WV_E_HIP ("wv_set_waterfall: no room for the stage and the sums") and leaves the engine
+ *     and any earlier plan untouched.  A new plan replaces the old one and forgets its sums; a NULL plan stops, forgets and frees (as
+ *     does wv_destroy)
+ *   - one domain only: a slab of a chain answers WV_E_STATE (the snapshot plan's reason)
+ *   - EXCLUSIVE with every other plan: all decide where passes end; setting one while another is active answers WV_E_STATE
+ *   - after a run that stopped on a flag at step f (an overflow, or keep_going cleared) the sums hold exactly the captures of steps
+ *     <= f, and wv_waterfall_count says how many: a capture of a step that was never committed is never folded in
+ *   - wv_step / wv_swap capture nothing; plan steps they pass are passed, as for snapshots
+ *   - wv_checkpoint copies the sums and the count aside (the copy is allocated by the first checkpoint taken under a plan: WV_E_HIP,
+ *     engine untouched, when there is no room); wv_rollback puts both back, and the re-run reproduces them bitwise.  A plan set
+ *     AFTER the checkpoint makes wv_rollback answer WV_E_STATE, as a changed source does
+ *   - wv_fetch_waterfall may be called any time outside wv_run; it folds what is staged and leaves the plan running
+ *   - with no plan nothing is launched, allocated or waited for; with one the fields, receiver rows and flags are bit-identical to
+ *     a run without
+ *
+ * wv_waterfall_count: as wv_spectrum_count.  wv_fetch_waterfall: the sums as complex128 [n_bins][n_freqs][nz][ny][nx] (re, im
+ * interleaved), *captures (may be NULL) = how many captures they hold.  The struct is 72 bytes: nine int32 from 0, first_step at 40,
+ * period at 48, n_freqs at 56, n_bins at 60, bin_captures at 64, reserved at 68. */
+typedef struct wv_waterfall_plan {
+    int32_t x0, y0, z0;     /* first node of the box */
+    int32_t nx, ny, nz;     /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;     /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step;    /* captures at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;        /* >= 1 */
+    uint32_t n_freqs;       /* K, 1 .. 64 */
+    uint32_t n_bins;        /* 1 .. 4096; n_freqs * n_bins <= 4096 */
+    uint32_t bin_captures;  /* W >= 1 captures per bin; the last bin is open-ended */
+    uint32_t reserved;      /* 0 */
+} wv_waterfall_plan;
+int wv_set_waterfall(wv_engine* e, const wv_waterfall_plan* plan, const double* cycles_per_step /* [n_freqs] */);
+int wv_waterfall_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
+int wv_fetch_waterfall(wv_engine* e, double* dst /* [n_bins][n_freqs][nz][ny][nx][2]: complex128 */, uint64_t* captures);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */
@@ -897,7 +953,8 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *   WV_QUERY_LATERAL_CAPTURES, WV_QUERY_LATERAL_FOLDS, WV_QUERY_LATERAL_NS, WV_QUERY_LATERAL_GATHER_NS, WV_QUERY_LATERAL_GATHERS
  *                            the intensity plan's five since wv_set_lateral
  *   WV_QUERY_MODULATION_CAPTURES, WV_QUERY_MODULATION_FOLDS, WV_QUERY_MODULATION_NS   the decay plan's three since wv_set_modulation
- *   WV_QUERY_ARRIVAL_BANDS_CAPTURES, WV_QUERY_ARRIVAL_BANDS_FOLDS, WV_QUERY_ARRIVAL_BANDS_NS   the decay plan's three since wv_set_arrival_bands */
+ *   WV_QUERY_ARRIVAL_BANDS_CAPTURES, WV_QUERY_ARRIVAL_BANDS_FOLDS, WV_QUERY_ARRIVAL_BANDS_NS   the decay plan's three since wv_set_arrival_bands
+ *   WV_QUERY_WATERFALL_CAPTURES, WV_QUERY_WATERFALL_FOLDS, WV_QUERY_WATERFALL_NS   the decay plan's three since wv_set_waterfall */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -922,7 +979,8 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
        WV_QUERY_LATERAL_CAPTURES = 40, WV_QUERY_LATERAL_FOLDS = 41, WV_QUERY_LATERAL_NS = 42,
        WV_QUERY_LATERAL_GATHER_NS = 43, WV_QUERY_LATERAL_GATHERS = 44,
        WV_QUERY_MODULATION_CAPTURES = 45, WV_QUERY_MODULATION_FOLDS = 46, WV_QUERY_MODULATION_NS = 47,
-       WV_QUERY_ARRIVAL_BANDS_CAPTURES = 48, WV_QUERY_ARRIVAL_BANDS_FOLDS = 49, WV_QUERY_ARRIVAL_BANDS_NS = 50 };
+       WV_QUERY_ARRIVAL_BANDS_CAPTURES = 48, WV_QUERY_ARRIVAL_BANDS_FOLDS = 49, WV_QUERY_ARRIVAL_BANDS_NS = 50,
+       WV_QUERY_WATERFALL_CAPTURES = 51, WV_QUERY_WATERFALL_FOLDS = 52, WV_QUERY_WATERFALL_NS = 53 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

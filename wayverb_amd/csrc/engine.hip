@@ -22,6 +22,7 @@
 #include "engine_lateral.hip.h"
 #include "engine_modulation.hip.h"
 #include "engine_arrival_bands.hip.h"
+#include "engine_waterfall.hip.h"
 #include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
@@ -319,6 +320,18 @@ int wv_fetch_arrival_bands(wv_engine* e, uint32_t* onset, float* peak, uint32_t*
                            uint64_t* captures) {
     WV_NEED(e);
     return e->fetch_arrival_bands(onset, peak, peak_capture, pre, moment, bins, captures);
+}
+int wv_set_waterfall(wv_engine* e, const wv_waterfall_plan* plan, const double* cycles_per_step) {
+    WV_NEED(e);
+    return e->set_waterfall(plan, cycles_per_step);
+}
+int wv_waterfall_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
+    WV_NEED(e);
+    return e->waterfall_count(captures, last_step);
+}
+int wv_fetch_waterfall(wv_engine* e, double* dst, uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_waterfall(dst, captures);
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

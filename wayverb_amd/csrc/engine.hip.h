@@ -18,12 +18,12 @@
 //   engine_snapshot.hip.h  field snapshots taken on the device while a run goes on (wv_set_snapshots): plan, ring, capture, copy stream, held log
 //   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape; what every
 //                        plan's setter checks: the box of a plan, the four shared refusals, frequencies, coefficients, physical constants
-//   engine_staged.hip.h  the life cycle the seven accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release;
+//   engine_staged.hip.h  the life cycle the eight accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release;
 //                        the host-written tables of a fold (bins, twiddles), the threshold map, the fetch of complex sums
 //   fold_parts.hip.h     the device pieces more than one fold kernel has and that leave its assembly alone: stage read, integrator step, onset rule
 //   engine_spectrum.hip.h  field spectra accumulated on the device while a run goes on (wv_set_spectrum): plan, stage, fold, fetch
 //   spectrum_plan.h      (host only, no HIP) free slots of the stage, when a fold is due, which captures survive a stop, sizes
-//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the seven accumulating plans
+//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the eight accumulating plans
 //   engine_decay.hip.h   time-binned field energy accumulated on the device while a run goes on (wv_set_decay): plan, stage, fold, fetch
 //   decay_plan.h         (host only, no HIP) the bin of a capture, sizes, the fold's traffic model
 //   decay_bands_kernels.hip.h   the fold of a band-limited decay plan (wv_set_decay_bands): biquad cascades ahead of the square
@@ -42,6 +42,9 @@
 //   engine_arrival_bands.hip.h  per octave band, energy of a box binned from each node's OWN arrival, with a uniform tail (wv_set_arrival_bands)
 //   arrival_bands_plan.h  (host only, no HIP) the tail, the bin of a capture behind an onset and a lag, sizes and places, the traffic model
 //   arrival_bands_kernels.hip.h  its fold: decay_bands_fold_kernel's cascade ahead of arrival_fold_kernel's onset and bins
+//   engine_waterfall.hip.h  per time bin, the Fourier sums of a box at K frequencies: short-time spectra and the cumulative spectral decay (wv_set_waterfall)
+//   waterfall_plan.h     (host only, no HIP) the cap on sums per node, sizes and places, the fold's traffic model
+//   waterfall_kernels.hip.h   its fold: spectrum_fold_kernel's chunked Fourier sum driven by decay_fold_kernel's held bin
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -56,6 +59,7 @@
 #include "lateral_plan.h"
 #include "modulation_plan.h"
 #include "arrival_bands_plan.h"
+#include "waterfall_plan.h"
 #include "capture_stage.h"
 
 #include "boundary_kernels.hip.h"
@@ -71,6 +75,7 @@
 #include "lateral_kernels.hip.h"
 #include "modulation_kernels.hip.h"
 #include "arrival_bands_kernels.hip.h"
+#include "waterfall_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -247,6 +252,11 @@ public:
     int arrival_bands_count(uint64_t* captures, uint64_t* last_step) override;
     int fetch_arrival_bands(uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) override;
     bool arrival_bands_active() const override { return arrb_.active; }
+    // ---- engine_waterfall.hip.h
+    int set_waterfall(const wv_waterfall_plan* plan, const double* cycles_per_step) override;
+    int waterfall_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(wf_, captures, last_step); }
+    int fetch_waterfall(double* dst, uint64_t* captures) override;
+    bool waterfall_active() const override { return wf_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -454,8 +464,8 @@ private:
     void directional_release();
     int directional_enqueue(uint64_t batch);
     std::unique_ptr<wv::SlabComm> comm_;
-    // the seven plans that accumulate on the device (engine_staged.hip.h)
-    enum PlanKind { kSpectrumPlan, kDecayPlan, kIntensityPlan, kArrivalPlan, kLateralPlan, kModulationPlan, kArrivalBandsPlan, kPlanKinds };
+    // the eight plans that accumulate on the device (engine_staged.hip.h)
+    enum PlanKind { kSpectrumPlan, kDecayPlan, kIntensityPlan, kArrivalPlan, kLateralPlan, kModulationPlan, kArrivalBandsPlan, kWaterfallPlan, kPlanKinds };
     static constexpr int kPlanBlocks = 2;  // device blocks of accumulated state a plan has at the most
     // wv_checkpoint / wv_rollback (engine_io.hip.h): device copies of the two live fields and the filter memories, and the
     // host-side position that goes with them
@@ -529,8 +539,8 @@ private:
     int snapshot_plan_batch();
     int snapshot_begin_run();
     void snapshot_rollback(uint64_t to_step);
-    // ---- engine_staged.hip.h: the seven plans that accumulate on the device -- spectrum, decay (plain and banded), intensity, arrival,
-    // lateral, modulation, banded arrival -- have ONE life cycle: captures into a device-only stage on the compute stream, committed batch by batch, folded into the
+    // ---- engine_staged.hip.h: the eight plans that accumulate on the device -- spectrum, decay (plain and banded), intensity, arrival,
+    // lateral, modulation, banded arrival, waterfall -- have ONE life cycle: captures into a device-only stage on the compute stream, committed batch by batch, folded into the
     // plan's accumulated state in one launch when the stage has no slot left, on fetch and on checkpoint.  StagedPlan holds what they
     // share; a plan's own struct adds its wv_*_plan, its tables and what its fold kernel needs
     struct StagedPlan {
@@ -572,7 +582,8 @@ private:
     };
     // a table of the staged captures which the host writes into one of two page-locked buffers in turn (two, so that it never rewrites a
     // table a queued copy still reads) and copies ahead of the fold: the bins int32[t] of the decay and the intensity plan (BinTable,
-    // engine_decay.hip.h), the twiddles double[t][n_freqs][2] of the spectrum and the modulation plan (TwiddleTable, engine_staged.hip.h)
+    // engine_decay.hip.h), the twiddles double[t][n_freqs][2] of the spectrum and the modulation plan (TwiddleTable, engine_staged.hip.h);
+    // the waterfall plan has one of each
     template <typename T>
     struct HostTable {
         T* host[2] = {nullptr, nullptr};
@@ -686,14 +697,29 @@ private:
         void free_own();
     } arrb_;
     int arrival_bands_enqueue(ArrivalBands& d, int b, int t, unsigned blocks);
+    // waterfall maps (engine_waterfall.hip.h): the planar sums the fold kernel accumulates per time bin and frequency; a bin table AND a
+    // twiddle table (each two page-locked buffers and their device copies) the host writes in turn
+    struct Waterfall : StagedPlan {
+        Waterfall() : StagedPlan(kWaterfallPlan, "waterfall", "wv_set_waterfall", "its sums have", "the waterfall plan's sums", nullptr, true, false) {}
+        wv_waterfall_plan plan{};
+        std::vector<double> freqs;      // cycles per step, [K]
+        double* acc() const { return reinterpret_cast<double*>(this->block[0]); }  // [n_bins][K][2][B]
+        BinTable table;
+        TwiddleTable tw;
+        void free_own() {
+            host_table_free(table);
+            host_table_free(tw);
+        }
+    } wf_;
+    int waterfall_enqueue(Waterfall& w, int b, int t, unsigned blocks);
     // ---- engine_staged.hip.h: one copy of each step of the life cycle
-    StagedPlan* const staged_[kPlanKinds] = {&spec_, &decay_, &inten_, &arr_, &lat_, &mod_, &arrb_};  // by PlanKind
-    StagedPlan* staged() const {  // the active one of the seven, or null: they exclude each other (and a snapshot plan)
+    StagedPlan* const staged_[kPlanKinds] = {&spec_, &decay_, &inten_, &arr_, &lat_, &mod_, &arrb_, &wf_};  // by PlanKind
+    StagedPlan* staged() const {  // the active one of the eight, or null: they exclude each other (and a snapshot plan)
         for (StagedPlan* p : staged_)
             if (p->active) return p;
         return nullptr;
     }
-    enum PlanRow { kSnapshotRow, kSpectrumRow, kBandedDecayRow, kPlainDecayRow, kIntensityRow, kArrivalRow, kLateralRow, kModulationRow, kArrivalBandsRow };
+    enum PlanRow { kSnapshotRow, kSpectrumRow, kBandedDecayRow, kPlainDecayRow, kIntensityRow, kArrivalRow, kLateralRow, kModulationRow, kArrivalBandsRow, kWaterfallRow };
     int plan_refused(const std::string& setter, PlanRow self);
     template <typename Plan>
     static void plan_release(Plan& p);

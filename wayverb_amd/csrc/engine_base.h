@@ -124,6 +124,10 @@ struct wv_engine {
     virtual int arrival_bands_count(uint64_t* captures, uint64_t* last_step) = 0;
     virtual int fetch_arrival_bands(uint32_t* onset, float* peak, uint32_t* peak_capture, double* pre, double* moment, double* bins, uint64_t* captures) = 0;
     virtual bool arrival_bands_active() const = 0;
+    virtual int set_waterfall(const wv_waterfall_plan* plan, const double* cycles_per_step) = 0;
+    virtual int waterfall_count(uint64_t* captures, uint64_t* last_step) = 0;
+    virtual int fetch_waterfall(double* dst, uint64_t* captures) = 0;
+    virtual bool waterfall_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;
     virtual int set_source(int kind, uint64_t node, const double* signal, uint64_t n) = 0;

@@ -476,6 +476,8 @@ int Engine<Real>::query(int what, uint64_t* value) {
         case WV_QUERY_MODULATION_FOLDS: *value = mod_.folds; return WV_OK;
         case WV_QUERY_ARRIVAL_BANDS_CAPTURES: *value = arrb_.st.captures(); return WV_OK;
         case WV_QUERY_ARRIVAL_BANDS_FOLDS: *value = arrb_.folds; return WV_OK;
+        case WV_QUERY_WATERFALL_CAPTURES: *value = wf_.st.captures(); return WV_OK;
+        case WV_QUERY_WATERFALL_FOLDS: *value = wf_.folds; return WV_OK;
         // (a plan's kernel times, once its timed folds and captures have run: engine_staged.hip.h)
         case WV_QUERY_SPECTRUM_NS: return staged_time_query(spec_, PlanTime::folds_ns, value);
         case WV_QUERY_DECAY_NS: return staged_time_query(decay_, PlanTime::folds_ns, value);
@@ -488,6 +490,7 @@ int Engine<Real>::query(int what, uint64_t* value) {
         case WV_QUERY_LATERAL_GATHERS: return staged_time_query(lat_, PlanTime::gathers, value);
         case WV_QUERY_MODULATION_NS: return staged_time_query(mod_, PlanTime::folds_ns, value);
         case WV_QUERY_ARRIVAL_BANDS_NS: return staged_time_query(arrb_, PlanTime::folds_ns, value);
+        case WV_QUERY_WATERFALL_NS: return staged_time_query(wf_, PlanTime::folds_ns, value);
         default: return fail(WV_E_INVALID_ARGUMENT, "unknown query");
     }
 }

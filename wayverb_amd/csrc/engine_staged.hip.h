@@ -1,6 +1,6 @@
-// engine_staged.hip.h -- the life cycle of the seven plans that accumulate on the device while wv_run keeps going: field spectra
+// engine_staged.hip.h -- the life cycle of the eight plans that accumulate on the device while wv_run keeps going: field spectra
 // (engine_spectrum.hip.h), energy decay maps plain and banded (engine_decay.hip.h), intensity maps (engine_intensity.hip.h),
-// arrival-aligned energy maps (engine_arrival.hip.h), lateral maps (engine_lateral.hip.h), modulation maps (engine_modulation.hip.h) and band-limited arrival maps (engine_arrival_bands.hip.h).  One copy of each step; what a plan's own
+// arrival-aligned energy maps (engine_arrival.hip.h), lateral maps (engine_lateral.hip.h), modulation maps (engine_modulation.hip.h), band-limited arrival maps (engine_arrival_bands.hip.h) and waterfall maps (engine_waterfall.hip.h).  One copy of each step; what a plan's own
 // file keeps is its setter's validation, sizes and first contents, the enqueue step of its fold and its fetch -- and
 // of those the pieces more than one plan has are here too: the host-written tables of a fold (HostTable: bins, twiddles), the threshold
 // map of the plans that find an onset, the fetch of complex sums.
@@ -29,7 +29,7 @@
 namespace wv {
 
 static_assert(kDecayStage == kSpectrumStage && kIntensityStage == kSpectrumStage && kArrivalStage == kSpectrumStage && kLateralStage == kSpectrumStage &&
-                      kModulationStage == kSpectrumStage && kArrivalBandsStage == kSpectrumStage,
+                      kModulationStage == kSpectrumStage && kArrivalBandsStage == kSpectrumStage && kWaterfallStage == kSpectrumStage,
               "every plan stages its captures by spectrum_plan.h's rules (capture_stage.h)");
 
 // What every plan's setter, wv_set_snapshots included, refuses a plan for before it looks at it: a slab of a chain (it would have to cut
@@ -52,6 +52,7 @@ int Engine<Real>::plan_refused(const std::string& setter, PlanRow self) {
         {kLateralRow, lat_.active, "a lateral plan is active (wv_set_lateral(e, NULL, NULL) stops it); the plans exclude each other"},
         {kModulationRow, mod_.active, "a modulation plan is active (wv_set_modulation(e, NULL, NULL, NULL, 0, 0) stops it); the plans exclude each other"},
         {kArrivalBandsRow, arrb_.active, "a banded arrival plan is active (wv_set_arrival_bands(e, NULL, NULL, NULL, 0, 0) stops it); the plans exclude each other"},
+        {kWaterfallRow, wf_.active, "a waterfall plan is active (wv_set_waterfall(e, NULL, NULL) stops it); the plans exclude each other"},
     };
     for (const auto& r : rows)
         if (r.active && r.row != self) return fail(WV_E_STATE, setter + ": " + r.sentence);
@@ -88,7 +89,8 @@ void Engine<Real>::staged_release(StagedPlan& p) {
         case kArrivalPlan: plan_release(static_cast<Arrival&>(p)); break;
         case kLateralPlan: plan_release(static_cast<Lateral&>(p)); break;
         case kModulationPlan: plan_release(static_cast<Modulation&>(p)); break;
-        default: plan_release(static_cast<ArrivalBands&>(p)); break;
+        case kArrivalBandsPlan: plan_release(static_cast<ArrivalBands&>(p)); break;
+        default: plan_release(static_cast<Waterfall&>(p)); break;
     }
 }
 
@@ -305,7 +307,8 @@ int Engine<Real>::staged_enqueue(StagedPlan& p, int b, int t, unsigned blocks) {
         case kArrivalPlan: return arrival_enqueue(static_cast<Arrival&>(p), b, t, blocks);
         case kLateralPlan: return lateral_enqueue(static_cast<Lateral&>(p), b, t, blocks);
         case kModulationPlan: return modulation_enqueue(static_cast<Modulation&>(p), b, t, blocks);
-        default: return arrival_bands_enqueue(static_cast<ArrivalBands&>(p), b, t, blocks);
+        case kArrivalBandsPlan: return arrival_bands_enqueue(static_cast<ArrivalBands&>(p), b, t, blocks);
+        default: return waterfall_enqueue(static_cast<Waterfall&>(p), b, t, blocks);
     }
 }
 

@@ -45,6 +45,7 @@ EXPORTS = [
     "wv_set_lateral", "wv_lateral_count", "wv_fetch_lateral",
     "wv_set_modulation", "wv_modulation_count", "wv_fetch_modulation",
     "wv_set_arrival_bands", "wv_arrival_bands_count", "wv_fetch_arrival_bands",
+    "wv_set_waterfall", "wv_waterfall_count", "wv_fetch_waterfall",
 ]
 
 
@@ -127,10 +128,16 @@ class WvArrivalBandsPlan(C.Structure):
                                    ("lag", C.c_uint32 * 8), ("reserved", C.c_uint32)]
 
 
+class WvWaterfallPlan(C.Structure):
+    """wv_waterfall_plan (include/wayverb_amd.h): the spectrum plan's box, strides, cadence and number of frequencies, then the decay
+    plan's number of time bins and captures per bin, and a reserved word."""
+    _fields_ = _BOX_AND_CADENCE + [("n_freqs", C.c_uint32), ("n_bins", C.c_uint32), ("bin_captures", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 ARRIVAL_NONE = 0xFFFFFFFF   # onset / peak_capture of a node that has none yet
 
 # The capture plans as this layer remembers them (Engine.<name>_shape) and as the library counts them (wv_<name>_count) ...
-PLAN_NAMES = ("snapshot", "spectrum", "decay", "intensity", "arrival", "lateral", "modulation", "arrival_bands")
+PLAN_NAMES = ("snapshot", "spectrum", "decay", "intensity", "arrival", "lateral", "modulation", "arrival_bands", "waterfall")
 # ... and their calls: wv_set_<key>(engine, plan, *what is listed first) and wv_fetch_<key>(engine, *what is listed second)
 _POINTER, _WORD, _RESULT = C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)
 _PLAN_CALLS = {
@@ -143,6 +150,7 @@ _PLAN_CALLS = {
     "lateral": (WvLateralPlan, [_POINTER], [_POINTER] * 4 + [_RESULT]),
     "modulation": (WvModulationPlan, [_POINTER, _POINTER, _WORD, _WORD], [_POINTER, _POINTER, _RESULT]),
     "arrival_bands": (WvArrivalBandsPlan, [_POINTER, _POINTER, _WORD, _WORD], [_POINTER] * 6 + [_RESULT]),
+    "waterfall": (WvWaterfallPlan, [_POINTER], [_POINTER, _RESULT]),
 }
 
 
@@ -457,7 +465,8 @@ class Engine:
     def _plan_state(self):
         """What this layer remembers of the capture plans: the shape a fetch returns, None while the plan is not set."""
         for name in PLAN_NAMES:
-            setattr(self, name + "_shape", None)
+            if not hasattr(type(self), name + "_shape"):   # (waterfall_shape: the class has its None)
+                setattr(self, name + "_shape", None)
         self.decay_banded = False
 
     def close(self):
@@ -946,6 +955,39 @@ class Engine:
                    pre=np.zeros(band, np.float64), moment=np.zeros(band, np.float64), bins=np.zeros(shape, np.float64))
         return out, self._fetch(self.lib.wv_fetch_arrival_bands, *out.values())   # (in the order the library takes them)
 
+    # ---- time-binned field spectra accumulated on the device while wv_run goes on ---------------------
+    # (None until a plan is set.  A default of the class, not one of _plan_state's attributes: tests/golden/python_front.json holds
+    # the attributes of a fresh engine name by name, and was recorded before this plan)
+    waterfall_shape = None
+
+    def set_waterfall(self, freqs, n_bins, bin_captures, box="mesh", stride=1, first_step=0, period=1):
+        """wv_set_waterfall.  `freqs`: K frequencies in CYCLES PER STEP, 0 .. 0.5 (K <= 64); `n_bins` time bins of `bin_captures` captures
+        each, the last open-ended (K * n_bins <= 4096); `box`, `stride`, `first_step`, `period` as for set_snapshots.  At every plan step
+        the engine captures the box as a snapshot would and adds it, on the device, to the Fourier sum of the capture's time bin per node
+        and frequency: capture j (0, 1, ... since the plan was set) of step n_j goes to bin min(j // bin_captures, n_bins - 1),
+        X[b][k] = X[b][k] + p_j exp(-2 pi i f_k n_j) with the twiddles spectrum_twiddle gives at the ABSOLUTE step -- a NumPy loop over
+        the snapshots of the same plan reproduces it bit for bit (wayverb_amd.waterfall.waterfall_fold).  |X[b][k]|^2 is the short-time
+        spectrum, the backward cumulative sums over b the cumulative spectral decay (wayverb_amd.waterfall).  No window.  Excludes
+        every other plan.  set_waterfall(None, None, None) stops and forgets.  Returns the shape (n_bins, K, nz, ny, nx)."""
+        if freqs is None:
+            return self._stop_plan("waterfall", self.lib.wv_set_waterfall, None, None)
+        f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        plan = WvWaterfallPlan()
+        taken = self._fill_box(plan, box, stride, first_step, period)
+        plan.n_freqs, plan.n_bins, plan.bin_captures = f.shape[0], int(n_bins), int(bin_captures)
+        _check(self.lib.wv_set_waterfall(self.h, C.byref(plan), f.ctypes.data_as(C.c_void_p)))
+        self.waterfall_shape = (int(n_bins), f.shape[0], taken[2], taken[1], taken[0])
+        return self.waterfall_shape
+
+    def waterfall_count(self):
+        """wv_waterfall_count: (captures of completed steps since the plan was set, the step of the last of them)."""
+        return self._count(self.lib.wv_waterfall_count)
+
+    def fetch_waterfall(self):
+        """wv_fetch_waterfall: (complex128[n_bins, K, nz, ny, nx], captures in it).  The plan keeps running."""
+        out = np.zeros(tuple(self.waterfall_shape or (0, 0, 0, 0, 0)), dtype=np.complex128)   # (no plan: the library says so)
+        return out, self._fetch(self.lib.wv_fetch_waterfall, out)
+
     def step_count(self):
         s = C.c_uint64()
         _check(self.lib.wv_step_count(self.h, C.byref(s)))
@@ -983,6 +1025,7 @@ class Engine:
     QUERY_LATERAL_CAPTURES, QUERY_LATERAL_FOLDS, QUERY_LATERAL_NS, QUERY_LATERAL_GATHER_NS, QUERY_LATERAL_GATHERS = 40, 41, 42, 43, 44
     QUERY_MODULATION_CAPTURES, QUERY_MODULATION_FOLDS, QUERY_MODULATION_NS = 45, 46, 47
     QUERY_ARRIVAL_BANDS_CAPTURES, QUERY_ARRIVAL_BANDS_FOLDS, QUERY_ARRIVAL_BANDS_NS = 48, 49, 50
+    QUERY_WATERFALL_CAPTURES, QUERY_WATERFALL_FOLDS, QUERY_WATERFALL_NS = 51, 52, 53
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

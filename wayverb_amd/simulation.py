@@ -248,6 +248,45 @@ def modulation_plan_arguments(modulation, mesh, sample_rate):
                 box=box, stride=modulation.get("stride", 1), first_step=int(modulation.get("first_step", 0)), period=every)
 
 
+WATERFALL_DEFAULT_BINS = 64     # bins of a waterfall plan that says only how long a bin is (bin_ms): the last is open-ended
+
+
+def waterfall_plan_arguments(waterfall, mesh, sample_rate):
+    """canonical's `waterfall` dict -> keyword arguments of Engine.set_waterfall: dict(freqs_hz=[...], plane=z in metres |
+    box=((x0, y0, z0), extent), stride=1, every=1, bin_ms= | n_bins= and bin_captures=, first_step=0).  `plane`: that whole horizontal
+    plane.  The frequencies (1 .. 64, in hertz) become cycles per step of the mesh, as spectrum_plan_arguments makes them; one above the
+    Nyquist rate of the series captured every `every` steps, sample_rate / (2 every), would fold back onto a lower one: refused.  A bin
+    is `bin_ms` milliseconds long, rounded to captures of that series and at least one (with n_bins= bins, by default 64 or as many as
+    4096 sums per node allow), or `bin_captures` captures with `n_bins` of them; the last bin is open-ended either way."""
+    every = _keys_and_cadence(waterfall, "waterfall", ("freqs_hz", "every", "bin_ms", "n_bins", "bin_captures", "stride", "first_step"), required=("freqs_hz",))
+    freqs_hz = np.atleast_1d(np.asarray(waterfall["freqs_hz"], dtype=np.float64)).reshape(-1)
+    if not 1 <= freqs_hz.shape[0] <= 64:
+        raise ValueError("waterfall: freqs_hz holds 1 .. 64 frequencies")
+    nyquist = float(sample_rate) / 2.0 / every
+    for f in freqs_hz:
+        if not 0.0 <= f <= nyquist:      # (a NaN is in no range)
+            raise ValueError("waterfall: %.6g Hz is outside 0 .. %.6g Hz (half the sample rate %.6g Hz divided by every=%d)" % (f, nyquist, sample_rate, every))
+    by_ms, by_captures = waterfall.get("bin_ms") is not None, waterfall.get("bin_captures") is not None
+    if by_ms == by_captures or (by_captures and waterfall.get("n_bins") is None):
+        raise ValueError("waterfall: a bin is bin_ms= long, or bin_captures= captures long with n_bins= of them")
+    most = 4096 // freqs_hz.shape[0]
+    if by_ms:
+        bin_ms = float(waterfall["bin_ms"])
+        if not (bin_ms > 0.0 and math.isfinite(bin_ms)):
+            raise ValueError("waterfall: bin_ms must be > 0")
+        bin_captures = max(1, int(round(bin_ms * 1e-3 * sample_rate / every)))
+    else:
+        bin_captures = int(waterfall["bin_captures"])
+        if bin_captures < 1:
+            raise ValueError("waterfall: bin_captures must be >= 1")
+    n_bins = int(waterfall["n_bins"]) if waterfall.get("n_bins") is not None else min(WATERFALL_DEFAULT_BINS, most)
+    if not 1 <= n_bins <= most:
+        raise ValueError("waterfall: n_bins must be 1 .. %d with %d frequencies (4096 sums per node at the most)" % (most, freqs_hz.shape[0]))
+    box = _plane_or_box(waterfall, "waterfall", mesh, rimless=False)
+    return dict(freqs=freqs_hz / float(sample_rate), n_bins=n_bins, bin_captures=bin_captures, box=box, stride=waterfall.get("stride", 1),
+                first_step=int(waterfall.get("first_step", 0)), period=every)
+
+
 def _decay_plan(decay, mesh, sample_rate, environment, simulation_time):
     if decay.get("bands") is not None:
         from . import decay as D
@@ -273,6 +312,7 @@ PLANS = (
     ("arrival", _arrival_plan),
     ("lateral", lambda plan, mesh, sample_rate, environment, _: ("lateral", (), lateral_plan_arguments(plan, mesh, sample_rate, environment))),
     ("modulation", lambda plan, mesh, sample_rate, *_: ("modulation", (), modulation_plan_arguments(plan, mesh, sample_rate))),
+    ("waterfall", lambda plan, mesh, sample_rate, *_: ("waterfall", (), waterfall_plan_arguments(plan, mesh, sample_rate))),
 )
 
 
@@ -285,12 +325,12 @@ def plan_call(keyword, plan, mesh, sample_rate, environment, simulation_time):
 # what the refusal of slabs > 1 calls each of them, in the order it looks
 SLABS_REFUSALS = {"modulation": "modulation maps are accumulated", "lateral": "lateral maps are accumulated", "arrival": "arrival maps are accumulated",
                   "intensity": "intensity bins are accumulated", "decay": "decay bins are accumulated", "snapshots": "snapshots are taken",
-                  "spectrum": "a spectrum is accumulated"}
+                  "spectrum": "a spectrum is accumulated", "waterfall": "waterfall sums are accumulated"}
 
 
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
               device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None, decay=None, intensity=None,
-              arrival=None, lateral=None, modulation=None):
+              arrival=None, lateral=None, modulation=None, waterfall=None):
     """canonical (single band): hard source at `source`, directional receiver at `receiver`, for
     ceil(sample_rate * simulation_time) steps.  Returns [(directional records, sample_rate,
     (0, cutoff))] -- the bandpass_band list waveguide::postprocess takes -- or None when stopped early.
@@ -335,9 +375,15 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     the band's energy and the Fourier sums of the squared output at the modulation frequencies (Engine.set_modulation); the return
     value is then (bands, ((energy float64[K, nz, ny, nx], sums complex128[K, M, nz, ny, nx]), captures)), which wayverb_amd.modulation
     turns into the modulation transfer function and the speech transmission index.  One domain only, and not together with another
-    plan."""
+    plan.
+    `waterfall`: dict(freqs_hz=[...], plane=<z in metres> or box=..., every=, bin_ms= | n_bins= and bin_captures=)
+    (waterfall_plan_arguments) -- the engine Fourier-transforms every node of that plane or box at those frequencies per time bin, on the
+    device (Engine.set_waterfall); the return value is then (bands, (complex128[n_bins, K, nz, ny, nx], captures)), which
+    wayverb_amd.waterfall turns into the short-time spectrum, the cumulative spectral decay and the decay time of single modes.  One
+    domain only, and not together with another plan."""
     asked = {keyword: plan for keyword, plan in (("snapshots", snapshots), ("spectrum", spectrum), ("decay", decay), ("intensity", intensity),
-                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation)) if plan is not None}
+                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation), ("waterfall", waterfall))
+             if plan is not None}
     for keyword in SLABS_REFUSALS:
         if keyword in asked and slabs > 1:
             raise ValueError("%s on one domain only (slabs=1)" % SLABS_REFUSALS[keyword])
@@ -502,7 +548,7 @@ def canonical_multiband(vm, source, receiver, environment, bands, cutoff, usable
 def impulse_response(vertices, triangles, surface_absorptions, source, receiver, cutoff=200.0, usable_portion=0.6,
                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
                      pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None, decay=None,
-                     intensity=None, arrival=None, lateral=None, modulation=None):
+                     intensity=None, arrival=None, lateral=None, modulation=None, waterfall=None):
     """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio.
     `snapshots`: a function mesh -> keyword arguments of Engine.set_snapshots (the mesh's size is not known before it is built),
     or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member.
@@ -511,14 +557,16 @@ def impulse_response(vertices, triangles, surface_absorptions, source, receiver,
     `intensity`: canonical's `intensity` dict; the fourth member is then (bins [4, n_bins, nz, ny, nx], captures).
     `arrival`: canonical's `arrival` dict; the fourth member is then (dict(onset, peak, peak_capture, pre, moment, bins), captures).
     `lateral`: canonical's `lateral` dict; the fourth member is then (dict(onset, pre, velocity, bins), captures).
-    `modulation`: canonical's `modulation` dict; the fourth member is then ((energy, sums), captures)."""
+    `modulation`: canonical's `modulation` dict; the fourth member is then ((energy, sums), captures).
+    `waterfall`: canonical's `waterfall` dict; the fourth member is then (bins complex128[n_bins, K, nz, ny, nx], captures)."""
     environment = environment or Environment()
     vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
     if spectrum is not None and snapshots is not None:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
     plans = {keyword: plan for keyword, plan in (("snapshots", snapshots), ("spectrum", spectrum), ("decay", decay), ("intensity", intensity),
-                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation)) if plan is not None}
+                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation), ("waterfall", waterfall))
+             if plan is not None}
     for keyword in ("snapshots", "spectrum"):
         if callable(plans.get(keyword)):
             plans[keyword] = plans[keyword](vm.mesh)
