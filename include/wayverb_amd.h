@@ -909,6 +909,84 @@ int wv_set_waterfall(wv_engine* e, const wv_waterfall_plan* plan, const double* 
 int wv_waterfall_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
 int wv_fetch_waterfall(wv_engine* e, double* dst /* [n_bins][n_freqs][nz][ny][nx][2]: complex128 */, uint64_t* captures);
 
+/* ---- interaural maps: IACF / IACC at every seat, correlated on the device -------------------------- */
+/* ISO 3382-1 Annex B reads spatial impression from the inter-aural cross-correlation function IACF and its maximum IACC (early,
+ * late, whole).  It is the one family the plans above cannot give: every one of them is quadratic in ONE node's signal, and the IACF
+ * is the normalised cross-correlation of TWO points an ear-distance apart at lags of up to +-1 ms.  An interaural plan captures, for
+ * every node taken by a box, the field at two nodes -- the node plus ear_a and the node plus ear_b, offsets in MESH NODES, not box
+ * strides -- and accumulates energies and lagged products per time bin counted from the node's own onset, ON THE DEVICE.  The
+ * waveguide carries the band below the crossover, where the head is small against the wavelength and the inter-aural difference is
+ * a time difference between two points in space: two mesh nodes 0.15 - 0.2 m apart are the head-less ("spaced omni") form of the
+ * measurement.  It is not a dummy head.  ear_a == ear_b is legal and gives the per-seat autocorrelation (periodicity, echo and
+ * flutter detection).  Ears inside a wall read what the field holds there.
+ *
+ * Definition.  Per taken node n and committed capture c = 0, 1, ... since the plan was set, in order; L = max_lag; thr = the node's
+ * entry of threshold_map, or `threshold`; the state starts as onset = NONE (all bits set), everything else +0.0:
+ *
+ *     a = (float)field[n + ear_a];  b = (float)field[n + ear_b]             the capture: two floats
+ *     mag = fmaxf(fabsf(a), fabsf(b))
+ *     if (onset == NONE && mag >= thr) onset = c                            unfiltered; a NaN is no onset
+ *     xa = cascade(a), xb = cascade(b)                                      doubles; per section, as wv_set_decay_bands:
+ *                                                                              out = x * b0 + z1;  z1 = (x * b1 - a1 * out) + z2;
+ *                                                                              z2 = x * b2 - a2 * out;  x = out
+ *                                                                           one state per ear, the sections shared;
+ *                                                                           n_sections == 0: xa = (double)a, xb = (double)b
+ *     if (onset == NONE) { pre[0] = pre[0] + xa * xa;  pre[1] = pre[1] + xb * xb; }
+ *     else { w = the largest w with edges[w] <= c - onset;
+ *            Ea[w] = Ea[w] + xa * xa;  Eb[w] = Eb[w] + xb * xb;  C[w][L] = C[w][L] + xa * xb;
+ *            for l = 1 .. L:  C[w][L + l] = C[w][L + l] + ha[l] * xb;       a earlier, b later by l captures: tau = +l
+ *                             C[w][L - l] = C[w][L - l] + hb[l] * xa; }     each product rounded, then the sum
+ *     for l = L .. 2: ha[l] = ha[l - 1], hb[l] = hb[l - 1];  ha[1] = xa, hb[1] = xb        EVERY capture, before the onset too
+ *
+ * A product goes to the bin of the LATER sample: this differs from ISO's "window on the left ear's time" by at most L captures at a
+ * bin edge.  wayverb_amd/interaural.py (interaural_fold) evaluates these lines in NumPy, the float lines on float32 and the rest on
+ * float64, and reproduces onset, pre and all bins BIT FOR BIT; iacf / iacc / iacc_lag there turn the bins into C / sqrt(Ea Eb).
+ *
+ *   - n_bins 1 .. 4; edges[0] == 0 and strictly increasing; threshold >= 0 and finite; max_lag 0 .. 16; every ear component in
+ *     -8 .. 8; n_sections 0 .. 4 (`sections`: that many wv_biquad, finite; ignored when 0); strides and period >= 1; the box inside
+ *     the mesh; every taken node plus either ear inside the mesh ("wv_set_interaural: an ear leaves the mesh"); fewer than 2^31 nodes
+ *     per plane; every entry of the map >= 0 and finite: WV_E_INVALID_ARGUMENT, looked at in this order
+ *   - everything (the stage of 16 captures, 128 bytes per node; the sums; the lag history and the filter states) is allocated when
+ *     the plan is set: with no room the call answers WV_E_HIP ("wv_set_interaural: no room for the stage and the state") and leaves
+ *     the engine and any earlier plan untouched.  A new plan replaces the old one and forgets its state; a NULL plan stops, forgets
+ *     and frees (as does wv_destroy)
+ *   - one domain only: a slab of a chain answers WV_E_STATE (the snapshot plan's reason)
+ *   - EXCLUSIVE with every other plan: all decide where passes end; setting one while another is active answers WV_E_STATE
+ *   - after a run that stopped on a flag at step f (an overflow, or keep_going cleared) the state holds exactly the captures of steps
+ *     <= f, and wv_interaural_count says how many
+ *   - wv_step / wv_swap capture nothing; plan steps they pass are passed, as for snapshots
+ *   - capture numbers are 32 bits: the capture after number 2^32 - 2 is refused (WV_E_STATE)
+ *   - wv_checkpoint copies the state and the count aside (the copy is allocated by the first checkpoint taken under a plan);
+ *     wv_rollback puts both back, and the re-run reproduces them bitwise.  A plan set AFTER the checkpoint makes wv_rollback answer
+ *     WV_E_STATE, as a changed source does
+ *   - wv_fetch_interaural may be called any time outside wv_run; it folds what is staged and leaves the plan running
+ *   - with no plan nothing is launched, allocated or waited for; with one the fields, receiver rows and flags are bit-identical to
+ *     a run without
+ *
+ * wv_interaural_count: as wv_spectrum_count.  wv_fetch_interaural: onset uint32 [nz][ny][nx] (0xFFFFFFFF: none yet), pre float64
+ * [2][nz][ny][nx], bins float64 [n_bins][2 L + 3][nz][ny][nx] in the order Ea, Eb, C[-L] .. C[+L]; any destination may be NULL;
+ * *captures (may be NULL) = how many captures they hold.  The struct is 112 bytes: nine int32 from 0, first_step at 40, period at
+ * 48, ear_a at 56, ear_b at 68, max_lag at 80, n_bins at 84, threshold at 88, edges at 92, n_sections at 108. */
+typedef struct wv_interaural_plan {
+    int32_t x0, y0, z0;     /* first node of the box */
+    int32_t nx, ny, nz;     /* nodes TAKEN along each axis (after decimation) */
+    int32_t sx, sy, sz;     /* take every s-th node along the axis, >= 1 */
+    uint64_t first_step;    /* captures at first_step + j * period, j = 0, 1, ... */
+    uint64_t period;        /* >= 1 */
+    int32_t ear_a[3];       /* x, y, z offset in mesh nodes from a taken node to its first ear, each -8 .. 8 */
+    int32_t ear_b[3];       /* ... to its second ear */
+    uint32_t max_lag;       /* L, 0 .. 16: lags -L .. L, counted in captures */
+    uint32_t n_bins;        /* 1 .. 4 */
+    float threshold;        /* >= 0, finite; used where threshold_map is NULL */
+    uint32_t edges[4];      /* first relative capture of bin w; edges[0] == 0, strictly increasing over n_bins entries */
+    uint32_t n_sections;    /* 0 .. 4 biquad sections of the ONE band-pass cascade both ears share; 0: no filter */
+} wv_interaural_plan;
+int wv_set_interaural(wv_engine* e, const wv_interaural_plan* plan, const wv_biquad* sections /* [n_sections], NULL when 0 */,
+                      const float* threshold_map /* [nz][ny][nx] or NULL; every entry >= 0, finite */);
+int wv_interaural_count(wv_engine* e, uint64_t* captures, uint64_t* last_step);
+int wv_fetch_interaural(wv_engine* e, uint32_t* onset, double* pre /* [2][nz][ny][nx] */,
+                        double* bins /* [n_bins][2 max_lag + 3][nz][ny][nx] */, uint64_t* captures);
+
 /* ---- timing hooks (bench.py) ------------------------------------------------------------------ */
 /* Mean duration in ms of the dominant (pressure update) kernel over the launches since the
  * last call, measured with HIP events on the engine's own stream; 0 launches -> 0. */
@@ -954,7 +1032,8 @@ int wv_kernel_time_detail(wv_engine* e, double* mean_ms, uint64_t* launches, uin
  *                            the intensity plan's five since wv_set_lateral
  *   WV_QUERY_MODULATION_CAPTURES, WV_QUERY_MODULATION_FOLDS, WV_QUERY_MODULATION_NS   the decay plan's three since wv_set_modulation
  *   WV_QUERY_ARRIVAL_BANDS_CAPTURES, WV_QUERY_ARRIVAL_BANDS_FOLDS, WV_QUERY_ARRIVAL_BANDS_NS   the decay plan's three since wv_set_arrival_bands
- *   WV_QUERY_WATERFALL_CAPTURES, WV_QUERY_WATERFALL_FOLDS, WV_QUERY_WATERFALL_NS   the decay plan's three since wv_set_waterfall */
+ *   WV_QUERY_WATERFALL_CAPTURES, WV_QUERY_WATERFALL_FOLDS, WV_QUERY_WATERFALL_NS   the decay plan's three since wv_set_waterfall
+ *   WV_QUERY_INTERAURAL_CAPTURES, WV_QUERY_INTERAURAL_FOLDS, WV_QUERY_INTERAURAL_NS   the decay plan's three since wv_set_interaural */
 enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_QUERY_MARCH_LIVE_PERMILLE = 3,
        WV_QUERY_SWEEP_LIVE_PERMILLE = 4, WV_QUERY_MARCH_ROUNDS = 5, WV_QUERY_HALO_WAIT_NS = 6, WV_QUERY_HALO_WAITS = 7,
        WV_QUERY_HALO_EXCHANGES = 8, WV_QUERY_HALO_BYTES_SENT = 9, WV_QUERY_EARLY_PASSES = 10,
@@ -980,7 +1059,8 @@ enum { WV_QUERY_PASSES = 0, WV_QUERY_XWALL_ENTRIES = 1, WV_QUERY_FIELDS = 2, WV_
        WV_QUERY_LATERAL_GATHER_NS = 43, WV_QUERY_LATERAL_GATHERS = 44,
        WV_QUERY_MODULATION_CAPTURES = 45, WV_QUERY_MODULATION_FOLDS = 46, WV_QUERY_MODULATION_NS = 47,
        WV_QUERY_ARRIVAL_BANDS_CAPTURES = 48, WV_QUERY_ARRIVAL_BANDS_FOLDS = 49, WV_QUERY_ARRIVAL_BANDS_NS = 50,
-       WV_QUERY_WATERFALL_CAPTURES = 51, WV_QUERY_WATERFALL_FOLDS = 52, WV_QUERY_WATERFALL_NS = 53 };
+       WV_QUERY_WATERFALL_CAPTURES = 51, WV_QUERY_WATERFALL_FOLDS = 52, WV_QUERY_WATERFALL_NS = 53,
+       WV_QUERY_INTERAURAL_CAPTURES = 54, WV_QUERY_INTERAURAL_FOLDS = 55, WV_QUERY_INTERAURAL_NS = 56 };
 int wv_query(wv_engine* e, int what, uint64_t* value);
 /* hipStreamSynchronize on every engine stream. */
 int wv_synchronize(wv_engine* e);

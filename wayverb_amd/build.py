@@ -13,8 +13,8 @@ LIB = os.path.join(HERE, "libwayverb_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["engine.hip", "mesh_setup.hip", "node_inside.hip", "boundary_surfaces.hip", "scene_mesh.hip", "compensation_signal.hip", "comm.cpp", "box_mesh.cpp", "filter_design.cpp", "postprocess.cpp", "biquad.cpp"]
-HEADERS = ["device_common.hip.h", "stream_kernels.hip.h", "boundary_kernels.hip.h", "pair_kernels.hip.h", "plane_kernels.hip.h", "snapshot_kernels.hip.h", "spectrum_kernels.hip.h", "decay_kernels.hip.h", "decay_bands_kernels.hip.h", "intensity_kernels.hip.h", "arrival_kernels.hip.h", "lateral_kernels.hip.h", "modulation_kernels.hip.h", "arrival_bands_kernels.hip.h", "waterfall_kernels.hip.h", "fold_parts.hip.h", "receiver_kernels.hip.h", "triple_kernels.hip.h", "compressed_kernels.hip.h", "comm.h", "engine_base.h", "march_plan.h", "snapshot_plan.h", "spectrum_plan.h", "decay_plan.h", "intensity_plan.h", "arrival_plan.h", "lateral_plan.h", "modulation_plan.h", "arrival_bands_plan.h", "waterfall_plan.h", "capture_stage.h", "engine.hip.h",
-           "engine_setup.hip.h", "engine_single.hip.h", "engine_pair.hip.h", "engine_triple.hip.h", "engine_batch.hip.h", "engine_io.hip.h", "engine_snapshot.hip.h", "engine_staged.hip.h", "engine_spectrum.hip.h", "engine_decay.hip.h", "engine_intensity.hip.h", "engine_arrival.hip.h", "engine_lateral.hip.h", "engine_modulation.hip.h", "engine_arrival_bands.hip.h", "engine_waterfall.hip.h", "engine_directional.hip.h", "engine_slab.hip.h",
+HEADERS = ["device_common.hip.h", "stream_kernels.hip.h", "boundary_kernels.hip.h", "pair_kernels.hip.h", "plane_kernels.hip.h", "snapshot_kernels.hip.h", "spectrum_kernels.hip.h", "decay_kernels.hip.h", "decay_bands_kernels.hip.h", "intensity_kernels.hip.h", "arrival_kernels.hip.h", "lateral_kernels.hip.h", "modulation_kernels.hip.h", "arrival_bands_kernels.hip.h", "waterfall_kernels.hip.h", "interaural_kernels.hip.h", "fold_parts.hip.h", "receiver_kernels.hip.h", "triple_kernels.hip.h", "compressed_kernels.hip.h", "comm.h", "engine_base.h", "march_plan.h", "snapshot_plan.h", "spectrum_plan.h", "decay_plan.h", "intensity_plan.h", "arrival_plan.h", "lateral_plan.h", "modulation_plan.h", "arrival_bands_plan.h", "waterfall_plan.h", "interaural_plan.h", "capture_stage.h", "engine.hip.h",
+           "engine_setup.hip.h", "engine_single.hip.h", "engine_pair.hip.h", "engine_triple.hip.h", "engine_batch.hip.h", "engine_io.hip.h", "engine_snapshot.hip.h", "engine_staged.hip.h", "engine_spectrum.hip.h", "engine_decay.hip.h", "engine_intensity.hip.h", "engine_arrival.hip.h", "engine_lateral.hip.h", "engine_modulation.hip.h", "engine_arrival_bands.hip.h", "engine_waterfall.hip.h", "engine_interaural.hip.h", "engine_directional.hip.h", "engine_slab.hip.h",
            os.path.join("..", "..", "include", "wayverb_amd.h")]
 
 # -ffp-contract=off: results must not depend on where the compiler chooses to fuse a*b+c

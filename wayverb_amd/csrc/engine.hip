@@ -23,6 +23,7 @@
 #include "engine_modulation.hip.h"
 #include "engine_arrival_bands.hip.h"
 #include "engine_waterfall.hip.h"
+#include "engine_interaural.hip.h"
 #include "engine_directional.hip.h"
 #include "engine_slab.hip.h"
 
@@ -332,6 +333,18 @@ int wv_waterfall_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
 int wv_fetch_waterfall(wv_engine* e, double* dst, uint64_t* captures) {
     WV_NEED(e);
     return e->fetch_waterfall(dst, captures);
+}
+int wv_set_interaural(wv_engine* e, const wv_interaural_plan* plan, const wv_biquad* sections, const float* threshold_map) {
+    WV_NEED(e);
+    return e->set_interaural(plan, sections, threshold_map);
+}
+int wv_interaural_count(wv_engine* e, uint64_t* captures, uint64_t* last_step) {
+    WV_NEED(e);
+    return e->interaural_count(captures, last_step);
+}
+int wv_fetch_interaural(wv_engine* e, uint32_t* onset, double* pre, double* bins, uint64_t* captures) {
+    WV_NEED(e);
+    return e->fetch_interaural(onset, pre, bins, captures);
 }
 int wv_step(wv_engine* e, int32_t* flag) {
     WV_NEED(e);

@@ -18,12 +18,12 @@
 //   engine_snapshot.hip.h  field snapshots taken on the device while a run goes on (wv_set_snapshots): plan, ring, capture, copy stream, held log
 //   snapshot_plan.h      (host only, no HIP) which steps are snapshot steps, how far a batch may go, box validity, output shape; what every
 //                        plan's setter checks: the box of a plan, the four shared refusals, frequencies, coefficients, physical constants
-//   engine_staged.hip.h  the life cycle the eight accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release;
+//   engine_staged.hip.h  the life cycle the nine accumulating plans below share: set, capture, commit, fold, checkpoint, rollback, release;
 //                        the host-written tables of a fold (bins, twiddles), the threshold map, the fetch of complex sums
 //   fold_parts.hip.h     the device pieces more than one fold kernel has and that leave its assembly alone: stage read, integrator step, onset rule
 //   engine_spectrum.hip.h  field spectra accumulated on the device while a run goes on (wv_set_spectrum): plan, stage, fold, fetch
 //   spectrum_plan.h      (host only, no HIP) free slots of the stage, when a fold is due, which captures survive a stop, sizes
-//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the eight accumulating plans
+//   capture_stage.h      (host only, no HIP) the bookkeeping of a stage of captures, shared by the nine accumulating plans
 //   engine_decay.hip.h   time-binned field energy accumulated on the device while a run goes on (wv_set_decay): plan, stage, fold, fetch
 //   decay_plan.h         (host only, no HIP) the bin of a capture, sizes, the fold's traffic model
 //   decay_bands_kernels.hip.h   the fold of a band-limited decay plan (wv_set_decay_bands): biquad cascades ahead of the square
@@ -45,6 +45,9 @@
 //   engine_waterfall.hip.h  per time bin, the Fourier sums of a box at K frequencies: short-time spectra and the cumulative spectral decay (wv_set_waterfall)
 //   waterfall_plan.h     (host only, no HIP) the cap on sums per node, sizes and places, the fold's traffic model
 //   waterfall_kernels.hip.h   its fold: spectrum_fold_kernel's chunked Fourier sum driven by decay_fold_kernel's held bin
+//   engine_interaural.hip.h  per node the energies and lagged products of the field at two nodes an ear-distance apart, binned from the node's own arrival: IACF / IACC (wv_set_interaural)
+//   interaural_plan.h    (host only, no HIP) what a plan is refused for and in which order, the lag class, sizes and places, the traffic model
+//   interaural_kernels.hip.h  its capture (ear_gather_kernel: the third kind beside the snapshot's and the intensity plan's) and its fold
 //   engine_directional.hip.h  receiver arrays: directional receivers recorded and integrated on the device (wv_set_directional_receivers)
 //   engine_slab.hip.h    z-slab chains: communicators, the in-process group (wv_comm_init_local / wv_run_group)
 // There is no CPU path: without a HIP device every entry point fails.
@@ -60,6 +63,7 @@
 #include "modulation_plan.h"
 #include "arrival_bands_plan.h"
 #include "waterfall_plan.h"
+#include "interaural_plan.h"
 #include "capture_stage.h"
 
 #include "boundary_kernels.hip.h"
@@ -76,6 +80,7 @@
 #include "modulation_kernels.hip.h"
 #include "arrival_bands_kernels.hip.h"
 #include "waterfall_kernels.hip.h"
+#include "interaural_kernels.hip.h"
 #include "receiver_kernels.hip.h"
 #include "triple_kernels.hip.h"
 
@@ -257,6 +262,11 @@ public:
     int waterfall_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(wf_, captures, last_step); }
     int fetch_waterfall(double* dst, uint64_t* captures) override;
     bool waterfall_active() const override { return wf_.active; }
+    // ---- engine_interaural.hip.h
+    int set_interaural(const wv_interaural_plan* plan, const wv_biquad* sections, const float* threshold_map) override;
+    int interaural_count(uint64_t* captures, uint64_t* last_step) override { return staged_count(ia_, captures, last_step); }
+    int fetch_interaural(uint32_t* onset, double* pre, double* bins, uint64_t* captures) override;
+    bool interaural_active() const override { return ia_.active; }
     // ---- engine_batch.hip.h
     int kernel_time(double* mean_ms, uint64_t* launches, uint64_t* steps) override;
     int synchronize() override;
@@ -464,8 +474,8 @@ private:
     void directional_release();
     int directional_enqueue(uint64_t batch);
     std::unique_ptr<wv::SlabComm> comm_;
-    // the eight plans that accumulate on the device (engine_staged.hip.h)
-    enum PlanKind { kSpectrumPlan, kDecayPlan, kIntensityPlan, kArrivalPlan, kLateralPlan, kModulationPlan, kArrivalBandsPlan, kWaterfallPlan, kPlanKinds };
+    // the nine plans that accumulate on the device (engine_staged.hip.h)
+    enum PlanKind { kSpectrumPlan, kDecayPlan, kIntensityPlan, kArrivalPlan, kLateralPlan, kModulationPlan, kArrivalBandsPlan, kWaterfallPlan, kInterauralPlan, kPlanKinds };
     static constexpr int kPlanBlocks = 2;  // device blocks of accumulated state a plan has at the most
     // wv_checkpoint / wv_rollback (engine_io.hip.h): device copies of the two live fields and the filter memories, and the
     // host-side position that goes with them
@@ -539,8 +549,8 @@ private:
     int snapshot_plan_batch();
     int snapshot_begin_run();
     void snapshot_rollback(uint64_t to_step);
-    // ---- engine_staged.hip.h: the eight plans that accumulate on the device -- spectrum, decay (plain and banded), intensity, arrival,
-    // lateral, modulation, banded arrival, waterfall -- have ONE life cycle: captures into a device-only stage on the compute stream, committed batch by batch, folded into the
+    // ---- engine_staged.hip.h: the nine plans that accumulate on the device -- spectrum, decay (plain and banded), intensity, arrival,
+    // lateral, modulation, banded arrival, waterfall, interaural -- have ONE life cycle: captures into a device-only stage on the compute stream, committed batch by batch, folded into the
     // plan's accumulated state in one launch when the stage has no slot left, on fetch and on checkpoint.  StagedPlan holds what they
     // share; a plan's own struct adds its wv_*_plan, its tables and what its fold kernel needs
     struct StagedPlan {
@@ -562,10 +572,12 @@ private:
         bool fold_wide = false;         // the fold takes two nodes per lane
         wv::SnapshotBox box;
         double spacing = 0;             // of the mesh (gradients only)
+        bool ears = false;              // a capture is ear_gather_kernel's two planes (the third kind: neither of the above)
+        int32_t ear_a[3] = {0, 0, 0}, ear_b[3] = {0, 0, 0};  // offsets in mesh nodes from a taken node to its ears (ears only)
         uint64_t generation = 0;        // bumped by every call of the setter (a checkpoint remembers which plan it saw)
         wv::CaptureStage st;            // staged steps, committed count, next plan step, the batch's end (capture_stage.h)
         uint64_t nodes = 0;             // B: nodes taken
-        float* stage = nullptr;         // [T][B], with gradients [T][4][B]: pressure, gx, gy, gz
+        float* stage = nullptr;         // [T][B], with gradients [T][4][B]: pressure, gx, gy, gz, with ears [T][2][B]: ear a, ear b
         unsigned char* block[kPlanBlocks] = {nullptr, nullptr};  // the accumulated state: what a checkpoint copies and a rollback restores
         size_t block_bytes[kPlanBlocks] = {0, 0};
         int n_blocks = 0;
@@ -712,14 +724,32 @@ private:
         }
     } wf_;
     int waterfall_enqueue(Waterfall& w, int b, int t, unsigned blocks);
+    // interaural maps (engine_interaural.hip.h): block 0 holds what a fetch returns (interaural_plan.h has the places): pre, bins, onset;
+    // block 1 what only the fold sees: the lag history of both ears and their filter states.  Edges, L and n_sections go to the kernel
+    // as arguments: there is no table to copy
+    struct Interaural : StagedPlan {
+        Interaural()
+            : StagedPlan(kInterauralPlan, "interaural", "wv_set_interaural", "its state has", "the interaural plan's sums",
+                         "the interaural plan's history and filter states", false, false, wv::kInterauralMaxCaptures) {
+            this->ears = true;
+        }
+        wv_interaural_plan plan{};
+        unsigned char* sums() const { return this->block[0]; }   // double pre[2][B], bins[n_bins][2 L + 3][B]; uint32 onset[B]
+        unsigned char* carry() const { return this->block[1]; }  // double history[2][L][B], z[2][n_sections][2][B]; null when L == 0 and n_sections == 0
+        double* coef = nullptr;         // [n_sections][5] on the device, or NULL: no filter
+        float* threshold_map = nullptr; // [B], or NULL: the plan's scalar for every node
+        void free_own();
+    } ia_;
+    int launch_ear_gather(const wv::SnapshotBox& box, const int32_t* ear_a, const int32_t* ear_b, float* dst);  // (engine_snapshot.hip.h, beside the other two)
+    int interaural_enqueue(Interaural& d, int b, int t, unsigned blocks);
     // ---- engine_staged.hip.h: one copy of each step of the life cycle
-    StagedPlan* const staged_[kPlanKinds] = {&spec_, &decay_, &inten_, &arr_, &lat_, &mod_, &arrb_, &wf_};  // by PlanKind
-    StagedPlan* staged() const {  // the active one of the eight, or null: they exclude each other (and a snapshot plan)
+    StagedPlan* const staged_[kPlanKinds] = {&spec_, &decay_, &inten_, &arr_, &lat_, &mod_, &arrb_, &wf_, &ia_};  // by PlanKind
+    StagedPlan* staged() const {  // the active one of the nine, or null: they exclude each other (and a snapshot plan)
         for (StagedPlan* p : staged_)
             if (p->active) return p;
         return nullptr;
     }
-    enum PlanRow { kSnapshotRow, kSpectrumRow, kBandedDecayRow, kPlainDecayRow, kIntensityRow, kArrivalRow, kLateralRow, kModulationRow, kArrivalBandsRow, kWaterfallRow };
+    enum PlanRow { kSnapshotRow, kSpectrumRow, kBandedDecayRow, kPlainDecayRow, kIntensityRow, kArrivalRow, kLateralRow, kModulationRow, kArrivalBandsRow, kWaterfallRow, kInterauralRow };
     int plan_refused(const std::string& setter, PlanRow self);
     template <typename Plan>
     static void plan_release(Plan& p);

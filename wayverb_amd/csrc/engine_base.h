@@ -128,6 +128,10 @@ struct wv_engine {
     virtual int waterfall_count(uint64_t* captures, uint64_t* last_step) = 0;
     virtual int fetch_waterfall(double* dst, uint64_t* captures) = 0;
     virtual bool waterfall_active() const = 0;
+    virtual int set_interaural(const wv_interaural_plan* plan, const wv_biquad* sections, const float* threshold_map) = 0;
+    virtual int interaural_count(uint64_t* captures, uint64_t* last_step) = 0;
+    virtual int fetch_interaural(uint32_t* onset, double* pre, double* bins, uint64_t* captures) = 0;
+    virtual bool interaural_active() const = 0;
     virtual int step(int32_t* flag) = 0;
     virtual int swap() = 0;
     virtual int set_source(int kind, uint64_t node, const double* signal, uint64_t n) = 0;

@@ -478,6 +478,8 @@ int Engine<Real>::query(int what, uint64_t* value) {
         case WV_QUERY_ARRIVAL_BANDS_FOLDS: *value = arrb_.folds; return WV_OK;
         case WV_QUERY_WATERFALL_CAPTURES: *value = wf_.st.captures(); return WV_OK;
         case WV_QUERY_WATERFALL_FOLDS: *value = wf_.folds; return WV_OK;
+        case WV_QUERY_INTERAURAL_CAPTURES: *value = ia_.st.captures(); return WV_OK;
+        case WV_QUERY_INTERAURAL_FOLDS: *value = ia_.folds; return WV_OK;
         // (a plan's kernel times, once its timed folds and captures have run: engine_staged.hip.h)
         case WV_QUERY_SPECTRUM_NS: return staged_time_query(spec_, PlanTime::folds_ns, value);
         case WV_QUERY_DECAY_NS: return staged_time_query(decay_, PlanTime::folds_ns, value);
@@ -491,6 +493,7 @@ int Engine<Real>::query(int what, uint64_t* value) {
         case WV_QUERY_MODULATION_NS: return staged_time_query(mod_, PlanTime::folds_ns, value);
         case WV_QUERY_ARRIVAL_BANDS_NS: return staged_time_query(arrb_, PlanTime::folds_ns, value);
         case WV_QUERY_WATERFALL_NS: return staged_time_query(wf_, PlanTime::folds_ns, value);
+        case WV_QUERY_INTERAURAL_NS: return staged_time_query(ia_, PlanTime::folds_ns, value);
         default: return fail(WV_E_INVALID_ARGUMENT, "unknown query");
     }
 }

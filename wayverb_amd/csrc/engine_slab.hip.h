@@ -131,6 +131,9 @@ inline int group_run(wv_engine* const* engines, int32_t n, uint64_t n_steps, uin
     for (int k = 0; k < n; ++k)
         if (engines[k]->waterfall_active())
             return fail(WV_E_STATE, "wv_run_group accumulates no waterfall maps: an engine with a waterfall plan is stepped with wv_run (wv_set_waterfall(e, NULL, NULL) stops the plan)");
+    for (int k = 0; k < n; ++k)
+        if (engines[k]->interaural_active())
+            return fail(WV_E_STATE, "wv_run_group accumulates no interaural maps: an engine with an interaural plan is stepped with wv_run (wv_set_interaural(e, NULL, NULL, NULL) stops the plan)");
     // lockstep needs the slabs in the same state: the same field buffer in the same role after the same number of steps
     // (exchanges address the neighbour's buffer by index)
     for (int k = 1; k < n; ++k)

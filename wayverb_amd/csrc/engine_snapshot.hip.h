@@ -133,6 +133,29 @@ int Engine<Real>::launch_intensity_gather(const wv::SnapshotBox& box, double spa
     return WV_OK;
 }
 
+// ear_gather_kernel (interaural_kernels.hip.h) on the compute stream: per node of `box` the field at the node plus ear_a and at the node
+// plus ear_b, from the field `current` -> the two dense planes at `dst`.  The one launch site of that kernel (an interaural plan's
+// capture, engine_staged.hip.h: staged_capture); the setter has checked that both ears of every node lie on the mesh (interaural_plan.h).
+template <typename Real>
+int Engine<Real>::launch_ear_gather(const wv::SnapshotBox& box, const int32_t* ear_a, const int32_t* ear_b, float* dst) {
+    wv::EarGatherArgs<Real> a{};
+    a.field = field_[cur_];
+    a.dst = dst;
+    a.pitch = pitch_;
+    a.nodes = (int64_t)wv::snapshot_elements(box);
+    a.ear_a = ((int64_t)ear_a[2] * ny_ + ear_a[1]) * (int64_t)pitch_ + ear_a[0];
+    a.ear_b = ((int64_t)ear_b[2] * ny_ + ear_b[1]) * (int64_t)pitch_ + ear_b[0];
+    a.mesh_ny = ny_;
+    a.x0 = box.x0, a.y0 = box.y0, a.z0 = box.z0;
+    a.nx = box.nx, a.ny = box.ny, a.nz = box.nz;
+    a.sx = box.sx, a.sy = box.sy, a.sz = box.sz;
+    const uint64_t items = (uint64_t)box.nx * (uint64_t)box.ny;
+    const dim3 grid((unsigned)std::min<uint64_t>((items + 255) / 256, 1u << 14), (unsigned)std::min(box.nz, 1024));
+    hipLaunchKernelGGL((wv::ear_gather_kernel<Real>), grid, dim3(256), 0, stream_, a);
+    WV_HIP(hipGetLastError());
+    return WV_OK;
+}
+
 // The capture of `step`, which the field `current` holds once everything enqueued on the compute stream so far has run.
 template <typename Real>
 int Engine<Real>::snapshot_capture(uint64_t step) {

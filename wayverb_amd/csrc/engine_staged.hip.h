@@ -1,6 +1,6 @@
-// engine_staged.hip.h -- the life cycle of the eight plans that accumulate on the device while wv_run keeps going: field spectra
+// engine_staged.hip.h -- the life cycle of the nine plans that accumulate on the device while wv_run keeps going: field spectra
 // (engine_spectrum.hip.h), energy decay maps plain and banded (engine_decay.hip.h), intensity maps (engine_intensity.hip.h),
-// arrival-aligned energy maps (engine_arrival.hip.h), lateral maps (engine_lateral.hip.h), modulation maps (engine_modulation.hip.h), band-limited arrival maps (engine_arrival_bands.hip.h) and waterfall maps (engine_waterfall.hip.h).  One copy of each step; what a plan's own
+// arrival-aligned energy maps (engine_arrival.hip.h), lateral maps (engine_lateral.hip.h), modulation maps (engine_modulation.hip.h), band-limited arrival maps (engine_arrival_bands.hip.h), waterfall maps (engine_waterfall.hip.h) and interaural maps (engine_interaural.hip.h).  One copy of each step; what a plan's own
 // file keeps is its setter's validation, sizes and first contents, the enqueue step of its fold and its fetch -- and
 // of those the pieces more than one plan has are here too: the host-written tables of a fold (HostTable: bins, twiddles), the threshold
 // map of the plans that find an onset, the fetch of complex sums.
@@ -8,8 +8,8 @@
 // Part of the engine behind the C ABI of include/wayverb_amd.h (engine.hip is the translation unit; see engine.hip.h for the class).
 //
 // Everything runs on the compute stream, in order:
-//   capture   snapshot_gather_kernel, or intensity_gather_kernel for a plan that integrates velocities (both launched in
-//             engine_snapshot.hip.h) -> the next free slot of the device-only stage, directly behind the pass that produced the step.
+//   capture   snapshot_gather_kernel, intensity_gather_kernel for a plan that integrates velocities, or ear_gather_kernel for the plan
+//             that reads two nodes per node taken (all three launched in engine_snapshot.hip.h) -> the next free slot of the device-only stage, directly behind the pass that produced the step.
 //             A plan step is the end of a pass exactly as a snapshot step is: engine_batch.hip.h cuts its batches and segments at
 //             whichever plan is active (they all exclude each other: plan_refused).
 //   commit    a batch's captures stay staged until commit_batch has said how many of its steps were good; those of later steps are
@@ -29,7 +29,8 @@
 namespace wv {
 
 static_assert(kDecayStage == kSpectrumStage && kIntensityStage == kSpectrumStage && kArrivalStage == kSpectrumStage && kLateralStage == kSpectrumStage &&
-                      kModulationStage == kSpectrumStage && kArrivalBandsStage == kSpectrumStage && kWaterfallStage == kSpectrumStage,
+                      kModulationStage == kSpectrumStage && kArrivalBandsStage == kSpectrumStage && kWaterfallStage == kSpectrumStage &&
+                      kInterauralStage == kSpectrumStage,
               "every plan stages its captures by spectrum_plan.h's rules (capture_stage.h)");
 
 // What every plan's setter, wv_set_snapshots included, refuses a plan for before it looks at it: a slab of a chain (it would have to cut
@@ -53,6 +54,7 @@ int Engine<Real>::plan_refused(const std::string& setter, PlanRow self) {
         {kModulationRow, mod_.active, "a modulation plan is active (wv_set_modulation(e, NULL, NULL, NULL, 0, 0) stops it); the plans exclude each other"},
         {kArrivalBandsRow, arrb_.active, "a banded arrival plan is active (wv_set_arrival_bands(e, NULL, NULL, NULL, 0, 0) stops it); the plans exclude each other"},
         {kWaterfallRow, wf_.active, "a waterfall plan is active (wv_set_waterfall(e, NULL, NULL) stops it); the plans exclude each other"},
+        {kInterauralRow, ia_.active, "an interaural plan is active (wv_set_interaural(e, NULL, NULL, NULL) stops it); the plans exclude each other"},
     };
     for (const auto& r : rows)
         if (r.active && r.row != self) return fail(WV_E_STATE, setter + ": " + r.sentence);
@@ -90,7 +92,8 @@ void Engine<Real>::staged_release(StagedPlan& p) {
         case kLateralPlan: plan_release(static_cast<Lateral&>(p)); break;
         case kModulationPlan: plan_release(static_cast<Modulation&>(p)); break;
         case kArrivalBandsPlan: plan_release(static_cast<ArrivalBands&>(p)); break;
-        default: plan_release(static_cast<Waterfall&>(p)); break;
+        case kWaterfallPlan: plan_release(static_cast<Waterfall&>(p)); break;
+        default: plan_release(static_cast<Interaural&>(p)); break;
     }
 }
 
@@ -257,6 +260,9 @@ int Engine<Real>::staged_capture(StagedPlan& p, uint64_t step) {
             WV_HIP(hipEventRecord(p.gather_done[slot], stream_));
             p.gather_timed[slot] = true;
         }
+    } else if (p.ears) {
+        const int rc = launch_ear_gather(p.box, p.ear_a, p.ear_b, p.stage + (uint64_t)slot * 2 * p.nodes);
+        if (rc) return rc;
     } else {
         const int rc = launch_snapshot_gather(p.box, p.gather_wide, p.stage + (uint64_t)slot * p.nodes);
         if (rc) return rc;
@@ -308,7 +314,8 @@ int Engine<Real>::staged_enqueue(StagedPlan& p, int b, int t, unsigned blocks) {
         case kLateralPlan: return lateral_enqueue(static_cast<Lateral&>(p), b, t, blocks);
         case kModulationPlan: return modulation_enqueue(static_cast<Modulation&>(p), b, t, blocks);
         case kArrivalBandsPlan: return arrival_bands_enqueue(static_cast<ArrivalBands&>(p), b, t, blocks);
-        default: return waterfall_enqueue(static_cast<Waterfall&>(p), b, t, blocks);
+        case kWaterfallPlan: return waterfall_enqueue(static_cast<Waterfall&>(p), b, t, blocks);
+        default: return interaural_enqueue(static_cast<Interaural&>(p), b, t, blocks);
     }
 }
 

@@ -46,6 +46,7 @@ EXPORTS = [
     "wv_set_modulation", "wv_modulation_count", "wv_fetch_modulation",
     "wv_set_arrival_bands", "wv_arrival_bands_count", "wv_fetch_arrival_bands",
     "wv_set_waterfall", "wv_waterfall_count", "wv_fetch_waterfall",
+    "wv_set_interaural", "wv_interaural_count", "wv_fetch_interaural",
 ]
 
 
@@ -134,10 +135,17 @@ class WvWaterfallPlan(C.Structure):
     _fields_ = _BOX_AND_CADENCE + [("n_freqs", C.c_uint32), ("n_bins", C.c_uint32), ("bin_captures", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class WvInterauralPlan(C.Structure):
+    """wv_interaural_plan (include/wayverb_amd.h): box, strides and cadence, the two ear offsets in mesh nodes, the largest lag, the
+    arrival plan's number of bins, threshold and edges (four of them), and the number of biquad sections both ears share."""
+    _fields_ = _BOX_AND_CADENCE + [("ear_a", C.c_int32 * 3), ("ear_b", C.c_int32 * 3), ("max_lag", C.c_uint32), ("n_bins", C.c_uint32),
+                                   ("threshold", C.c_float), ("edges", C.c_uint32 * 4), ("n_sections", C.c_uint32)]
+
+
 ARRIVAL_NONE = 0xFFFFFFFF   # onset / peak_capture of a node that has none yet
 
 # The capture plans as this layer remembers them (Engine.<name>_shape) and as the library counts them (wv_<name>_count) ...
-PLAN_NAMES = ("snapshot", "spectrum", "decay", "intensity", "arrival", "lateral", "modulation", "arrival_bands", "waterfall")
+PLAN_NAMES = ("snapshot", "spectrum", "decay", "intensity", "arrival", "lateral", "modulation", "arrival_bands", "interaural", "waterfall")
 # ... and their calls: wv_set_<key>(engine, plan, *what is listed first) and wv_fetch_<key>(engine, *what is listed second)
 _POINTER, _WORD, _RESULT = C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)
 _PLAN_CALLS = {
@@ -150,6 +158,8 @@ _PLAN_CALLS = {
     "lateral": (WvLateralPlan, [_POINTER], [_POINTER] * 4 + [_RESULT]),
     "modulation": (WvModulationPlan, [_POINTER, _POINTER, _WORD, _WORD], [_POINTER, _POINTER, _RESULT]),
     "arrival_bands": (WvArrivalBandsPlan, [_POINTER, _POINTER, _WORD, _WORD], [_POINTER] * 6 + [_RESULT]),
+    # (tests/test_waterfall_plan.py pins the waterfall plan as the last name and the last row: a later plan stands ahead of it)
+    "interaural": (WvInterauralPlan, [_POINTER, _POINTER], [_POINTER] * 3 + [_RESULT]),
     "waterfall": (WvWaterfallPlan, [_POINTER], [_POINTER, _RESULT]),
 }
 
@@ -465,7 +475,7 @@ class Engine:
     def _plan_state(self):
         """What this layer remembers of the capture plans: the shape a fetch returns, None while the plan is not set."""
         for name in PLAN_NAMES:
-            if not hasattr(type(self), name + "_shape"):   # (waterfall_shape: the class has its None)
+            if not hasattr(type(self), name + "_shape"):   # (waterfall_shape, interaural_shape: the class has their None)
                 setattr(self, name + "_shape", None)
         self.decay_banded = False
 
@@ -988,6 +998,54 @@ class Engine:
         out = np.zeros(tuple(self.waterfall_shape or (0, 0, 0, 0, 0)), dtype=np.complex128)   # (no plan: the library says so)
         return out, self._fetch(self.lib.wv_fetch_waterfall, out)
 
+    # ---- interaural maps accumulated on the device while wv_run goes on -------------------------------
+    # (a default of the class, as waterfall_shape is and for its reason)
+    interaural_shape = None
+
+    def set_interaural(self, edges, ear_a=(0, 0, 0), ear_b=(0, 0, 0), max_lag=0, threshold=0.0, sections=None, box="mesh", stride=1, first_step=0,
+                       period=1, threshold_map=None):
+        """wv_set_interaural.  `ear_a`, `ear_b`: offsets in MESH NODES (not box strides) from a taken node to its two ears, every
+        component -8 .. 8, both on the mesh for every node taken (interaural.ear_offsets makes them of an axis and a distance in
+        metres); equal ears give the autocorrelation form.  `max_lag`: L, 0 .. 16 captures (interaural.max_lag makes it of
+        milliseconds).  `edges` (4 at the most), `threshold`, `threshold_map`, `box`, `stride`, `first_step`, `period` as for
+        set_arrival.  `sections`: None, or float64[S][5], S <= 4 biquad sections of the ONE band-pass cascade both ears run through
+        (decay.butterworth_bandpass designs them, for the rate of the CAPTURED series).  Per node the engine keeps the onset (of the
+        louder ear, unfiltered), the two energies ahead of it and, in bins counted from the node's OWN onset, Ea, Eb and the lagged
+        products C[-L] .. C[+L] (tau = +l: ear a earlier, ear b later by l captures; a product goes to the bin of the LATER sample);
+        interaural.interaural_fold over snapshots of the two ear planes reproduces all of it bit for bit, and interaural.iacf / iacc /
+        iacc_lag turn the bins into ISO 3382-1 Annex B's figures in their head-less (spaced omni) form -- not a dummy head.  Excludes
+        every other plan.  set_interaural(None) stops and forgets.  Returns the shape of the bins, (n_bins, 2 L + 3, nz, ny, nx): Ea, Eb,
+        C[-L] .. C[+L]."""
+        if edges is None:
+            return self._stop_plan("interaural", self.lib.wv_set_interaural, None, None, None)
+        plan = WvInterauralPlan()
+        n_bins = self._fill_edges(plan, edges, 4, "set_interaural")
+        taken = self._fill_box(plan, box, stride, first_step, period)
+        for axis in range(3):
+            plan.ear_a[axis], plan.ear_b[axis] = int(ear_a[axis]), int(ear_b[axis])
+        plan.max_lag, plan.threshold = int(max_lag), float(threshold)
+        coefficients, pointer = None, None
+        if sections is not None:
+            coefficients = np.ascontiguousarray(sections, dtype=np.float64)
+            if coefficients.ndim != 2 or coefficients.shape[1] != 5:
+                raise ValueError("set_interaural: sections is float64[S][5], got shape %r" % (coefficients.shape,))
+            plan.n_sections, pointer = coefficients.shape[0], coefficients.ctypes.data_as(C.c_void_p)
+        threshold_map, map_pointer = self._threshold_map(threshold_map, taken, "set_interaural")
+        _check(self.lib.wv_set_interaural(self.h, C.byref(plan), pointer, map_pointer))
+        self.interaural_shape = (n_bins, 2 * int(max_lag) + 3, taken[2], taken[1], taken[0])
+        return self.interaural_shape
+
+    def interaural_count(self):
+        """wv_interaural_count: (captures of completed steps since the plan was set, the step of the last of them)."""
+        return self._count(self.lib.wv_interaural_count)
+
+    def fetch_interaural(self):
+        """wv_fetch_interaural: (dict(onset=uint32[nz, ny, nx], pre=float64[2, nz, ny, nx], bins=float64[n_bins, 2 L + 3, nz, ny, nx]),
+        captures in them).  ARRIVAL_NONE marks a node without an onset.  The plan keeps running."""
+        shape = tuple(self.interaural_shape or (0, 0, 0, 0, 0))   # (no plan: the library says so)
+        out = dict(onset=np.zeros(shape[2:], np.uint32), pre=np.zeros((2,) + shape[2:], np.float64), bins=np.zeros(shape, np.float64))
+        return out, self._fetch(self.lib.wv_fetch_interaural, *out.values())   # (in the order the library takes them)
+
     def step_count(self):
         s = C.c_uint64()
         _check(self.lib.wv_step_count(self.h, C.byref(s)))
@@ -1026,6 +1084,7 @@ class Engine:
     QUERY_MODULATION_CAPTURES, QUERY_MODULATION_FOLDS, QUERY_MODULATION_NS = 45, 46, 47
     QUERY_ARRIVAL_BANDS_CAPTURES, QUERY_ARRIVAL_BANDS_FOLDS, QUERY_ARRIVAL_BANDS_NS = 48, 49, 50
     QUERY_WATERFALL_CAPTURES, QUERY_WATERFALL_FOLDS, QUERY_WATERFALL_NS = 51, 52, 53
+    QUERY_INTERAURAL_CAPTURES, QUERY_INTERAURAL_FOLDS, QUERY_INTERAURAL_NS = 54, 55, 56
 
     def query(self, what):
         """wv_query: two-step passes taken / wall nodes on compact copies / fields allocated."""

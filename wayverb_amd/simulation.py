@@ -287,6 +287,66 @@ def waterfall_plan_arguments(waterfall, mesh, sample_rate):
                 first_step=int(waterfall.get("first_step", 0)), period=every)
 
 
+INTERAURAL_KEYS = ("threshold", "every", "edges_ms", "ear_axis", "ear_distance", "ears", "max_lag_ms", "band_hz", "threshold_map", "stride", "first_step")
+
+
+def interaural_plan_arguments(interaural, mesh, sample_rate):
+    """canonical's `interaural` dict -> keyword arguments of Engine.set_interaural: dict(plane=z in metres | box=((x0, y0, z0), extent),
+    stride=1, every=1, threshold=, threshold_map=None, edges_ms=(0, 80), ear_axis=(0, 1, 0) with ear_distance=0.17 (metres) | ears=((x, y,
+    z), (x, y, z)) in mesh nodes, max_lag_ms=1.0, band_hz=(lo, hi) | None, first_step=0).  `plane`: that whole horizontal plane (the ears
+    of its outermost seats must still lie on the mesh: the engine refuses a plan one of whose ears leaves it).  The bins begin at every
+    one of `edges_ms` milliseconds behind each node's onset, the first of which is 0 (with the default, bin 0 is IACC_E's 0 .. 80 ms, bin
+    1 IACC_L's, both together IACC_A's); `threshold` is the pressure magnitude at either ear that counts as the arrival of the direct
+    sound.  The ear distance is rounded to mesh nodes along the axis (interaural.ear_offsets): more than a quarter off the distance asked
+    for is warned about.  The lags reach max_lag_ms at the rate of the captured series, sample_rate / every (interaural.max_lag): more
+    than the engine's 16 captures are clipped to 16 with a warning -- a larger `every` reaches further.  `band_hz`: a 4th-order
+    Butterworth band-pass both ears run through, designed at the rate of the captured series (decay.butterworth_bandpass).
+    Checked in this order: the keys and `every`, edges_ms, the ears, max_lag_ms, band_hz, the plane."""
+    import warnings
+    from . import decay as D
+    from . import interaural as IA
+    every = _keys_and_cadence(interaural, "interaural", INTERAURAL_KEYS, required=("threshold",))
+    edges_ms = [float(m) for m in interaural.get("edges_ms", (0.0, 80.0))]
+    if not edges_ms or edges_ms[0] != 0.0 or len(edges_ms) > IA.MAX_BINS:
+        raise ValueError("interaural: edges_ms begins with 0 and has 4 entries at the most")
+    if interaural.get("ears") is not None:
+        if "ear_axis" in interaural or "ear_distance" in interaural:
+            raise ValueError("interaural: the ears are ears=((x, y, z), (x, y, z)) in mesh nodes, or ear_axis= and ear_distance= in metres")
+        ears = [[int(v) for v in ear] for ear in interaural["ears"]]
+        if len(ears) != 2 or any(len(ear) != 3 or any(abs(v) > IA.MAX_EAR for v in ear) for ear in ears):
+            raise ValueError("interaural: ears holds two offsets (x, y, z) in mesh nodes, every component -8 .. 8")
+        ear_a, ear_b = tuple(ears[0]), tuple(ears[1])
+    else:
+        distance = float(interaural.get("ear_distance", 0.17))
+        try:
+            ear_a, ear_b, rounded = IA.ear_offsets(mesh.spacing, interaural.get("ear_axis", (0.0, 1.0, 0.0)), distance)
+        except ValueError:
+            raise ValueError("interaural: ear_axis is a non-zero vector and ear_distance >= 0 metres")
+        if any(abs(v) > IA.MAX_EAR for v in ear_a + ear_b):
+            raise ValueError("interaural: ear_distance=%g m is more than 8 mesh nodes (spacing %g m) from the seat" % (distance, mesh.spacing))
+        if abs(rounded - distance) > 0.25 * distance:
+            warnings.warn("interaural: the ears are %g m apart on this mesh (spacing %g m), more than a quarter off the %g m asked for"
+                          % (rounded, mesh.spacing, distance))
+    lag_ms = float(interaural.get("max_lag_ms", 1.0))
+    if not (lag_ms >= 0.0 and math.isfinite(lag_ms)):
+        raise ValueError("interaural: max_lag_ms must be >= 0")
+    lag = IA.max_lag(sample_rate, every, lag_ms)
+    if lag > IA.MAX_LAG:
+        warnings.warn("interaural: max_lag_ms=%g needs %d captures at every=%d, the engine holds 16: the lags end at %.3g ms"
+                      % (lag_ms, lag, every, 16e3 * every / sample_rate))
+        lag = IA.MAX_LAG
+    sections = None
+    if interaural.get("band_hz") is not None:
+        band = tuple(float(v) for v in np.atleast_1d(interaural["band_hz"]))
+        if len(band) != 2 or not 0 < band[0] < band[1]:
+            raise ValueError("interaural: band_hz is (lo_hz, hi_hz) with 0 < lo < hi, or None")
+        sections = D.butterworth_bandpass(band[0], band[1], sample_rate / every)
+    box = _plane_or_box(interaural, "interaural", mesh, rimless=False)
+    return dict(edges=IA.edges_from_ms(edges_ms[1:], every, sample_rate), ear_a=ear_a, ear_b=ear_b, max_lag=lag, threshold=float(interaural["threshold"]),
+                sections=sections, threshold_map=interaural.get("threshold_map"), box=box, stride=interaural.get("stride", 1),
+                first_step=int(interaural.get("first_step", 0)), period=every)
+
+
 def _decay_plan(decay, mesh, sample_rate, environment, simulation_time):
     if decay.get("bands") is not None:
         from . import decay as D
@@ -314,23 +374,30 @@ PLANS = (
     ("modulation", lambda plan, mesh, sample_rate, *_: ("modulation", (), modulation_plan_arguments(plan, mesh, sample_rate))),
     ("waterfall", lambda plan, mesh, sample_rate, *_: ("waterfall", (), waterfall_plan_arguments(plan, mesh, sample_rate))),
 )
+# (the plans that came after tests/test_waterfall_front.py and tests/test_waterfall_plan.py pinned PLANS row by row, the waterfall plan last:
+# canonical and plan_call look in ALL_PLANS)
+ALL_PLANS = PLANS + (
+    ("interaural", lambda plan, mesh, sample_rate, *_: ("interaural", (), interaural_plan_arguments(plan, mesh, sample_rate))),
+)
 
 
 def plan_call(keyword, plan, mesh, sample_rate, environment, simulation_time):
     """What canonical does with the value of one plan keyword: (name, positional, keyword arguments) -- Engine.set_<name>(*positional,
     **keyword arguments) sets the plan, Engine.fetch_<name>() fetches it.  A banded arrival plan's bin edges are positional[0]."""
-    return dict(PLANS)[keyword](plan, mesh, sample_rate, environment, simulation_time)
+    return dict(ALL_PLANS)[keyword](plan, mesh, sample_rate, environment, simulation_time)
 
 
 # what the refusal of slabs > 1 calls each of them, in the order it looks
 SLABS_REFUSALS = {"modulation": "modulation maps are accumulated", "lateral": "lateral maps are accumulated", "arrival": "arrival maps are accumulated",
                   "intensity": "intensity bins are accumulated", "decay": "decay bins are accumulated", "snapshots": "snapshots are taken",
                   "spectrum": "a spectrum is accumulated", "waterfall": "waterfall sums are accumulated"}
+# (and of the plans behind the pinned ones, as ALL_PLANS)
+ALL_SLABS_REFUSALS = dict(SLABS_REFUSALS, interaural="interaural maps are accumulated")
 
 
 def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulation_time, precision="f64",
               device=-1, keep_going=lambda: True, slabs=1, devices=None, snapshots=None, spectrum=None, decay=None, intensity=None,
-              arrival=None, lateral=None, modulation=None, waterfall=None):
+              arrival=None, lateral=None, modulation=None, waterfall=None, interaural=None):
     """canonical (single band): hard source at `source`, directional receiver at `receiver`, for
     ceil(sample_rate * simulation_time) steps.  Returns [(directional records, sample_rate,
     (0, cutoff))] -- the bandpass_band list waveguide::postprocess takes -- or None when stopped early.
@@ -380,19 +447,26 @@ def canonical(vm, source, receiver, environment, cutoff, usable_portion, simulat
     (waterfall_plan_arguments) -- the engine Fourier-transforms every node of that plane or box at those frequencies per time bin, on the
     device (Engine.set_waterfall); the return value is then (bands, (complex128[n_bins, K, nz, ny, nx], captures)), which
     wayverb_amd.waterfall turns into the short-time spectrum, the cumulative spectral decay and the decay time of single modes.  One
-    domain only, and not together with another plan."""
+    domain only, and not together with another plan.
+    `interaural`: dict(plane=<z in metres> or box=..., every=, threshold=, edges_ms=(0, 80), ear_axis=(0, 1, 0), ear_distance=0.17 |
+    ears=((..), (..)), max_lag_ms=1.0, band_hz=(lo, hi) | None) (interaural_plan_arguments) -- for every node of that plane or box the
+    engine correlates the field at two nodes an ear-distance apart, on the device, in bins counted from the node's own onset
+    (Engine.set_interaural); the return value is then (bands, (dict(onset, pre, bins), captures)), which wayverb_amd.interaural turns into
+    IACF, IACC_E / IACC_L / IACC_A and the lag of the maximum: ISO 3382-1 Annex B in its head-less (spaced omni) form -- not a dummy
+    head.  One domain only, and not together with another plan."""
     asked = {keyword: plan for keyword, plan in (("snapshots", snapshots), ("spectrum", spectrum), ("decay", decay), ("intensity", intensity),
-                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation), ("waterfall", waterfall))
+                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation), ("waterfall", waterfall),
+                                                 ("interaural", interaural))
              if plan is not None}
-    for keyword in SLABS_REFUSALS:
+    for keyword in ALL_SLABS_REFUSALS:
         if keyword in asked and slabs > 1:
-            raise ValueError("%s on one domain only (slabs=1)" % SLABS_REFUSALS[keyword])
+            raise ValueError("%s on one domain only (slabs=1)" % ALL_SLABS_REFUSALS[keyword])
     if "spectrum" in asked and "snapshots" in asked:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
     mesh = vm.mesh
     sample_rate = compute_sample_rate(mesh.spacing, environment.speed_of_sound)
     # (name of the Engine's plan, positional and keyword arguments of its set_*), in PLANS' order
-    plans = [plan_call(keyword, asked[keyword], mesh, sample_rate, environment, simulation_time) for keyword, _ in PLANS if keyword in asked]
+    plans = [plan_call(keyword, asked[keyword], mesh, sample_rate, environment, simulation_time) for keyword, _ in ALL_PLANS if keyword in asked]
 
     def mesh_index(pt):
         idx = vm.compute_index(pt)
@@ -548,7 +622,7 @@ def canonical_multiband(vm, source, receiver, environment, bands, cutoff, usable
 def impulse_response(vertices, triangles, surface_absorptions, source, receiver, cutoff=200.0, usable_portion=0.6,
                      simulation_time=1.0, output_sample_rate=44100.0, environment=None, method=P.ATTENUATOR_NULL,
                      pointing=(0.0, 0.0, 1.0), shape=0.0, precision="f64", device=-1, snapshots=None, spectrum=None, decay=None,
-                     intensity=None, arrival=None, lateral=None, modulation=None, waterfall=None):
+                     intensity=None, arrival=None, lateral=None, modulation=None, waterfall=None, interaural=None):
     """The waveguide leg of combined::engine (engine.cpp:90-188) end to end: scene -> audio.
     `snapshots`: a function mesh -> keyword arguments of Engine.set_snapshots (the mesh's size is not known before it is built),
     or those arguments themselves; the return value then has the (snapshots, steps) pair as a fourth member.
@@ -558,14 +632,16 @@ def impulse_response(vertices, triangles, surface_absorptions, source, receiver,
     `arrival`: canonical's `arrival` dict; the fourth member is then (dict(onset, peak, peak_capture, pre, moment, bins), captures).
     `lateral`: canonical's `lateral` dict; the fourth member is then (dict(onset, pre, velocity, bins), captures).
     `modulation`: canonical's `modulation` dict; the fourth member is then ((energy, sums), captures).
-    `waterfall`: canonical's `waterfall` dict; the fourth member is then (bins complex128[n_bins, K, nz, ny, nx], captures)."""
+    `waterfall`: canonical's `waterfall` dict; the fourth member is then (bins complex128[n_bins, K, nz, ny, nx], captures).
+    `interaural`: canonical's `interaural` dict; the fourth member is then (dict(onset, pre, bins), captures)."""
     environment = environment or Environment()
     vm = compute_voxels_and_mesh(vertices, triangles, surface_absorptions, receiver,
                                  compute_sampling_frequency(cutoff, usable_portion), environment.speed_of_sound)
     if spectrum is not None and snapshots is not None:
         raise ValueError("a spectrum plan and a snapshot plan exclude each other")
     plans = {keyword: plan for keyword, plan in (("snapshots", snapshots), ("spectrum", spectrum), ("decay", decay), ("intensity", intensity),
-                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation), ("waterfall", waterfall))
+                                                 ("arrival", arrival), ("lateral", lateral), ("modulation", modulation), ("waterfall", waterfall),
+                                                 ("interaural", interaural))
              if plan is not None}
     for keyword in ("snapshots", "spectrum"):
         if callable(plans.get(keyword)):
