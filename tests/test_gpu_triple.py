@@ -71,7 +71,7 @@ def test_triple_path_ragged_meshes_match_oracle(oracle, dims, tag):
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_triple_path_x_facing_walls_on_their_compact_copies_or_not(oracle, dims, tag, xwall):
     """The wall nodes that face along x through a pass's three levels on compact copies of what they would gather from the fields
-    (boundary_xwall=1, the default: xwall3_node -- they also finish the node they face at t+2 and t+3, which the third level's list
+    (boundary_xwall=1, the default: xwall_node -- they also finish the node they face at t+2 and t+3, which the third level's list
     then leaves out), in two-step passes only (2) or nowhere (0): the same bits; batches that end in a two-step pass or a single step
     after the three-step ones hand the copies over and take them back."""
     dtype = np.float32 if tag == "f32" else np.float64
@@ -95,6 +95,49 @@ def test_triple_path_x_facing_walls_on_their_compact_copies_or_not(oracle, dims,
         assert got["previous"].tobytes() == want["previous"].tobytes()
         for a, b in zip(got["bd"], want["bd"]):
             assert a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("dims", [(24, 20, 18), (131, 9, 7)], ids=lambda d: "x".join(map(str, d)))
+@pytest.mark.parametrize("tag", ["f32", "f64"])
+def test_x_facing_walls_copies_pass_between_three_and_two_step_passes(oracle, dims, tag):
+    """One engine, several runs, no field write between them: the compact copies a three-step pass leaves (own value at t+2 and t+3,
+    faced node at t+3) are what a two-step pass starts from, and the reverse -- xwall_node's table of roles.  After every run the
+    receiver trace, both fields and all filter memories are the oracle's, run from scratch to the same step."""
+    dtype = np.float32 if tag == "f32" else np.float64
+    set_tuning(boundary_xwall=1, **ON)
+    # (steps, three-step passes, two-step passes, single steps) of each run: fields written by the caller go through two single sweeps
+    # first, so the first run ends on a three-step pass; then three + two; then three-step passes only; then three + one
+    runs = [(8, 2, 0, 2), (5, 1, 1, 0), (6, 2, 0, 0), (4, 1, 0, 1)]
+    total = sum(r[0] for r in runs)
+    case = _random_case(dims, seed=sum(dims), steps=total, reentrant=False)
+    ci, (nx, ny, nz) = case["mesh"].compute_index, dims
+    # on the nodes the entries finish themselves (the faced ones and the ones behind them), and the centre
+    case["recv"] = [ci(nx // 2, ny // 2, nz // 2)] + [ci(x, ny // 2, nz // 2 + 1) for x in (2, 3, nx - 4, nx - 3)]
+    eng = E.Engine(case["mesh"], precision=tag)
+    try:
+        prev, cur = case["init"]
+        eng.write_field(prev.astype(dtype), E.BUF_PREVIOUS)
+        eng.write_field(cur.astype(dtype), E.BUF_CURRENT)
+        eng.set_source(case["source_kind"], case["source_node"], case["signal"])
+        eng.set_receivers(case["recv"])
+        done, triples, pairs = 0, 0, 0
+        for steps, want_triples, want_pairs, want_singles in runs:
+            got_steps, flag = eng.run_steps(steps)
+            assert (got_steps, flag) == (steps, 0)
+            done += steps
+            t, p = eng.query(E.Engine.QUERY_TRIPLE_PASSES), eng.query(E.Engine.QUERY_PASSES)
+            assert (t - triples, p - pairs, steps - 3 * (t - triples) - 2 * (p - pairs)) == (want_triples, want_pairs, want_singles)
+            triples, pairs = t, p
+            assert eng.query(E.Engine.QUERY_XWALL_ENTRIES) > 0
+            want = run_oracle(oracle, dict(case, steps=done, signal=case["signal"][:done]), dtype, threads=4)
+            assert want["flag"] == 0 and want["steps"] == done
+            assert np.array_equal(eng.fetch_receivers(0, done).astype(dtype).view(np.uint8), want["trace"].view(np.uint8))
+            assert eng.read_field(E.BUF_CURRENT).tobytes() == want["current"].tobytes()
+            assert eng.read_field(E.BUF_PREVIOUS).tobytes() == want["previous"].tobytes()
+            for d, b in zip((1, 2, 3), want["bd"]):
+                assert eng.read_boundary_data(d).tobytes() == b.tobytes()
+    finally:
+        eng.close()
 
 
 @pytest.mark.parametrize("lanes", [8, 16])

@@ -232,139 +232,68 @@ __device__ __forceinline__ void boundary_node(const BoundaryArgs<Real>& a, const
 // The mesh is x-fastest, so a wall node at (1, y, z) owns a 128-byte line of every field it touches and uses 8-24
 // bytes of it; its in-wall neighbours (1, y+-1, z), (1, y, z+-1) each sit in a line of their own.  boundary_node's
 // gathers cost such a node 2.4 whole lines in the first launch of a two-step pass and 6 in the second (PMC, round 2),
-// where a node of a y- or z-facing wall moves little more than its algorithmic 168 B.  So in two-step passes the
-// 1-D entries that face along x (in the marched planes; the first xw_n positions of the entry list, engine_setup)
+// where a node of a y- or z-facing wall moves little more than its algorithmic 168 B.  So in two- and three-step passes
+// the 1-D entries that face along x (in the marched planes; the first xw_n positions of the entry list, engine_setup)
 // keep what they would gather in compact arrays indexed by entry position -- neighbours are then +-1 / +-8 positions
-// away in brick order -- and touch the fields for exactly what must cross between wall and march:
-//   level 1 (t-1, t -> t+1)  reads one line of the t+1 field: the faced node's value (the march's output) and the node
-//                            behind it; writes its own t+1 value into that line
-//   level 2 (t, t+1 -> t+2)  reads no field at all; writes its own and the faced node's t+2 values (one line)
-// xw_a / xw_b: the wall node's own value at the odd / even time level (t-1 then t+1 / t then t+2, updated in
-// place); xw_f: the faced node at the even level; xw_f1 / xw_g: the faced node and the node behind it at t+1, captured
-// by level 1 for level 2.  xw_nbr[k][pos], k = y-, y+, z-, z+: position of that in-wall neighbour if it is one of these
-// entries (bit 31: it faces the same way, so ITS faced node is the lateral neighbour of mine), else XW_FIELD: read the
-// field as boundary_node would.  Same arithmetic (boundary_value / faced_value), same results.
-constexpr uint32_t XW_FIELD = 0xFFFFFFFFu, XW_SAME_FACING = 0x80000000u;
-
-template <typename Real, int LEVEL>
-__device__ __forceinline__ void xwall_node(const BoundaryArgs<Real>& a, const double* coeffs, uint32_t pos_e, int& bad) {
-    const uint32_t idx = a.bnode[pos_e];
-    const uint32_t dirs = a.btype[pos_e];  // 1: inner node at x-1, 2: at x+1
-    const int x = (int)(idx % (uint32_t)a.pitch);
-    const uint32_t q = idx / (uint32_t)a.pitch;
-    const int y = (int)(q % (uint32_t)a.ny);
-    const int z = (int)(q / (uint32_t)a.ny);
-    const int64_t plane = (int64_t)a.pitch * a.ny;
-    const int64_t stride[3] = {1, a.pitch, plane};
-    const int pos[3] = {x, y, z};
-    const int lim[3] = {a.nx, a.ny, a.nz};
-    const int step = (dirs & 2u) ? 1 : -1;
-    const int64_t fn = (int64_t)idx + step;  // the faced node: in the grid (xwall_eligible_kernel)
-    const bool far_off = x + 2 * step < 0 || x + 2 * step >= a.nx;
-
-    // ---- loads -----------------------------------------------------------------------------------
-    uint32_t ref[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) ref[k] = a.xw_nbr[(size_t)k * a.xw_n + pos_e];
-    const Real* level = LEVEL == 1 ? a.xw_b : a.xw_a;  // wall values at the time level the neighbours are read at
-    Real nb[3][2];
-    bool off[3][2];
-    off[0][0] = x - 1 < 0;
-    off[0][1] = x + 1 >= a.nx;
-    nb[0][0] = nb[0][1] = LEVEL == 1 ? a.xw_f[pos_e] : a.xw_f1[pos_e];  // (only the inner side enters the sums)
-    bool any_field = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int ax = 1 + (k >> 1), s = k & 1;
-        const int c = pos[ax] + (s ? 1 : -1);
-        off[ax][s] = c < 0 || c >= lim[ax];
-        const bool mirrored = ref[k] != XW_FIELD;
-        nb[ax][s] = level[mirrored ? (ref[k] & ~XW_SAME_FACING) : pos_e];
-        any_field = any_field || !mirrored;
-    }
-    const Real prev = LEVEL == 1 ? a.xw_a[pos_e] : a.xw_b[pos_e];
-    double m[1][6];
-    const double* cf[1];
-    cf[0] = coeffs + (size_t)a.cidx[pos_e] * 14;  // (1-D entries: slot = position)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) m[0][j] = __builtin_nontemporal_load(a.fmem + (size_t)j * a.n_slots + pos_e);
-    // level 1: what level 2 will want of the t+1 field (a.next), both in this node's line
-    Real f1 = 0, far1 = 0;
-    // level 2: the faced node's update
-    Real fnb[3][2], fprev = 0;
-    bool any_lateral_field = false;
-    if (LEVEL == 1) {
-        f1 = a.next[fn];
-        far1 = a.next[fn + (far_off ? 0 : step)];
-        far1 = far_off ? Real(0) : far1;
-    } else {
-        const Real own1 = a.xw_a[pos_e], far = a.xw_g[pos_e];
-        fnb[0][0] = step > 0 ? own1 : far;
-        fnb[0][1] = step > 0 ? far : own1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ax = 1 + (k >> 1), s = k & 1;
-            const bool regular = ref[k] != XW_FIELD && (ref[k] & XW_SAME_FACING);
-            const Real v = a.xw_f1[regular ? (ref[k] & ~XW_SAME_FACING) : pos_e];
-            fnb[ax][s] = off[ax][s] ? Real(0) : v;  // (the faced node's y, z are this node's)
-            any_lateral_field = any_lateral_field || (!regular && !off[ax][s]);
-        }
-        fprev = a.xw_f[pos_e];
-    }
-    // the wall's rim, walls that meet other things than walls: those neighbours come from the fields
-    if (any_field) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ax = 1 + (k >> 1), s = k & 1;
-            if (ref[k] == XW_FIELD) nb[ax][s] = a.cur[(int64_t)idx + (off[ax][s] ? 0 : (s ? stride[ax] : -stride[ax]))];
-        }
-    }
-    if (LEVEL == 2 && any_lateral_field) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ax = 1 + (k >> 1), s = k & 1;
-            const bool regular = ref[k] != XW_FIELD && (ref[k] & XW_SAME_FACING);
-            if (!regular && !off[ax][s]) fnb[ax][s] = a.cur[fn + (s ? stride[ax] : -stride[ax])];
-        }
-    }
-
-    // ---- the node's new value, its filter's new memories; stores -----------------------------------------
-    const Real next = boundary_value<Real, 1>(a.courant, a.courant_sq, dirs, nb, off, prev, m, cf);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) __builtin_nontemporal_store(m[0][j], a.fmem + (size_t)j * a.n_slots + pos_e);
-    bad |= bad_bits(next);
-    a.next[idx] = next;
-    if (LEVEL == 1) {
-        a.xw_a[pos_e] = next;
-        a.xw_f1[pos_e] = f1;
-        a.xw_g[pos_e] = far1;
-    } else {
-        const Real s2 = faced_value<Real>(fnb, fprev);
-        bad |= bad_bits(s2);
-        a.next[fn] = s2;
-        a.xw_b[pos_e] = next;
-        a.xw_f[pos_e] = s2;
-    }
-}
-
-// The same walls in a THREE-step pass (engine_triple.hip.h): three levels on the compact copies, the generations rotating through the
-// arrays so that no lane overwrites what another lane of the same launch still reads.  With t the pass's `current`:
-//   own value    xw_a = t-1, xw_b = t   --L1-->  xw_o2 = t+1   --L2-->  xw_a = t+2   --L3-->  xw_b = t+3        (the roles the next pass starts from)
-//   faced node   xw_f = t                --L1-->  xw_f1 = t+1 (captured from the march's t+1 field, with xw_g = the node behind it)
-//                                        --L2-->  xw_f2 = t+2 (computed here, as in a two-step pass)   --L3-->  xw_f = t+3 (computed here)
-//   level 1 (t-1, t -> t+1)    reads one line of the t+1 field (the march's shell values), writes its own t+1 into it
-//   level 2 (t, t+1 -> t+2)    reads no field; writes its own and the faced node's t+2 (one line)
+// away in brick order -- and touch the fields for exactly what must cross between wall and march.  DEPTH = the steps of
+// the pass (2 or 3), LEVEL = 1..DEPTH, t = the pass's `current`:
+//   level 1 (t-1, t -> t+1)    reads one line of the t+1 field: the faced node's value (the march's output, its shell values) and the node
+//                              behind it; writes its own t+1 value into that line
+//   level 2 (t, t+1 -> t+2)    reads no field at all; writes its own and the faced node's t+2 values (one line)
 //   level 3 (t+1, t+2 -> t+3)  reads no field; writes its own, the faced node's AND the t+3 of the node behind that one (one line) -- none
 //                              of these nodes is on the third level's list, where each node two columns from an x-facing wall cost six lines
 //                              (1.56 GB per launch of that list at 1024^3 for 0.3 GB of values)
+// The arrays, in a TWO-step pass: xw_a / xw_b: the wall node's own value at the odd / even time level (t-1 then t+1 / t then t+2, updated in
+// place: a lane overwrites only its own slot, which no other lane reads at that level); xw_f: the faced node at the even level; xw_f1 / xw_g:
+// the faced node and the node behind it at t+1, captured by level 1 for level 2.
+// In a THREE-step pass (engine_triple.hip.h) the generations rotate through the arrays, so that no lane overwrites what another lane of the
+// same launch still reads:
+//   own value    xw_a = t-1, xw_b = t   --L1-->  xw_o2 = t+1   --L2-->  xw_a = t+2   --L3-->  xw_b = t+3        (the roles the next pass starts from)
+//   faced node   xw_f = t                --L1-->  xw_f1 = t+1 (captured from the march's t+1 field, with xw_g = the node behind it)
+//                                        --L2-->  xw_f2 = t+2 (computed here, as in a two-step pass)   --L3-->  xw_f = t+3 (computed here)
+// Either pass starts from (xw_a, xw_b, xw_f) = (t-1, t, t) and leaves them one pass on -- (t+1, t+2, t+2) or (t+2, t+3, t+3) --: the
+// two kinds of pass follow each other on the same copies.  xw_roles below is the one place that says which array is what at which level.
 // The node behind the faced one (xw_gok: a plain node whose six neighbours are plain, the one behind it neither a boundary node nor finished
-// by one -- its t+2 is the march's or the second level's list's, final before level 2 runs): level 2 captures its t+2 and that of the node
-// behind it from their line of the t+2 field (xw_g2 / xw_h2); level 3 gives it its update from the faced node's fresh t+2 (xw_f2), xw_h2,
-// the lateral neighbours' xw_g2 and its own t+1 (xw_g).  Where xw_gok is 0 level 3 reads that node from the t+2 field as before and the
-// list keeps it.
-// a.prev / a.cur / a.next are the fields at the levels boundary_node would read and write; rim entries fall back to them as in xwall_node.
-template <typename Real, int LEVEL>
-__device__ __forceinline__ void xwall3_node(const BoundaryArgs<Real>& a, const double* coeffs, uint32_t pos_e, int& bad) {
+// by one -- its t+2 is the march's or the second level's list's, final before level 2 runs): level 2 of a three-step pass captures its t+2
+// and that of the node behind it from their line of the t+2 field (xw_g2 / xw_h2); level 3 gives it its update from the faced node's fresh
+// t+2 (xw_f2), xw_h2, the lateral neighbours' xw_g2 and its own t+1 (xw_g).  Where xw_gok is 0 level 3 reads that node from the t+2 field as
+// before and the list keeps it.
+// xw_nbr[k][pos], k = y-, y+, z-, z+: position of that in-wall neighbour if it is one of these entries (bit 31: it faces the same way, so
+// ITS faced node is the lateral neighbour of mine), else XW_FIELD: read the field as boundary_node would -- a.prev / a.cur / a.next are the
+// fields at the levels boundary_node would read and write, and rim entries fall back to them.  Same arithmetic (boundary_value /
+// faced_value), same results.
+constexpr uint32_t XW_FIELD = 0xFFFFFFFFu, XW_SAME_FACING = 0x80000000u;
+
+// Which array plays which role at which level (null: not at this level).
+template <typename Real>
+struct XwRoles {
+    using Array = Real* BoundaryArgs<Real>::*;
+    Array own_nb;    // the wall node's own value at the level the neighbours are read at
+    Array own_prev;  // ... one level back: this node's own old value
+    Array own_out;   // ... written
+    Array f_nb;      // the faced node at the neighbours' level: the wall node's inner neighbour
+    Array f_prev;    // ... one level back: the faced node's own old value
+    Array f_out;     // ... written (level 1 writes none: it captures xw_f1, xw_g from a.next)
+    Array behind;    // the node behind the faced one at the neighbours' level (3 / L3: where xw_gok, else from a.cur; 0 off the grid)
+};
+template <typename Real, int DEPTH, int LEVEL>
+constexpr XwRoles<Real> xw_roles() {
+    static_assert((DEPTH == 2 || DEPTH == 3) && LEVEL >= 1 && LEVEL <= DEPTH, "no such level of a pass on compact copies");
+    using A = BoundaryArgs<Real>;
+    constexpr XwRoles<Real> table[2][3] = {
+        //             own_nb     own_prev   own_out    f_nb       f_prev     f_out      behind
+        {/* 2 / L1 */ {&A::xw_b,  &A::xw_a,  &A::xw_a,  &A::xw_f,  nullptr,   nullptr,   nullptr},
+         /* 2 / L2 */ {&A::xw_a,  &A::xw_b,  &A::xw_b,  &A::xw_f1, &A::xw_f,  &A::xw_f,  &A::xw_g},
+         {}},
+        {/* 3 / L1 */ {&A::xw_b,  &A::xw_a,  &A::xw_o2, &A::xw_f,  nullptr,   nullptr,   nullptr},
+         /* 3 / L2 */ {&A::xw_o2, &A::xw_b,  &A::xw_a,  &A::xw_f1, &A::xw_f,  &A::xw_f2, &A::xw_g},  // (and captures xw_g2, xw_h2 from a.next)
+         /* 3 / L3 */ {&A::xw_a,  &A::xw_o2, &A::xw_b,  &A::xw_f2, &A::xw_f1, &A::xw_f,  &A::xw_g2}}};  // (and updates the node behind)
+    return table[DEPTH - 2][LEVEL - 1];
+}
+
+template <typename Real, int DEPTH, int LEVEL>
+__device__ __forceinline__ void xwall_node(const BoundaryArgs<Real>& a, const double* coeffs, uint32_t pos_e, int& bad) {
+    constexpr XwRoles<Real> role = xw_roles<Real, DEPTH, LEVEL>();
     const uint32_t idx = a.bnode[pos_e];
     const uint32_t dirs = a.btype[pos_e];  // 1: inner node at x-1, 2: at x+1
     const int x = (int)(idx % (uint32_t)a.pitch);
@@ -378,21 +307,20 @@ __device__ __forceinline__ void xwall3_node(const BoundaryArgs<Real>& a, const d
     const int step = (dirs & 2u) ? 1 : -1;
     const int64_t fn = (int64_t)idx + step;  // the faced node: in the grid (xwall_eligible_kernel)
     const bool far_off = x + 2 * step < 0 || x + 2 * step >= a.nx;
-    // which array holds what at this level
-    const Real* const own_nb = LEVEL == 1 ? a.xw_b : (LEVEL == 2 ? a.xw_o2 : a.xw_a);    // wall values at the level the neighbours are read at
-    const Real* const own_prev = LEVEL == 1 ? a.xw_a : (LEVEL == 2 ? a.xw_b : a.xw_o2);  // ... one level back: this node's own old value
-    Real* const own_out = LEVEL == 1 ? a.xw_o2 : (LEVEL == 2 ? a.xw_a : a.xw_b);
-    const Real* const f_nb = LEVEL == 1 ? a.xw_f : (LEVEL == 2 ? a.xw_f1 : a.xw_f2);     // the faced node at the neighbours' level
+    const Real* const own_nb = a.*role.own_nb;
+    const Real* const own_prev = a.*role.own_prev;
+    Real* const own_out = a.*role.own_out;
+    const Real* const f_nb = a.*role.f_nb;
     const int64_t gn = fn + (far_off ? 0 : step);  // the node behind the faced one (the faced one itself if that is off the grid)
     const bool h_off = far_off || x + 3 * step < 0 || x + 3 * step >= a.nx;
-    const bool gok = LEVEL != 1 && a.xw_gok[pos_e] != 0;
+    const bool gok = DEPTH == 3 && LEVEL != 1 && a.xw_gok[pos_e] != 0;
 
     // ---- loads -----------------------------------------------------------------------------------
     uint32_t ref[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) ref[k] = a.xw_nbr[(size_t)k * a.xw_n + pos_e];
-    Real g2c = 0, h2c = 0;  // level 2: t+2 of that node and of the one behind it (a.next: nobody writes them in this launch where gok)
-    if (LEVEL == 2) {
+    Real g2c = 0, h2c = 0;  // 3 / L2: t+2 of that node and of the one behind it (a.next: nobody writes them in this launch where gok)
+    if (DEPTH == 3 && LEVEL == 2) {
         g2c = a.next[gn];
         h2c = a.next[gn + (h_off ? 0 : step)];
     }
@@ -422,14 +350,14 @@ __device__ __forceinline__ void xwall3_node(const BoundaryArgs<Real>& a, const d
     // levels 2, 3: the faced node's update from the level the neighbours are read at
     Real fnb[3][2], fprev = 0;
     bool any_lateral_field = false;
-    if (LEVEL == 1) {
+    if constexpr (LEVEL == 1) {
         f1 = a.next[fn];
         far1 = a.next[fn + (far_off ? 0 : step)];
         far1 = far_off ? Real(0) : far1;
     } else {
         const Real own_at = own_nb[pos_e];  // this node's own value at the neighbours' level
         // (level 3: from level 2's capture where there is one -- no field line --, else from the t+2 field)
-        Real far = LEVEL == 2 ? a.xw_g[pos_e] : *(gok ? a.xw_g2 + pos_e : a.cur + gn);
+        Real far = LEVEL == 2 ? (a.*role.behind)[pos_e] : *(gok ? a.*role.behind + pos_e : a.cur + gn);
         far = (LEVEL == 3 && far_off) ? Real(0) : far;
         fnb[0][0] = step > 0 ? own_at : far;
         fnb[0][1] = step > 0 ? far : own_at;
@@ -441,7 +369,7 @@ __device__ __forceinline__ void xwall3_node(const BoundaryArgs<Real>& a, const d
             fnb[ax][s] = off[ax][s] ? Real(0) : v;  // (the faced node's y, z are this node's)
             any_lateral_field = any_lateral_field || (!regular && !off[ax][s]);
         }
-        fprev = LEVEL == 2 ? a.xw_f[pos_e] : a.xw_f1[pos_e];
+        fprev = (a.*role.f_prev)[pos_e];
     }
     // level 3: the node behind the faced one, from copies alone where its lateral neighbours are such nodes of neighbouring entries
     Real gnb[3][2], gprev = 0;
@@ -493,18 +421,18 @@ __device__ __forceinline__ void xwall3_node(const BoundaryArgs<Real>& a, const d
     bad |= bad_bits(next);
     a.next[idx] = next;
     own_out[pos_e] = next;
-    if (LEVEL == 1) {
+    if constexpr (LEVEL == 1) {
         a.xw_f1[pos_e] = f1;
         a.xw_g[pos_e] = far1;
     } else {
         const Real sf = faced_value<Real>(fnb, fprev);
         bad |= bad_bits(sf);
         a.next[fn] = sf;
-        (LEVEL == 2 ? a.xw_f2 : a.xw_f)[pos_e] = sf;
-        if (LEVEL == 2) {
+        (a.*role.f_out)[pos_e] = sf;
+        if (DEPTH == 3 && LEVEL == 2) {
             a.xw_g2[pos_e] = g2c;
             a.xw_h2[pos_e] = h_off ? Real(0) : h2c;
-        } else {
+        } else if (LEVEL == 3) {
             const Real sg = faced_value<Real>(gnb, gprev);
             if (gok) {
                 bad |= bad_bits(sg);
@@ -541,9 +469,14 @@ __device__ __forceinline__ void pre_post_body(const PrePostArgs<Real>& a, uint32
 // (BoundaryArgs::fix_z0 / fix_z1).
 // (`block` of `blocks`: this workgroup's place among the boundary workgroups of the launch -- all of it for boundary_kernel, the
 // tail of the grid for plane_step_kernel.)
-// XW3: 0, or the level (1, 2, 3) of a three-step pass whose x-facing walls work on their compact copies (xwall3_node)
-template <typename Real, bool LDSC, bool FIX, int XW3 = 0>
+// XWD, XWL: the depth (2, 3) and level (1..XWD) of a pass whose x-facing walls work on their compact copies (xwall_node) where a.xw_n says
+// so -- or XWD = 0: none, or a TWO-step pass's, which shares its instantiations with the launches without copies and tells them apart by
+// a.xw_n at run time; its level is then what FIX says (the host picks FIX = false for level 1 and FIX = true for level 2: launch_boundary).
+template <typename Real, bool LDSC, bool FIX, int XWD = 0, int XWL = 0>
 __device__ __forceinline__ void boundary_body(const BoundaryArgs<Real>& a, const PrePostArgs<Real>& next, uint32_t block, uint32_t blocks) {
+    constexpr int DEPTH = XWD ? XWD : 2, LEVEL = XWD ? XWL : (FIX ? 2 : 1);
+    static_assert(XWD ? (XWD == 2 || XWD == 3) && XWL >= 1 && XWL <= XWD : XWL == 0, "no such level of a pass on compact copies");
+    static_assert(LEVEL != 2 || FIX, "level 2 on compact copies finishes the nodes its entries face");
     __shared__ double s_coeffs[LDSC ? kMaxLdsCoefficientSets * 14 : 1];
     if (LDSC) {
         for (uint32_t w = threadIdx.x; w < a.n_coeffs * 14u; w += 256) s_coeffs[w] = a.coeffs[w];
@@ -553,15 +486,9 @@ __device__ __forceinline__ void boundary_body(const BoundaryArgs<Real>& a, const
     const uint32_t t = block * blockDim.x + threadIdx.x;
     int bad = 0;
     if (a.xw_n) {
-        // two-step pass: the first xw_n entries (x-facing walls) by their compact copies, whole workgroups of them
-        // first; then everything else as ever (FIX = this is the pass's second launch = level 2)
+        // the first xw_n entries (x-facing walls) by their compact copies, whole workgroups of them first; then everything else as ever
         if (t < a.xw_pad) {
-            if (t < a.xw_n) {
-                if (XW3)
-                    xwall3_node<Real, XW3 ? XW3 : 1>(a, coeffs, t, bad);
-                else
-                    xwall_node<Real, FIX ? 2 : 1>(a, coeffs, t, bad);
-            }
+            if (t < a.xw_n) xwall_node<Real, DEPTH, LEVEL>(a, coeffs, t, bad);
         } else if (a.order) {
             if (t - a.xw_pad < a.n_order) boundary_entry<Real, FIX>(a, coeffs, a.order[t - a.xw_pad], bad);
         } else {
@@ -576,6 +503,7 @@ __device__ __forceinline__ void boundary_body(const BoundaryArgs<Real>& a, const
     if (next.fused && block == blocks - 1) pre_post_body<Real>(next, threadIdx.x, 256);
 }
 
+// XW3: 0, or the level (1, 2, 3) of a three-step pass on compact copies (a two-step pass's levels: XW3 = 0, see boundary_body)
 template <typename Real, bool LDSC, bool FIX = false, int XW3 = 0>
 __global__ void __launch_bounds__(256) boundary_kernel(const BoundaryArgs<Real> a, const PrePostArgs<Real> next) {
     if (next.fused) {
@@ -587,20 +515,20 @@ __global__ void __launch_bounds__(256) boundary_kernel(const BoundaryArgs<Real> 
             return;
         }
         PrePostArgs<Real> none{};
-        boundary_body<Real, LDSC, FIX, XW3>(a, none, blockIdx.x - 1, gridDim.x - 1);
+        boundary_body<Real, LDSC, FIX, XW3 ? 3 : 0, XW3>(a, none, blockIdx.x - 1, gridDim.x - 1);
         return;
     }
-    boundary_body<Real, LDSC, FIX, XW3>(a, next, blockIdx.x, gridDim.x);
+    boundary_body<Real, LDSC, FIX, XW3 ? 3 : 0, XW3>(a, next, blockIdx.x, gridDim.x);
 }
 
-// the inside nodes the x-facing walls' entries finish at the third level of a three-step pass (xwall3_node): a bit per stored node, for the
+// the inside nodes the x-facing walls' entries finish at the third level of a three-step pass (xwall_node): a bit per stored node, for the
 // third-level list to leave them out (triple_map_kernel)
 struct XwCoverArgs {
     const uint32_t* bnode;
     const uint8_t* btype;
     uint32_t* covered;  // bitmap over stored node indices
     uint32_t xw_n;
-    // the node behind the faced one: xwall3_node's xw_gok (see there) -- and covered too where that says yes
+    // the node behind the faced one: xwall_node's xw_gok (see there) -- and covered too where that says yes
     const uint8_t* pair_map;
     uint8_t* gok;
     int nx, ny, nz, pitch, cls_pitch;

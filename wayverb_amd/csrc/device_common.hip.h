@@ -144,12 +144,12 @@ struct BoundaryArgs {
     // Its cache lines are the ones the entry touches anyway (boundary_kernel<.., FIX = true>; pair_kernels.hip.h,
     // pair_map_kernel).
     int fix_z0, fix_z1;
-    // Two-step passes, x-facing walls on compact copies (boundary_kernels.hip.h, xwall_node): the first xw_n entries;
+    // Two- and three-step passes, x-facing walls on compact copies (boundary_kernels.hip.h, xwall_node and its table of roles): the first xw_n entries;
     // xw_pad = xw_n rounded up to whole workgroups; 0 = every entry gathers from the fields.
     uint32_t xw_n, xw_pad;
     const uint32_t* xw_nbr;                  // [4][xw_n]
     Real *xw_a, *xw_b, *xw_f, *xw_f1, *xw_g;  // [xw_n] each
-    // ... and in three-step passes (xwall3_node): two more generations, the wall node's own value at a third time level and the faced
+    // ... and in three-step passes (xwall_node<Real, 3, LEVEL>): two more generations, the wall node's own value at a third time level and the faced
     // node at t+2
     Real *xw_o2, *xw_f2;
     // ... and for the node BEHIND the faced one, which such an entry finishes at the third level too where xw_gok says it may (a plain

@@ -119,16 +119,30 @@ public:
     // (`planes`: how many owned planes next to each neighbour -- 1: the face planes, 2: the faces and the planes next to them)
     int launch_faces(Real* prev, const Real* cur, int* flag, Real* out, int planes = 1);
     wv::BoundaryArgs<Real> boundary_args(Real* prev, const Real* cur, int* flag) const;
-    // (z0 = z1 = -1: the boundary nodes of a slab's face planes)
-    // (z0 = z1 = -2: of the two planes next to each neighbour; `levels`: a two-step pass's launch over the bulk of the mesh,
-    // in which the x-facing walls go by position on their compact copies)
     struct BoundaryLaunch {
         wv::BoundaryArgs<Real> args;
         unsigned blocks = 0;
         bool lds = false;
     };
-    int launch_boundary(Real* prev, const Real* cur, int* flag, int z0, int z1, const wv::PrePostArgs<Real>* next = nullptr, Real* out = nullptr, bool fix_inner = false,
-                        bool levels = false, BoundaryLaunch* plan_only = nullptr, int xw3 = 0);
+    // What a boundary launch covers and does, by name.
+    struct BoundaryPlanes {
+        enum Which { range, faces, faces_and_next } which = range;  // [z0, z1) | a slab's face planes | ... and the planes next to them
+        int z0 = 0, z1 = 0;
+        static BoundaryPlanes of(int z0, int z1) { return {range, z0, z1}; }
+        static BoundaryPlanes next_to_neighbours(int planes) { return {planes == 2 ? faces_and_next : faces, 0, 0}; }
+    };
+    struct XwallUse {  // the x-facing walls by position on their compact copies, in a pass's launch over the bulk of the mesh
+        int depth = 0, level = 0;  // none, or the steps of the pass (2, 3) and the level (1..depth) of this launch
+    };
+    struct BoundarySpec {
+        BoundaryPlanes planes;
+        Real* out = nullptr;                          // passes: the new values go to another field instead of replacing `prev`
+        const wv::PrePostArgs<Real>* ride = nullptr;  // source / receiver work that rides in the launch
+        bool fix_inner = false;                       // 1-D entries also finish the inside node they face
+        XwallUse copies;
+        BoundaryLaunch* plan_only = nullptr;          // hand the launch's arguments and grid back instead of launching
+    };
+    int launch_boundary(Real* prev, const Real* cur, int* flag, const BoundarySpec& spec);
     wv::PrePostArgs<Real> pre_post_args(Real* cur, int slot, bool with_pre_post, uint64_t signal_pos, bool source_live) const;
     int enqueue_step(int slot, bool with_pre_post, uint64_t signal_pos, bool source_live, int fuse_next = 0);
     // one-launch steps (plane_kernels.hip.h, whole_step_kernel): may this engine take them (synchronises once per source / receiver
@@ -286,8 +300,7 @@ private:
     void launch_pre_post(Real* field, int slot, uint64_t signal_pos, bool source_live, bool clear_flag, int* flag2 = nullptr, bool with_pre_post = true);
     // who does the source / receiver work that goes with a boundary launch: nobody here, the launch's last workgroup, a launch behind it
     enum class IoRide { none, carried, behind };
-    int launch_boundary_with_io(int part, Real* prev, const Real* cur, int* flag, int z0, int z1, Real* out, bool fix_inner, bool levels, int xw3,
-                                const wv::PrePostArgs<Real>& io, IoRide ride);
+    int launch_boundary_with_io(int part, Real* prev, const Real* cur, int* flag, const BoundarySpec& spec, const wv::PrePostArgs<Real>& io, IoRide ride);
     void carry_short_list(wv::PrePostArgs<Real>& io, const Real* cur, Real* out2, int* flag2) const;
     void refresh_xwall_copies(Real* prev, const Real* cur, int* flag);
     void rotate_after_pass();
@@ -396,7 +409,7 @@ private:
     bool pass_timed_ = false;
     unsigned part_timing_calls_ = 0;
     std::vector<uint32_t> plane_start_, plane_start_rest_;
-    // x-facing walls on compact copies in two-step passes (boundary_kernels.hip.h, xwall_node; engine_pair.hip.h)
+    // x-facing walls on compact copies in two- and three-step passes (boundary_kernels.hip.h, xwall_node; engine_pair.hip.h)
     uint32_t n_xw_ = 0;            // the first n_xw_ entries qualify (settled with the entry order in init)
     uint32_t* xw_nbr_ = nullptr;   // [4][n_xw_] in-wall neighbours by entry position
     Real* xw_val_ = nullptr;       // [9][n_xw_]: own value at the odd / even level, faced node, level 1's captures; a three-step pass's third generations and level 2's captures

@@ -148,7 +148,7 @@ bool Engine<Real>::io_nodes_unfaced() {
 }
 
 // true when, besides, none of them lies within two nodes of a boundary node along x: in a three-step pass the entries of x-facing walls
-// finish the node they face and the one behind it at t+3 (xwall3_node), in the launch the next step's source / receiver work would ride in
+// finish the node they face and the one behind it at t+3 (xwall_node<Real, 3, 3>), in the launch the next step's source / receiver work would ride in
 template <typename Real>
 bool Engine<Real>::io_nodes_clear_of_x_walls() {
     if (!io_nodes_unfaced()) return false;

@@ -509,8 +509,10 @@ int Engine<Real>::enqueue_pair_a(int slot, uint64_t signal_pos, bool source_live
     }
     // (not carried, early: the planes next to the faces have been to t+1 already; step t+1's source / receiver work is part B's)
     const bool inner = !carry && early;
-    if ((rc = launch_boundary_with_io(0, A, B, flag1, inner ? pair_s0_ : pair_plan_.z0, inner ? pair_s1_ : pair_plan_.z1, O1, false, true, 0, nx,
-                                      carry ? IoRide::carried : IoRide::none))) return rc;
+    if ((rc = launch_boundary_with_io(0, A, B, flag1,
+                                      {.planes = inner ? BoundaryPlanes::of(pair_s0_, pair_s1_) : BoundaryPlanes::of(pair_plan_.z0, pair_plan_.z1), .out = O1,
+                                       .copies = {.depth = 2, .level = 1}},
+                                      nx, carry ? IoRide::carried : IoRide::none))) return rc;
     pair_mid_done_ = carry;
     WV_HIP(hipGetLastError());
     return WV_OK;
@@ -548,13 +550,15 @@ void Engine<Real>::launch_pre_post(const wv::PrePostArgs<Real>& pp) {
 // launch's last workgroup does it (the caller has seen to it that the launch writes none of the nodes concerned) --, in a launch of its own
 // behind it, or none of this call's business (`io` is not read then).
 template <typename Real>
-int Engine<Real>::launch_boundary_with_io(int part, Real* prev, const Real* cur, int* flag, int z0, int z1, Real* out, bool fix_inner, bool levels,
-                                          int xw3, const wv::PrePostArgs<Real>& io, IoRide ride) {
+int Engine<Real>::launch_boundary_with_io(int part, Real* prev, const Real* cur, int* flag, const BoundarySpec& spec, const wv::PrePostArgs<Real>& io,
+                                          IoRide ride) {
     int rc;
     // (more than 64 columns never ride in a boundary launch: batch_can_fuse_ and io_nodes_unfaced() are false for them, engine_io.hip.h)
     assert(!(ride == IoRide::carried && io.n_recv > 64));
     const int token = begin_part_timing(part);
-    if ((rc = launch_boundary(prev, cur, flag, z0, z1, ride == IoRide::carried ? &io : nullptr, out, fix_inner, levels, nullptr, xw3))) return rc;
+    BoundarySpec with_io = spec;
+    with_io.ride = ride == IoRide::carried ? &io : nullptr;
+    if ((rc = launch_boundary(prev, cur, flag, with_io))) return rc;
     if (ride == IoRide::behind) launch_pre_post(io);
     return end_part_timing(part, token);
 }
@@ -659,8 +663,10 @@ int Engine<Real>::enqueue_pair_b(int slot, uint64_t signal_pos, bool source_live
     const bool carry = fuse_next && n_entries_ && io_nodes_unfaced();
     wv::PrePostArgs<Real> nx = pre_post_args(O2, slot + 2, true, signal_pos + 2, source_live);
     if (fuse_next == 2) nx.flag2 = flags_ + slot + 3;
-    if ((rc = launch_boundary_with_io(1, B, O1, flag2, pair_plan_.z0, pair_plan_.z1, O2, pair_inner_ok_ > 0, true, 0, nx,
-                                      carry ? IoRide::carried : IoRide::none))) return rc;  // (not carried: the next step's or pass's own launch)
+    if ((rc = launch_boundary_with_io(1, B, O1, flag2,
+                                      {.planes = BoundaryPlanes::of(pair_plan_.z0, pair_plan_.z1), .out = O2, .fix_inner = pair_inner_ok_ > 0,
+                                       .copies = {.depth = 2, .level = 2}},
+                                      nx, carry ? IoRide::carried : IoRide::none))) return rc;  // (not carried: the next step's or pass's own launch)
     if (carry) pre_post_done_ = true;
     pass_timed_ = false;
     WV_HIP(hipGetLastError());

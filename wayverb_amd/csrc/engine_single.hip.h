@@ -141,33 +141,49 @@ wv::BoundaryArgs<Real> Engine<Real>::boundary_args(Real* prev, const Real* cur, 
     return b;
 }
 
-// Boundary nodes of planes [z0, z1).  MUST be enqueued after the streaming launch that covers
-// those planes (the sweep writes boundary nodes' old values back, see X_STORE_ALL).
-// `out` (two-step passes): the new values go to another field instead of replacing `prev`.
+// The boundary kernel for a launch: [coefficients in LDS][1-D entries finish the nodes they face][level of a three-step pass on compact
+// copies, 0 = none].  The ten there are; a null entry is a combination no kernel exists for (boundary_body's static_assert: level 2
+// finishes the faced nodes).  A two-step pass's levels on copies share the kernels of the launches without copies, which take
+// `fix_inner` for the level -- so there level 1 goes without it and level 2 with it, or there is no kernel either.
 template <typename Real>
-int Engine<Real>::launch_boundary(Real* prev, const Real* cur, int* flag, int z0, int z1, const wv::PrePostArgs<Real>* next, Real* out, bool fix_inner,
-                                  bool levels, BoundaryLaunch* plan_only, int xw3) {
-    const bool faces = z0 == z1 && (z0 == -1 || z0 == -2);
+static auto boundary_kernel_for(bool lds, bool fix_inner, int depth, int level) -> void (*)(wv::BoundaryArgs<Real>, wv::PrePostArgs<Real>) {
+    using wv::boundary_kernel;
+    static constexpr void (*table[2][2][4])(wv::BoundaryArgs<Real>, wv::PrePostArgs<Real>) = {
+        {{boundary_kernel<Real, false, false, 0>, boundary_kernel<Real, false, false, 1>, nullptr, boundary_kernel<Real, false, false, 3>},
+         {boundary_kernel<Real, false, true, 0>, nullptr, boundary_kernel<Real, false, true, 2>, nullptr}},
+        {{boundary_kernel<Real, true, false, 0>, boundary_kernel<Real, true, false, 1>, nullptr, boundary_kernel<Real, true, false, 3>},
+         {boundary_kernel<Real, true, true, 0>, nullptr, boundary_kernel<Real, true, true, 2>, nullptr}}};
+    if (depth == 0) return table[lds][fix_inner][0];
+    if (depth == 2) return (level == 1 || level == 2) && fix_inner == (level == 2) ? table[lds][fix_inner][0] : nullptr;
+    return depth == 3 && level >= 1 && level <= 3 ? table[lds][fix_inner][level] : nullptr;
+}
+
+// Boundary nodes of the planes `spec` names.  MUST be enqueued after the streaming launch that covers
+// those planes (the sweep writes boundary nodes' old values back, see X_STORE_ALL).
+template <typename Real>
+int Engine<Real>::launch_boundary(Real* prev, const Real* cur, int* flag, const BoundarySpec& spec) {
+    const int z0 = spec.planes.z0, z1 = spec.planes.z1;
+    const bool faces = spec.planes.which != BoundaryPlanes::range;
     if (!n_entries_ || (z0 >= z1 && !faces)) return WV_OK;
     wv::BoundaryArgs<Real> b = boundary_args(prev, cur, flag);
-    if (out) b.next = out;
-    b.fix_z0 = z0;  // (fix_inner: second launch of a two-step pass over the marched planes)
+    if (spec.out) b.next = spec.out;
+    b.fix_z0 = z0;  // (fix_inner: second launch of a pass over the marched planes)
     b.fix_z1 = z1;
     wv::PrePostArgs<Real> nx{};  // fused == 0: nothing rides in this launch
-    if (next) {
-        nx = *next;
+    if (spec.ride) {
+        nx = *spec.ride;
         nx.fused = 1;
     }
-    // a two-step pass's launches over the bulk of the mesh: the x-facing walls by position, on their compact copies
+    // a pass's launches over the bulk of the mesh: the x-facing walls by position, on their compact copies (xwall_node)
     // (all of them lie in the planes of either such launch: xwall_eligible_kernel, engine_setup.hip.h)
-    // (xw3: level 1, 2 or 3 of a three-step pass that does the same -- xwall3_node)
-    const bool xw = out && xw_active_ && (levels || xw3);
+    const bool xw = spec.out && xw_active_ && spec.copies.depth;
     uint32_t n = n_entries_ - (xw ? n_xw_ : 0u);
     if (faces) {
         const int rc = build_plane_order();
         if (rc != WV_OK) return rc;
-        b.order = z0 == -1 ? face_order_ : early_order_;
-        b.n_order = n = z0 == -1 ? face_n_ : early_n_;
+        const bool only = spec.planes.which == BoundaryPlanes::faces;
+        b.order = only ? face_order_ : early_order_;
+        b.n_order = n = only ? face_n_ : early_n_;
         if (!n) return WV_OK;
     } else if (z0 > z_begin_ || z1 < z_end_) {
         const int rc = build_plane_order();
@@ -184,36 +200,16 @@ int Engine<Real>::launch_boundary(Real* prev, const Real* cur, int* flag, int z0
         n += b.xw_pad;
     }
     const bool lds = n_coeffs_ <= wv::kMaxLdsCoefficientSets && opt_.tuning.boundary_lds != 0;
-    if (plan_only) {
-        plan_only->args = b;
-        plan_only->blocks = (n + 255) / 256;
-        plan_only->lds = lds;
+    if (spec.plan_only) {
+        spec.plan_only->args = b;
+        spec.plan_only->blocks = (n + 255) / 256;
+        spec.plan_only->lds = lds;
         return WV_OK;
     }
+    const auto kernel = boundary_kernel_for<Real>(lds, spec.fix_inner, xw ? spec.copies.depth : 0, xw ? spec.copies.level : 0);
+    if (!kernel) return fail(WV_E_STATE, "launch_boundary: a pass's second level on compact copies without its entries finishing the nodes they face, or no such level");
     const dim3 grid((n + 255) / 256 + (nx.fused ? 1u : 0u)), block(256);  // (+ 1: the riding source / receiver work's own workgroup)
-    if (xw && xw3) {
-        if (lds && xw3 == 1)
-            hipLaunchKernelGGL((wv::boundary_kernel<Real, true, false, 1>), grid, block, 0, st(), b, nx);
-        else if (lds && xw3 == 2 && fix_inner)
-            hipLaunchKernelGGL((wv::boundary_kernel<Real, true, true, 2>), grid, block, 0, st(), b, nx);
-        else if (lds && xw3 == 3)
-            hipLaunchKernelGGL((wv::boundary_kernel<Real, true, false, 3>), grid, block, 0, st(), b, nx);
-        else if (xw3 == 1)
-            hipLaunchKernelGGL((wv::boundary_kernel<Real, false, false, 1>), grid, block, 0, st(), b, nx);
-        else if (xw3 == 2 && fix_inner)
-            hipLaunchKernelGGL((wv::boundary_kernel<Real, false, true, 2>), grid, block, 0, st(), b, nx);
-        else if (xw3 == 3)
-            hipLaunchKernelGGL((wv::boundary_kernel<Real, false, false, 3>), grid, block, 0, st(), b, nx);
-        else
-            return fail(WV_E_STATE, "launch_boundary: a three-step pass's second level on compact copies without its entries finishing the nodes they face");
-    } else if (lds && fix_inner)
-        hipLaunchKernelGGL((wv::boundary_kernel<Real, true, true>), grid, block, 0, st(), b, nx);
-    else if (lds)
-        hipLaunchKernelGGL((wv::boundary_kernel<Real, true, false>), grid, block, 0, st(), b, nx);
-    else if (fix_inner)
-        hipLaunchKernelGGL((wv::boundary_kernel<Real, false, true>), grid, block, 0, st(), b, nx);
-    else
-        hipLaunchKernelGGL((wv::boundary_kernel<Real, false, false>), grid, block, 0, st(), b, nx);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st(), b, nx);
     return WV_OK;
 }
 
@@ -230,7 +226,7 @@ int Engine<Real>::launch_faces(Real* prev, const Real* cur, int* flag, Real* out
         BoundaryLaunch bd;
         int rc = launch_stream(prev, cur, flag, z_begin_, zi0, false, out, zi1, z_end_, &sw);
         if (rc) return rc;
-        if ((rc = launch_boundary(prev, cur, flag, -planes, -planes, nullptr, out, false, false, &bd))) return rc;
+        if ((rc = launch_boundary(prev, cur, flag, {.planes = BoundaryPlanes::next_to_neighbours(planes), .out = out, .plan_only = &bd}))) return rc;
         if (sw.grid && bd.blocks) {
             const dim3 grid(sw.grid + bd.blocks), block(256);
             if (bd.lds)
@@ -242,7 +238,7 @@ int Engine<Real>::launch_faces(Real* prev, const Real* cur, int* flag, Real* out
     }
     int rc = launch_stream(prev, cur, flag, z_begin_, zi0, false, out, zi1, z_end_);
     if (rc) return rc;
-    return launch_boundary(prev, cur, flag, -planes, -planes, nullptr, out);
+    return launch_boundary(prev, cur, flag, {.planes = BoundaryPlanes::next_to_neighbours(planes), .out = out});
 }
 
 // One loop body: [pre/post on device] + pressure update + boundary update; flag -> flags_[slot]
@@ -352,7 +348,7 @@ int Engine<Real>::launch_whole_step(Real* prev, const Real* cur, int slot, uint6
     if (rc) return rc;
     sw.args.tile_list = nullptr;
     sw.grid = 8u * (unsigned)plan_.passes * (unsigned)(z_end_ - z_begin_) * (unsigned)(sw.args.tiles_x * sw.args.tiles_y_stripe);
-    if ((rc = launch_boundary(prev, cur, flag, z_begin_, z_end_, nullptr, nullptr, false, false, &bd))) return rc;
+    if ((rc = launch_boundary(prev, cur, flag, {.planes = BoundaryPlanes::of(z_begin_, z_end_), .plan_only = &bd}))) return rc;
     if (!n_entries_) bd.args = boundary_args(prev, cur, flag);
     wv::StepDuties<Real> d{};
     if (serve_next) {
@@ -417,7 +413,7 @@ int Engine<Real>::enqueue_step(int slot, bool with_pre_post, uint64_t signal_pos
         if (!comm_->bulk_begin(stream_, &cerr)) return fail(WV_E_COMM, cerr);  // (slabs of one device take turns at the interior sweep)
         if ((rc = launch_stream(prev, cur, flag, zi0, zi1, true))) return rc;
         if (!comm_->bulk_end(stream_, &cerr)) return fail(WV_E_COMM, cerr);
-        if ((rc = launch_boundary(prev, cur, flag, zi0, zi1))) return rc;
+        if ((rc = launch_boundary(prev, cur, flag, {.planes = BoundaryPlanes::of(zi0, zi1)}))) return rc;
     } else if (fuse_next != 2 && whole_step_ready()) {
         // (the duties were looked up when the batch was planned: nothing synchronises here)
         if ((rc = launch_whole_step(prev, cur, slot, signal_pos, source_live, fuse_next == 1))) return rc;
@@ -429,9 +425,9 @@ int Engine<Real>::enqueue_step(int slot, bool with_pre_post, uint64_t signal_pos
             wv::PrePostArgs<Real> nx = pre_post_args(prev, slot + 1, true, signal_pos + 1, source_live);
             if (fuse_next == 2) nx.flag2 = flags_ + slot + 2;  // a two-step pass follows: both its flag words
             assert(nx.n_recv <= 64);  // (fuse_next comes from batch_can_fuse_, which more than 64 columns never get: io_nodes)
-            if ((rc = launch_boundary(prev, cur, flag, z_begin_, z_end_, &nx))) return rc;
+            if ((rc = launch_boundary(prev, cur, flag, {.planes = BoundaryPlanes::of(z_begin_, z_end_), .ride = &nx}))) return rc;
             pre_post_done_ = true;
-        } else if ((rc = launch_boundary(prev, cur, flag, z_begin_, z_end_))) {
+        } else if ((rc = launch_boundary(prev, cur, flag, {.planes = BoundaryPlanes::of(z_begin_, z_end_)}))) {
             return rc;
         }
     }

@@ -18,7 +18,7 @@
 // fifth holds t+1 at the shell nodes and the boundary nodes of whatever pass is in flight and zeros at outside nodes.
 // (the exact-flags check shares the launch of fix-up list 3; the source / receiver work rides in the boundary launches where it may:
 // five launches.)  The x-facing walls' entries work on compact copies at all three levels and finish the two nodes in front of them
-// (boundary_kernels.hip.h, xwall3_node); a room that leaves much of its mesh outside marches a work list (build_triple_units); a
+// (boundary_kernels.hip.h, xwall_node<Real, 3, LEVEL>); a room that leaves much of its mesh outside marches a work list (build_triple_units); a
 // z-slab of a chain takes the same pass in three parts around three halo exchanges (enqueue_triple_slab).
 // Results are bit-identical to three single steps (tests/test_gpu_triple.py, test_gpu_slabs.py).
 #pragma once
@@ -365,20 +365,22 @@ int Engine<Real>::enqueue_triple(int slot, uint64_t signal_pos, bool source_live
     // is a boundary node: their t+1 has been final since the march) and then the second level's list where it is short and none of its
     // nodes has a boundary node for a neighbour (the source's neighbours, typically)
     const bool xw = triple_xw_ && xw_active_;
+    auto on_copies = [xw](int level) { return xw ? XwallUse{3, level} : XwallUse{}; };  // this pass's level `level`, if its x-facing walls work on their copies
     if (xw && !xw_valid_) refresh_xwall_copies(A, B, flag1);  // the x-facing walls' compact copies, from fields t-1 and t
     xw_valid_ = xw;  // (passes that do not maintain the copies leave them behind)
     wv::PrePostArgs<Real> nx = pre_post_args(O1, slot + 1, true, signal_pos + 1, source_live);
     nx.flag = nullptr;
     const bool list2_done = fuse && io && pair_list_early_ok_ && pair_list_n_;
     if (list2_done) carry_short_list(nx, B, O2, flag2);
-    if ((rc = launch_boundary_with_io(0, A, B, flag1, z_begin_, z_end_, O1, false, false, xw ? 1 : 0, nx,
+    if ((rc = launch_boundary_with_io(0, A, B, flag1, {.planes = BoundaryPlanes::of(z_begin_, z_end_), .out = O1, .copies = on_copies(1)}, nx,
                                       fuse && io ? IoRide::carried : io ? IoRide::behind : IoRide::none))) return rc;
     // level 2: the second level's list (as in a two-step pass), then the boundary nodes, whose 1-D entries finish the nodes they face --
     // with step t+2's source / receiver work where none of those nodes is written by the launch
     if (!list2_done && (rc = launch_fixup(0, pair_list_n_, O1, B, O2, flag2))) return rc;
     nx = pre_post_args(O2, slot + 2, true, signal_pos + 2, source_live);
     nx.flag = nullptr;
-    if ((rc = launch_boundary_with_io(1, B, O1, flag2, z_begin_, z_end_, O2, pair_inner_ok_ > 0, false, xw ? 2 : 0, nx,
+    if ((rc = launch_boundary_with_io(1, B, O1, flag2,
+                                      {.planes = BoundaryPlanes::of(z_begin_, z_end_), .out = O2, .fix_inner = pair_inner_ok_ > 0, .copies = on_copies(2)}, nx,
                                       fuse && io && io_nodes_unfaced() ? IoRide::carried : io ? IoRide::behind : IoRide::none))) return rc;
     // level 3: every shell node from the finished t+2 field -- and the exact error bits of what the march was the last to write, should it
     // have seen an inf or a nan (fields t-1 and t are still what the march read) --, then the boundary nodes
@@ -390,7 +392,7 @@ int Engine<Real>::enqueue_triple(int slot, uint64_t signal_pos, bool source_live
     const bool carry = fuse && fuse_next && (!xw || io_nodes_clear_of_x_walls());
     nx = pre_post_args(O3, slot + 3, true, signal_pos + 3, source_live);
     if (fuse_next == 2) nx.flag2 = flags_ + slot + 4;
-    if ((rc = launch_boundary_with_io(2, O1, O2, flag3, z_begin_, z_end_, O3, false, false, xw ? 3 : 0, nx,
+    if ((rc = launch_boundary_with_io(2, O1, O2, flag3, {.planes = BoundaryPlanes::of(z_begin_, z_end_), .out = O3, .copies = on_copies(3)}, nx,
                                       carry ? IoRide::carried : IoRide::none))) return rc;  // (not carried: the next step's or pass's own launch)
     if (carry) pre_post_done_ = true;
     pass_timed_ = false;
@@ -435,6 +437,7 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
     std::string cerr;
     const bool io = n_recv_ || source_live;
     const bool xw = triple_xw_ && xw_active_;
+    auto on_copies = [xw](int level) { return xw ? XwallUse{3, level} : XwallUse{}; };  // this pass's level `level`, if its x-facing walls work on their copies
     const size_t plane = (size_t)pitch_ * ny_;
     const int z0 = triple_plan_.z0, z1 = triple_plan_.z1;
     const int n0 = z0 - (opt_.ghost_lo ? 1 : 0), n1 = z1 + (opt_.ghost_hi ? 1 : 0);  // ... and the planes next to the faces
@@ -468,7 +471,7 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
         if (xw && !xw_valid_) refresh_xwall_copies(A, B, flag1);  // the x-facing walls' compact copies, from fields t-1 and t
         xw_valid_ = xw;
         const int token = begin_part_timing(0);
-        if ((rc = launch_boundary(A, B, flag1, z0, z1, nullptr, O1, false, false, nullptr, xw ? 1 : 0))) return rc;
+        if ((rc = launch_boundary(A, B, flag1, {.planes = BoundaryPlanes::of(z0, z1), .out = O1, .copies = on_copies(1)}))) return rc;
         if ((rc = end_part_timing(0, token))) return rc;
     } else if (part == 1) {
         if ((rc = wait_for(spare_[1]))) return rc;
@@ -480,7 +483,7 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
         if (!comm_->exchange_faces(stream_, spare_[0], &cerr)) return fail(WV_E_COMM, cerr);
         if ((rc = launch_fixup(0, pair_list_n_, O1, B, O2, flag2))) return rc;
         const int token = begin_part_timing(1);
-        if ((rc = launch_boundary(B, O1, flag2, n0, n1, nullptr, O2, pair_inner_ok_ > 0, false, nullptr, xw ? 2 : 0))) return rc;
+        if ((rc = launch_boundary(B, O1, flag2, {.planes = BoundaryPlanes::of(n0, n1), .out = O2, .fix_inner = pair_inner_ok_ > 0, .copies = on_copies(2)}))) return rc;
         if ((rc = end_part_timing(1, token))) return rc;
     } else {
         if ((rc = wait_for(spare_[0]))) return rc;
@@ -492,7 +495,7 @@ int Engine<Real>::enqueue_triple_slab(int slot, int part, uint64_t signal_pos, b
         if ((rc = launch_triple_list(slot, A, B, O1, O2, O3, source_live))) return rc;
         if ((rc = end_part_timing(3, token))) return rc;
         token = begin_part_timing(2);
-        if ((rc = launch_boundary(O1, O2, flag3, z0, z1, nullptr, O3, false, false, nullptr, xw ? 3 : 0))) return rc;
+        if ((rc = launch_boundary(O1, O2, flag3, {.planes = BoundaryPlanes::of(z0, z1), .out = O3, .copies = on_copies(3)}))) return rc;
         if ((rc = end_part_timing(2, token))) return rc;
         pass_timed_ = false;
         WV_HIP(hipGetLastError());
