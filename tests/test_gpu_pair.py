@@ -112,19 +112,22 @@ def test_pair_path_source_on_and_near_walls(oracle, where):
 
 
 @pytest.mark.parametrize("bad_step", [16, 17, 18, 0, 1])
-def test_pair_path_stops_at_the_failing_step(bad_step):
-    """The flag of each of the two steps of a pass is its own: the run stops at the exact step."""
+def test_pair_path_stops_at_the_failing_step(oracle, bad_step):
+    """The flag of each of the two steps of a pass is its own: the run stops at the exact step, with the oracle's word."""
     mesh = M.box_mesh(12, 12, 12)
     sig = np.zeros(40)
     sig[0] = 1.0
     sig[bad_step] = np.inf
+    want = run_oracle(oracle, dict(mesh=mesh, steps=40, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig,
+                                   recv=[mesh.compute_index(7, 6, 6)], init=None), np.float32)
+    assert want["steps"] == bad_step and want["flag"] & M.ERR_INF
     for pair in (1, 0):
         set_tuning(pair=pair)
         eng = E.Engine(mesh, precision="f32")
         eng.set_source(E.SOURCE_HARD, mesh.compute_index(6, 6, 6), sig)
         eng.set_receivers([mesh.compute_index(7, 6, 6)])
         done, flag = eng.run_steps(40)
-        assert done == bad_step and flag & M.ERR_INF
+        assert (done, flag) == (want["steps"], want["flag"])
         assert eng.fetch_receivers(0, bad_step).shape == (bad_step, 1)
         eng.close()
 

@@ -191,7 +191,7 @@ def test_slab_chain_equals_single_domain(built_library, world, room, dims, preci
             assert all(t == (steps - 2) // 3 for t in got["queries"][2]), got["queries"]
 
 
-def test_a_flag_on_one_slab_stops_the_whole_chain(built_library):
+def test_a_flag_on_one_slab_stops_the_whole_chain(built_library, oracle):
     """SURVEY.md 8(e) "error-flag OR": waveguide.h:100-119 throws on the step that produced the value;
     here every slab must stop there, not only the one that saw it."""
     dims = (16, 14, 24)
@@ -203,8 +203,12 @@ def test_a_flag_on_one_slab_stops_the_whole_chain(built_library):
     zeros = np.zeros(gmesh.num_nodes)
     want = single_domain(gmesh, "f64", zeros, zeros, E.SOURCE_HARD, source, sig, [gmesh.compute_index(8, 7, 20)], 40)
     got = slab_chain(gmesh, 3, "f64", zeros, zeros, E.SOURCE_HARD, source, sig, [gmesh.compute_index(8, 7, 20)], 40)
-    assert want["done"] == 17 and want["flag"] & M.ERR_INF
-    assert got["done"] == 17 and got["flag"] & M.ERR_INF
+    from helpers import run_oracle
+    named = run_oracle(oracle, dict(mesh=gmesh, steps=40, source_kind=E.SOURCE_HARD, source_node=source, signal=sig,
+                                    recv=[gmesh.compute_index(8, 7, 20)], init=None), np.float64)
+    assert named["steps"] == 17 and named["flag"] & M.ERR_INF
+    assert (want["done"], want["flag"]) == (named["steps"], named["flag"])
+    assert (got["done"], got["flag"]) == (named["steps"], named["flag"])
     assert got["trace"].tobytes() == want["trace"].tobytes()
 
 

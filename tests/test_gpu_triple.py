@@ -257,12 +257,16 @@ def test_triple_path_source_on_and_near_walls(oracle, where):
 
 @pytest.mark.parametrize("bad_step", [15, 16, 17, 18, 0, 1, 2])
 @pytest.mark.parametrize("tag", ["f32", "f64"])
-def test_triple_path_stops_at_the_failing_step(bad_step, tag):
-    """The flag of each of the three steps of a pass is its own: the run stops at the exact step, with the reference's bits."""
+def test_triple_path_stops_at_the_failing_step(oracle, bad_step, tag):
+    """The flag of each of the three steps of a pass is its own: the run stops at the exact step, with the oracle's word."""
     mesh = M.box_mesh(12, 12, 12)
     sig = np.zeros(40)
     sig[0] = 1.0
     sig[bad_step] = np.inf
+    case = dict(mesh=mesh, steps=40, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig,
+                recv=[mesh.compute_index(7, 6, 6)], init=None)
+    want = run_oracle(oracle, case, np.float32 if tag == "f32" else np.float64)
+    assert want["steps"] == bad_step and want["flag"] & M.ERR_INF
     results = []
     for triple in (1, 0):
         set_tuning(pair=triple, triple=triple, tile_lists=0)
@@ -270,7 +274,7 @@ def test_triple_path_stops_at_the_failing_step(bad_step, tag):
         eng.set_source(E.SOURCE_HARD, mesh.compute_index(6, 6, 6), sig)
         eng.set_receivers([mesh.compute_index(7, 6, 6)])
         done, flag = eng.run_steps(40)
-        assert done == bad_step and flag & M.ERR_INF
+        assert (done, flag) == (want["steps"], want["flag"])
         assert eng.fetch_receivers(0, bad_step).shape == (bad_step, 1)
         results.append((done, flag))
         eng.close()

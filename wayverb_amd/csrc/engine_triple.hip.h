@@ -302,7 +302,8 @@ int Engine<Real>::launch_triple_march(int slot, const Real* A, const Real* B, Re
 }
 
 // The third level's list -- every shell node of the march's planes from the finished t+2 field -- and the exact error bits of what the
-// march was the last to write, should it have seen an inf or a nan (fields t-1 and t are still what the march read).
+// march was the last to write, should it have seen an inf or a nan (fields t-1 and t are still what the march read) -- a slab's t+2 on
+// the planes next to its face planes included.
 template <typename Real>
 int Engine<Real>::launch_triple_list(int slot, const Real* A, const Real* B, const Real* O1, const Real* O2, Real* O3, bool source_live) {
     wv::PairFixupArgs<Real> f{};
@@ -334,6 +335,8 @@ int Engine<Real>::launch_triple_list(int slot, const Real* A, const Real* B, con
     g.cls_pitch = cls_pitch_;
     g.z_begin = triple_plan_.z0;
     g.z_end = triple_plan_.z1;
+    g.z2_lo = triple_plan_.z0 > z_begin_ ? 1 : 0;  // (launch_triple_march: the planes whose t+2 the march stored)
+    g.z2_hi = triple_plan_.z1 < z_end_ ? 1 : 0;
     hipLaunchKernelGGL(wv::triple_list_kernel<Real>, dim3(std::max(1u, (triple_list_n_ + 255) / 256)), dim3(256), 0, stream_, f, g);
     return WV_OK;
 }

@@ -608,7 +608,9 @@ __global__ void __launch_bounds__(256) triple_mark_kernel(const TripleMarkArgs a
 // ---- exact error bits of the values the march is the last to write, when it has seen an inf or a nan (never in a healthy run) -------
 // Launched behind every march; leaves at once unless `suspect` is set.  t+1 of every node that takes the 7-point update (recomputed:
 // a deep node's t+1 is not stored); t+2 where nothing but plain nodes lies within one node, t+3 within two (the placeholders' owners --
-// fix-up lists, boundary launches -- test their own values).
+// fix-up lists, boundary launches -- test their own values).  A z-slab's march is also the last to write t+2 on the plane next to a face
+// plane (TripleArgs::z2_lo / z2_hi): that plane is tested for t+2 alone -- its t+1 and t+3 are plain steps' (launch_faces), which test
+// what they store.
 template <typename Real>
 struct TripleFlagsArgs {
     const Real *prev, *cur, *out2, *out3;
@@ -618,13 +620,15 @@ struct TripleFlagsArgs {
     uint64_t source_node;
     int nx, ny, nz, pitch, cls_pitch;
     int z_begin, z_end;
+    int z2_lo, z2_hi;  // as TripleArgs': t+2 of the plane beyond either end is the march's too
 };
 
 template <typename Real>
 __device__ __forceinline__ void triple_flags_body(const TripleFlagsArgs<Real>& a) {
     if (*a.suspect == 0) return;
     const int64_t plane = (int64_t)a.pitch * a.ny;
-    const int64_t n = plane * (a.z_end - a.z_begin);
+    const int z_first = a.z_begin - a.z2_lo;
+    const int64_t n = plane * (a.z_end + a.z2_hi - z_first);
     auto pc_at = [&](int x, int y, int z) -> uint32_t {
         if (x < 0 || x >= a.pitch || y < 0 || y >= a.ny || z < 0 || z >= a.nz) return 1u;
         return (a.pair_map[cls_byte_index(x, y, z, a.ny, a.cls_pitch)] >> ((x & 3) * 2)) & 3u;
@@ -637,9 +641,13 @@ __device__ __forceinline__ void triple_flags_body(const TripleFlagsArgs<Real>& a
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int x = (int)(i % a.pitch);
         const int64_t q = i / a.pitch;
-        const int y = (int)(q % a.ny), z = a.z_begin + (int)(q / a.ny);
+        const int y = (int)(q % a.ny), z = z_first + (int)(q / a.ny);
         const uint32_t pc = pc_at(x, y, z);
         if (!(pc & 1u)) continue;
+        if (z < a.z_begin || z >= a.z_end) {  // next to a slab's face plane: t+2 where nothing but plain nodes lies within one node, no more
+            if (pc == 1u) bad2 |= bad_bits(at(a.out2, x, y, z));
+            continue;
+        }
         Real s = Real(0) + at(a.cur, x - 1, y, z);
         s += at(a.cur, x + 1, y, z);
         s += at(a.cur, x, y - 1, z);
