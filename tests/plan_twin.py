@@ -399,9 +399,8 @@ def stop_plan(eng, kind):
         KINDS[kind].count(eng)
 
 
-def assert_outputs(eng, kind, want, where):
-    """Every output of the active plan, under the names of PlanTwin.expected: dtype, shape, then bytes."""
-    got = dict(count=KINDS[kind].count(eng), **KINDS[kind].fetch(eng))
+def assert_same(got, want, where=None):
+    """Two sets of outputs under the same names: dtype, shape, then bytes."""
     assert sorted(got) == sorted(want), where
     for name in sorted(want):
         if isinstance(want[name], np.ndarray):
@@ -409,6 +408,11 @@ def assert_outputs(eng, kind, want, where):
             assert got[name].tobytes() == want[name].tobytes(), (name, where)
         else:
             assert got[name] == want[name], (name, got[name], want[name], where)
+
+
+def assert_outputs(eng, kind, want, where):
+    """Every output of the active plan, under the names of PlanTwin.expected: dtype, shape, then bytes."""
+    assert_same(dict(count=KINDS[kind].count(eng), **KINDS[kind].fetch(eng)), want, where)
 
 
 class PlanTwin(Twin):

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from plan_cases import random_sections
 from test_arrival_host import NAN_CAPTURE, T, THRESHOLD, series
 from wayverb_amd import arrival as A
 from wayverb_amd import decay as D
@@ -20,16 +21,6 @@ SOURCE = os.path.join(ROOT, "tests", "cpp", "arrival_bands_kernel_host.cpp")
 COMPILE = ["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized", "-ffp-contract=off",
            "-I", os.path.join(ROOT, "tests", "cpp", "hip_stub"), "-I", CSRC, SOURCE]
 IDENTITY = np.array([[[1.0, 0.0, 0.0, 0.0, 0.0]]])
-
-
-def random_sections(K, S, seed):
-    """float64[K][S][5]: stable sections (|a1| < 1 + a2, 0 < a2 < 1) with numerators of either sign -- the fold is held to the bits
-    whatever the filter is."""
-    rng = np.random.default_rng(seed)
-    a2 = rng.uniform(0.1, 0.8, (K, S))
-    a1 = rng.uniform(-0.9, 0.9, (K, S)) * (1.0 + a2)
-    b = rng.standard_normal((K, S, 3))
-    return np.ascontiguousarray(np.concatenate([b, a1[..., None], a2[..., None]], axis=2))
 
 
 def run_host(exe, tmp_path, snaps, edges, sections, tail, lags, threshold, threshold_map, first_fold):

@@ -57,6 +57,48 @@ def test_the_plans_are_the_issues():
     assert plain["max_lag"] == 16 and plain["sections"] is None and plain["ear_a"] == (-1, 0, 1)
 
 
+def test_the_life_cycle_columns_are_there_for_every_kind_and_name_what_the_engine_has(eleven_kinds):
+    """tests/plan_cases.py COLUMNS beside plan_twin.KINDS: every accumulating kind has every column, the query constants are
+    Engine's own (three per kind, five where the kind gathers, the two decay kinds sharing theirs), the refusal sentences are the ones
+    the library's sources and tests/golden/arrival_bands_refusals.json spell, and a plan written by plan_on is plan_twin's."""
+    import json
+    import os
+    import re
+    import plan_cases as C
+    from wayverb_amd import engine as E
+    assert tuple(C.COLUMNS) == tuple(k for k in K.KINDS11 if k != "snapshots")
+    constants = {name: getattr(E.Engine, name) for name in dir(E.Engine) if name.startswith("QUERY_")}
+    used = []
+    for kind, column in C.COLUMNS.items():
+        row = C.kind_row(kind)
+        assert all(hasattr(row, name) for name in C.COLUMN_NAMES + ("set", "stop", "count", "fetch", "expect", "something", "hull", "setter", "active")), kind
+        assert tuple(column.queries)[:3] == ("captures", "folds", "ns") and len(column.queries) in (3, 5), kind
+        prefix = {name[:-len("_CAPTURES")] for name, value in constants.items() if value == column.queries["captures"] and name.endswith("_CAPTURES")}
+        assert len(prefix) == 1, kind
+        for name, value in column.queries.items():
+            assert constants[prefix.copy().pop() + "_" + name.upper()] == value, (kind, name)
+        assert ("gathers" in column.queries) == (prefix.copy().pop() + "_GATHERS" in constants), kind
+        used.append(tuple(column.queries.values()))
+        assert re.fullmatch(r"wv_rollback: the [a-z ]+ plan was set after the checkpoint \(its (sums|bins|state) ha(ve|s) no copy to go back to\)", column.rollback), kind
+        assert sorted(column.no_plan) == ["count", "fetch"] and all(re.fullmatch(r"wv_\w+: no [a-z ]+ plan is set", s) for s in column.no_plan.values()), kind
+        assert hasattr(E.Engine, "set_" + column.answer[0][:-len("_shape")]) and callable(column.meaningful) and callable(column.spread) and callable(column.captures)
+    assert len(set(used)) == 9 and used[1] == used[2]         # decay and banded decay: one plan in the engine, one set of counters
+    source = "".join(open(os.path.join(os.path.dirname(E.__file__), "csrc", name)).read() for name in ("engine.hip.h", "engine_staged.hip.h", "engine_io.hip.h"))
+    for kind, column in C.COLUMNS.items():        # the sentences are put together from StagedPlan's name and `lost`
+        name, lost = re.fullmatch(r"wv_rollback: the (.+) plan was set after the checkpoint \((.+) no copy to go back to\)", column.rollback).groups()
+        assert '"%s", "%s", "%s"' % (name, P.KINDS["decay" if kind == "banded" else kind].setter, lost) in source, kind
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "arrival_bands_refusals.json")))
+    bands = C.COLUMNS["arrival_bands"]
+    assert golden["rollback"] == [-6, bands.rollback]
+    assert golden["no_plan"] == dict(arrival_bands_count=[-6, bands.no_plan["count"]], fetch_arrival_bands=[-6, bands.no_plan["fetch"]])
+    plan = C.plan_on("random", "interaural", box=((0, 2, 0), (None, 16, None)), stride=3, period=7, threshold=0.0, ear_a=(0, -2, 0), ear_b=(0, 2, 0))
+    assert plan["box"] == ((0, 2, 0), (24, 16, 28)) and plan["stride"] == (3, 3, 3) and plan["first_step"] == 0 and plan["threshold_map"] is None
+    assert P.taken(plan) == (8, 6, 10) and C.whole_mesh(plan) == dict(box="mesh", first_step=0, period=7)
+    hull = C.plan_on((24, 20, 28), "lateral", box=((3, 2, 4), (9, 9, 7)), threshold=0.5)
+    assert C.captured_by(hull) == dict(box=((2, 1, 3), (11, 11, 9)), stride=(1, 1, 1), first_step=0, period=1) == dict(C.hull_of(hull)[0], stride=(1, 1, 1), first_step=0)
+    assert C.resolved(dict(hull, threshold=lambda snaps, plan: snaps + plan["period"]), 2)["threshold"] == 3
+
+
 def front_form(plan):
     """(the kind's *_plan_arguments applied to the plan written as canonical's dict at RATE, the keys of the answer that must be the
     plan's own) -- or None for a kind that has no such function (snapshots and the two decay plans go to the engine as they are)."""

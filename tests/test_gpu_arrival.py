@@ -7,8 +7,8 @@ import pytest
 
 import cases
 from helpers import set_tuning
-from test_gpu_decay import BOXES, reference_snapshots
-from test_gpu_snapshots import FORMS, make_engine
+from plan_cases import (BOXES, FILE_FORMS, FORMS, FORM_QUERIES, box_scene, changes_nothing, check, default_tuning_afterwards, make_engine,
+                        median_threshold, plan_engine, plan_on, reference_snapshots, scaled_map)
 from wayverb_amd import arrival as A
 from wayverb_amd import engine as E
 from wayverb_amd import mesh as M
@@ -20,61 +20,20 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(autouse=True)
 def _default_tuning_afterwards(built_library):
     yield
-    set_tuning()
+    default_tuning_afterwards()
 
 
-def median_threshold(snaps):
-    """The median, over the box's nodes, of the reference snapshots' per-node max |p| (float32, as the plan holds it)."""
-    return np.float32(np.median(np.abs(snaps).max(axis=0)))
-
-
-def arrival_engine(case_name, tag, form, plan, edges, threshold, threshold_map=None):
-    set_tuning(**FORMS[form])
-    eng = make_engine(cases.CASES[case_name](), tag)
-    shape = eng.set_arrival(edges, threshold, threshold_map=threshold_map, **plan)
-    return eng, shape
+def arrival_plan(case, cadence, edges, threshold=median_threshold, map_factors=None):
+    """`threshold`: a number, or a callable(snaps, plan) of the reference's snapshots; `map_factors`: a per-node map of that many times it."""
+    if map_factors is not None:
+        return plan_on(case, "arrival", edges=list(edges), threshold=0.0, threshold_map=scaled_map(threshold, map_factors), **cadence)
+    return plan_on(case, "arrival", edges=list(edges), threshold=threshold, **cadence)
 
 
 def same(got, want):
     for key in A.KEYS:
         assert got[key].dtype == want[key].dtype and got[key].shape == want[key].shape, key
         assert got[key].tobytes() == want[key].tobytes(), "%s differs at %d nodes" % (key, (got[key] != want[key]).sum())
-
-
-def not_trivial(want, nodes):
-    """What the reference alone must show before a comparison means anything."""
-    heard = want["onset"] != A.NONE
-    assert heard.sum() >= nodes / 4 and (~heard).sum() >= nodes / 4, (heard.sum(), nodes)
-    assert len(set(want["onset"][heard].tolist())) >= 3, sorted(set(want["onset"][heard].tolist()))
-    assert (want["bins"].reshape(want["bins"].shape[0], -1).max(axis=1) > 0).sum() >= 2
-
-
-def check(case_name, tag, form, plan, edges, n_steps, threshold=None, map_factors=None, query=None, trivial_check=True):
-    snaps, steps = reference_snapshots(case_name, tag, form, plan, n_steps)
-    thr = median_threshold(snaps) if threshold is None else np.float32(threshold(snaps) if callable(threshold) else threshold)
-    threshold_map = None if map_factors is None else (thr * map_factors(snaps.shape[1:])).astype(np.float32)
-    want = A.arrival_fold(snaps, thr if threshold_map is None else threshold_map, edges)
-    if trivial_check:
-        not_trivial(want, want["onset"].size)
-    eng, shape = arrival_engine(case_name, tag, form, plan, edges, 0.0 if threshold_map is not None else thr, threshold_map)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.arrival_count() == (len(steps), int(steps[-1]))
-        got, captures = eng.fetch_arrival()
-        if query is not None:
-            assert eng.query(query) > 0
-        assert eng.query(E.Engine.QUERY_ARRIVAL_CAPTURES) == len(steps)
-        folds = eng.query(E.Engine.QUERY_ARRIVAL_FOLDS)
-    finally:
-        eng.close()
-    assert captures == len(steps) and len(steps) > 1
-    assert shape == want["bins"].shape
-    assert folds <= -(-len(steps) // 16) + 1
-    same(got, want)
-    return got, want, snaps
-
-
-FORM_QUERIES = {"single": None, "graph": None, "pair": E.Engine.QUERY_PASSES, "triple": E.Engine.QUERY_TRIPLE_PASSES}
 
 
 @pytest.mark.parametrize("period", range(1, 8))
@@ -95,16 +54,17 @@ def test_every_stepping_form_gives_the_fold_of_the_snapshots(form, period, tag):
     # (a pass form shows in its counter only where the period leaves room for a pass of that length)
     query = FORM_QUERIES[form] if (form == "pair" and period >= 2) or (form == "triple" and period >= 3) else None
     plan = dict(box=((0, 0, 15), (None, None, 1)), period=period)
-    got, want, snaps = check("impulse_flat", tag, form, plan, (0, 1, 3), n_steps, query=query, trivial_check=period % 2 == 1)
+    got, want, _, snaps, _ = check("arrival", "impulse_flat", tag, form, arrival_plan("impulse_flat", plan, (0, 1, 3)), n_steps, query,
+                                   **({} if period % 2 == 1 else dict(condition=None)))
     if period % 2 == 1:
         assert median_threshold(snaps) > 0
     else:
         assert median_threshold(snaps) == 0 and (want["onset"] == 0).all() and (want["bins"].reshape(3, -1).max(axis=1) > 0).sum() >= 2
 
-        def lower_quartile(snaps):
+        def lower_quartile(snaps, plan):
             highest = np.abs(snaps).max(axis=0)
-            return np.quantile(highest[highest > 0], 0.25)
-        check("impulse_flat", tag, form, plan, (0, 1, 3), n_steps, threshold=lower_quartile)
+            return np.float32(np.quantile(highest[highest > 0], 0.25))
+        check("arrival", "impulse_flat", tag, form, arrival_plan("impulse_flat", plan, (0, 1, 3), lower_quartile), n_steps)
 
 
 def _random_factors(shape):
@@ -118,8 +78,8 @@ def test_boxes_and_strides_on_a_room_with_walls(name, with_map):
     every step captured, 33 captures (16 + 16 + 1), edges (0, 1, 5, 16, 17): an edge inside a fold, one on a fold's first slot and
     one behind it.  Once with the scalar median threshold, once with a per-node map of 0.1 .. 10 times that median.  (One node has no
     quarter of nodes to show: the box of one node is compared as it is.)"""
-    check("random", "f64", "triple", dict(BOXES[name], period=1), (0, 1, 5, 16, 17), 32, map_factors=_random_factors if with_map else None,
-          trivial_check=name != "one-node")
+    plan = arrival_plan("random", dict(BOXES[name], period=1), (0, 1, 5, 16, 17), map_factors=_random_factors if with_map else None)
+    check("arrival", "random", "f64", "triple", plan, 32, **(dict(condition=None) if name == "one-node" else {}))
 
 
 @pytest.mark.parametrize("w,n_bins", [(1, 16), (5, 7), (16, 3), (40, 2)])
@@ -128,7 +88,7 @@ def test_threshold_zero_and_even_edges_equal_the_decay_plan(w, n_bins):
     one on the same captures."""
     plan = dict(BOXES["sub-box-567-odd"], period=1)
     edges = [k * w for k in range(n_bins)]
-    got, want, snaps = check("random", "f64", "pair", plan, edges, 32, threshold=0.0, trivial_check=False)
+    got = check("arrival", "random", "f64", "pair", arrival_plan("random", plan, edges, 0.0), 32, condition=None)[0]
     set_tuning(**FORMS["pair"])
     eng = make_engine(cases.CASES["random"](), "f64")
     eng.set_decay(n_bins, w, **plan)
@@ -150,7 +110,7 @@ def test_no_onset_is_earlier_than_the_stencil_can_carry_it(tag):
     n_steps = 20
     case = cases.CASES["impulse_flat"]()
     first_sample = int(np.flatnonzero(case["signal"])[0])
-    eng, shape = arrival_engine("impulse_flat", tag, "triple", dict(box="mesh", period=1), (0, 8), 1e-30)
+    eng = plan_engine("impulse_flat", tag, "triple", arrival_plan("impulse_flat", dict(box="mesh", period=1), (0, 8), 1e-30))
     try:
         assert eng.run_steps(n_steps) == (n_steps, 0)
         got, captures = eng.fetch_arrival()
@@ -167,129 +127,6 @@ def test_no_onset_is_earlier_than_the_stencil_can_carry_it(tag):
     far = distance > n_steps
     assert far.sum() > 1000 and not heard[far].any() and (got["peak"][far] == 0).all() and (got["peak_capture"][far] == A.NONE).all()
     assert (got["pre"][~heard] == 0).all() and (got["peak"][heard] > 0).all()
-
-
-def test_fetching_mid_run_and_at_the_end():
-    plan = dict(BOXES["sub-box-630"], period=1)
-    edges = (0, 1, 5, 16, 17)
-    snaps, steps = reference_snapshots("random", "f64", "pair", plan, 30)
-    thr = median_threshold(snaps)
-    eng, _ = arrival_engine("random", "f64", "pair", plan, edges, thr)
-    try:
-        assert eng.run_steps(13) == (13, 0)
-        mid, mid_count = eng.fetch_arrival()
-        again, again_count = eng.fetch_arrival()
-        assert eng.run_steps(17) == (17, 0)
-        end, end_count = eng.fetch_arrival()
-    finally:
-        eng.close()
-    assert (mid_count, again_count, end_count) == (14, 14, 31)
-    same(mid, A.arrival_fold(snaps[:14], thr, edges))
-    same(again, mid)
-    want = A.arrival_fold(snaps, thr, edges)
-    same(end, want)
-    assert ((want["onset"] >= 14) & (want["onset"] != A.NONE)).any()      # onsets on both sides of the fetch
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-def test_checkpoint_run_rollback_rerun_gives_the_same_state_twice(form):
-    """The impulse room's plane: the wavefront is crossing it at the checkpoint, so some onsets lie before it and some behind."""
-    plan = dict(box=((0, 0, 15), (None, None, 1)), period=1)
-    edges = (0, 2, 6)
-    snaps, steps = reference_snapshots("impulse_flat", "f64", form, plan, 27)
-    thr = median_threshold(snaps)
-    want = A.arrival_fold(snaps, thr, edges)
-    heard = want["onset"] != A.NONE
-    assert (want["onset"][heard] <= 10).any() and (want["onset"][heard] > 10).any()
-    eng, _ = arrival_engine("impulse_flat", "f64", form, plan, edges, thr)
-    try:
-        assert eng.run_steps(10) == (10, 0)            # captures of 0 .. 10
-        eng.checkpoint()
-        assert eng.run_steps(17) == (17, 0)
-        first, first_count = eng.fetch_arrival()
-        eng.rollback()
-        assert eng.step_count() == 10 and eng.arrival_count() == (11, 10)
-        kept, kept_count = eng.fetch_arrival()
-        assert eng.run_steps(17) == (17, 0)
-        second, second_count = eng.fetch_arrival()
-        assert eng.arrival_count() == (28, 27)
-        # a plan set after the checkpoint has no state to go back to
-        eng.set_arrival(edges, thr, **plan)
-        with pytest.raises(E.WaveguideError, match="error -6: .*after the checkpoint"):
-            eng.rollback()
-    finally:
-        eng.close()
-    assert (first_count, kept_count, second_count) == (28, 11, 28)
-    same(kept, A.arrival_fold(snaps[:11], thr, edges))
-    same(first, want)
-    same(second, want)
-
-
-@pytest.mark.parametrize("bad_step", [12, 13])
-def test_a_run_that_stops_on_a_flag_holds_nothing_of_a_later_step(bad_step):
-    """inf in the source signal at step f: the run completes f steps; with a capture every 4 steps the state holds the captures of
-    0, 4, 8, 12 and nothing of 16, whose field the batch had already produced when the flag was read."""
-    set_tuning(**FORMS["triple"])
-    mesh = M.box_mesh(12, 12, 12)
-    sig = np.zeros(40)
-    sig[0] = 1.0
-    sig[bad_step] = np.inf
-    case = dict(mesh=mesh, init=None, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig,
-                recv=[mesh.compute_index(7, 6, 6)])
-    plan = dict(box=((0, 0, 6), (None, None, 1)), period=4)
-    engines = [make_engine(case, "f64", plan), make_engine(case, "f64")]
-    try:
-        engines[1].set_arrival((0, 1), 1e-3, **plan)
-        for eng in engines:
-            done, flag = eng.run_steps(40)
-            assert done == bad_step and flag & M.ERR_INF
-        snaps, steps = engines[0].fetch_snapshots()
-        assert list(steps) == [0, 4, 8, 12] and engines[1].arrival_count() == (4, 12)
-        got, count = engines[1].fetch_arrival()
-    finally:
-        for eng in engines:
-            eng.close()
-    want = A.arrival_fold(snaps, np.float32(1e-3), (0, 1))
-    assert count == 4 and np.isfinite(got["bins"]).all() and np.isfinite(got["peak"]).all() and (want["onset"] != A.NONE).any()
-    same(got, want)
-
-
-def test_generic_steps_in_between_capture_nothing():
-    set_tuning(**FORMS["pair"])
-    case = cases.CASES["random"]()
-    plan = dict(box=((0, 0, 0), (None, None, 2)), period=3)
-    engines = [make_engine(case, "f32"), make_engine(case, "f32")]
-    try:
-        for e in engines:
-            assert e.run_steps(9) == (9, 0)
-        engines[0].set_arrival((0, 1), 0.2, **plan)       # steps 0, 3, 6 lie before the plan; 9 is the count it is set at
-        engines[1].set_snapshots(**plan)
-        assert engines[0].arrival_count() == (0, 0)
-        for e in engines:
-            assert e.run_steps(4) == (4, 0)               # 9 (at the start of this run), 12
-            for _ in range(3):                            # 13 -> 16 by generic steps: 15 is passed
-                assert e.step() == 0
-                e.swap()
-        assert engines[0].arrival_count() == (2, 12)
-        for e in engines:
-            assert e.run_steps(2) == (2, 0)               # 18
-        got, count = engines[0].fetch_arrival()
-        snaps, steps = engines[1].fetch_snapshots()
-        assert list(steps) == [9, 12, 18] and count == 3
-        want = A.arrival_fold(snaps, np.float32(0.2), (0, 1))
-        same(got, want)
-        assert (want["onset"] != A.NONE).any() and (want["onset"] == A.NONE).any()
-        engines[0].set_arrival(None)                      # stops, forgets and frees ...
-        with pytest.raises(E.WaveguideError, match="error -6: .*no arrival plan"):
-            engines[0].arrival_count()
-        with pytest.raises(E.WaveguideError, match="error -6: .*no arrival plan"):
-            engines[0].fetch_arrival()
-        engines[0].set_decay(2, 2, **plan)                # ... and a decay plan takes its place
-        assert engines[0].run_steps(3) == (3, 0) and engines[0].decay_count() == (2, 21)
-        assert engines[0].fetch_decay()[0].max() > 0
-    finally:
-        for e in engines:
-            e.close()
 
 
 def test_refusals_leave_an_earlier_plan_intact():
@@ -380,47 +217,19 @@ def test_refusals_leave_an_earlier_plan_intact():
         group.close()
 
 
-@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("form", FILE_FORMS["arrival"])
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_a_plan_changes_nothing_the_run_computes(form, tag):
-    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise."""
-    set_tuning(**FORMS[form])
-    case = cases.CASES["random"]()
-    out = []
-    for plan in (None, dict(box="mesh", stride=(1, 2, 1), period=7, first_step=3)):
-        eng = make_engine(case, tag)
-        try:
-            if plan:
-                eng.set_arrival((0, 2, 4), 0.3, **plan)
-            assert eng.run_steps(case["steps"]) == (case["steps"], 0)
-            out.append([eng.fetch_receivers(0, case["steps"]), eng.read_field(E.BUF_CURRENT), eng.read_field(E.BUF_PREVIOUS)] +
-                       [eng.read_boundary_data(d) for d in (1, 2, 3)])
-            if plan:
-                assert eng.arrival_count() == (9, 59)   # steps 3, 10, ..., 59
-        finally:
-            eng.close()
-    for a, b in zip(*out):
-        assert a.tobytes() == b.tobytes()
-    assert np.abs(out[0][0]).max() > 0
-
-
-def test_kernel_timing_accounts_for_the_fold_kernels():
-    eng, _ = arrival_engine("impulse_flat", "f64", "single", dict(box="mesh", period=1), (0, 4, 8), 1e-6)
-    try:
-        eng.enable_kernel_timing(True)
-        assert eng.run_steps(40) == (40, 0)
-        eng.fetch_arrival()
-        assert eng.query(E.Engine.QUERY_ARRIVAL_FOLDS) == 3 and eng.query(E.Engine.QUERY_ARRIVAL_NS) > 0
-    finally:
-        eng.close()
+    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise:
+    plan_cases.changes_nothing, in the forms this file always named."""
+    changes_nothing("arrival", tag, form)
 
 
 def test_canonical_returns_the_maps_beside_the_receiver_output():
     """simulation.canonical(..., arrival=...): the records are those of a run without a plan, the state is the engine-level one
     (folded from canonical's own snapshots of the same plane and cadence)."""
-    from test_gpu_decay import _box_scene
     set_tuning()
-    W, vm, source, receiver = _box_scene()
+    W, vm, source, receiver = box_scene()
     env = W.Environment()
     rate = W.compute_sample_rate(vm.mesh.spacing, env.speed_of_sound)
     seconds = 39.5 / rate      # 40 steps

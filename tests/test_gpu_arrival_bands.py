@@ -14,12 +14,13 @@ import pytest
 
 import cases
 from helpers import set_tuning
-from test_arrival_bands_host import IDENTITY, random_sections
-from test_gpu_decay import BOXES, reference_snapshots
-from test_gpu_plan_refusals import CONSTANTS, refusal
+from test_arrival_bands_host import IDENTITY
+from plan_cases import (BOXES, FILE_FORMS, FORMS, FORM_QUERIES, box_scene, changes_nothing, check, default_tuning_afterwards,
+                        make_engine, plan_on, random_sections, reference_snapshots, scaled_map)
+from plan_cases import median_or_lower_quartile as threshold_of
+from test_gpu_plan_refusals import refusal
 from test_gpu_plan_refusals import SET as SET7
 from test_gpu_plan_refusals import STOP as STOP7
-from test_gpu_snapshots import FORMS, make_engine
 from wayverb_amd import arrival as A
 from wayverb_amd import decay as D
 from wayverb_amd import engine as E
@@ -38,57 +39,20 @@ PLANE = dict(box=((0, 0, 15), (None, None, 1)))      # of the 32^3 impulse room
 @pytest.fixture(autouse=True)
 def _default_tuning_afterwards(built_library):
     yield
-    set_tuning()
+    default_tuning_afterwards()
 
 
-def threshold_of(snaps):
-    """The median, over the box's nodes, of the snapshots' per-node max |p|, so that lanes of one wave sit in different bins; where
-    that is 0 (an impulse seen at an even period: more than half of the nodes never move) the lower quartile of the non-zero maxima."""
-    highest = np.abs(snaps).max(axis=0)
-    median = np.float32(np.median(highest))
-    return median if median > 0 or not (highest > 0).any() else np.float32(np.quantile(highest[highest > 0], 0.25))
-
-
-def bands_engine(case_name, tag, form, plan, edges, sections, threshold, **more):
-    set_tuning(**FORMS[form])
-    eng = make_engine(cases.CASES[case_name](), tag)
-    shape = eng.set_arrival_bands(edges, sections, threshold, **dict(more, **plan))
-    return eng, shape
+def bands_plan(case, cadence, edges, sections, tail=None, lag=0, threshold=threshold_of, map_factors=None):
+    """`threshold`: a number, or a callable(snaps, plan) of the reference's snapshots; `map_factors`: a per-node map of that many times it."""
+    lag = [int(lag)] * sections.shape[0] if np.isscalar(lag) else list(lag)
+    onset = dict(threshold=threshold) if map_factors is None else dict(threshold=0.0, threshold_map=scaled_map(threshold, map_factors))
+    return plan_on(case, "arrival_bands", edges=list(edges), bands=sections, tail=tail, lag=lag, **onset, **cadence)
 
 
 def same(got, want):
     for key in A.KEYS:
         assert got[key].dtype == want[key].dtype and got[key].shape == want[key].shape, key
         assert got[key].tobytes() == want[key].tobytes(), "%s differs at %d places" % (key, (got[key] != want[key]).sum())
-
-
-def check(case_name, tag, form, plan, edges, sections, n_steps, tail=None, lag=0, threshold=None, map_factors=None, query=None, spread=True):
-    snaps, steps = reference_snapshots(case_name, tag, form, plan, n_steps)
-    thr = threshold_of(snaps) if threshold is None else np.float32(threshold)
-    threshold_map = None if map_factors is None else (thr * map_factors(snaps.shape[1:])).astype(np.float32)
-    want = A.banded_arrival_fold(snaps, thr if threshold_map is None else threshold_map, edges, sections, tail=tail, lag=lag)
-    if spread:      # what the reference alone must show before a comparison means anything
-        heard = want["onset"] != A.NONE
-        assert heard.any() and (~heard).any() and len(set(want["onset"][heard].tolist())) >= 3
-        assert (want["bins"].reshape(want["bins"].shape[:2] + (-1,)).max(axis=2) > 0).sum(axis=1).min() >= 2
-    eng, shape = bands_engine(case_name, tag, form, plan, edges, sections, 0.0 if threshold_map is not None else thr, tail=tail, lag=lag,
-                              threshold_map=threshold_map)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.arrival_bands_count() == (len(steps), int(steps[-1]))
-        got, captures = eng.fetch_arrival_bands()
-        if query is not None:
-            assert eng.query(query) > 0
-        assert eng.query(E.Engine.QUERY_ARRIVAL_BANDS_CAPTURES) == len(steps)
-        folds = eng.query(E.Engine.QUERY_ARRIVAL_BANDS_FOLDS)
-    finally:
-        eng.close()
-    assert captures == len(steps) and shape == want["bins"].shape and folds <= -(-len(steps) // 16) + 1
-    same(got, want)
-    return got, want, snaps
-
-
-FORM_QUERIES = {"single": None, "graph": None, "pair": E.Engine.QUERY_PASSES, "triple": E.Engine.QUERY_TRIPLE_PASSES}
 
 
 @pytest.mark.parametrize("period", [1, 2, 3, 7])
@@ -100,7 +64,8 @@ def test_every_stepping_form_gives_the_fold_of_the_snapshots(form, period, tag):
     node's onset and a tail of two-capture bins from 4."""
     n_steps = 64 if form == "graph" else 30
     query = FORM_QUERIES[form] if (form == "pair" and period >= 2) or (form == "triple" and period >= 3) else None
-    check("impulse_flat", tag, form, dict(PLANE, period=period), (0, 1, 3), random_sections(2, 2, 3), n_steps, tail=(3, 4, 2), lag=(0, 2), query=query)
+    plan = bands_plan("impulse_flat", dict(PLANE, period=period), (0, 1, 3), random_sections(2, 2, 3), tail=(3, 4, 2), lag=(0, 2))
+    check("arrival_bands", "impulse_flat", tag, form, plan, n_steps, query)
 
 
 def _random_factors(shape):
@@ -119,21 +84,22 @@ def test_boxes_bands_and_sections_on_a_room_with_walls(name, K, S, lag, with_map
     """tests/golden/cases.py "random": 24 x 20 x 28, six wall filters, a soft source, noise in the field from the start; every step
     captured, 33 captures (16 + 16 + 1), edges (0, 1, 5, 16, 17) and a tail of three-capture bins from 19 whose last bin goes
     open-ended at 28.  The threshold is the median of the per-node max |p|, or a per-node map of 0.1 .. 10 times it."""
-    got, want, _ = check("random", "f64", "triple", dict(BOXES[name], period=1), EDGES, random_sections(K, S, 10 * K + S), 32, tail=TAIL_W3, lag=lag,
-                         map_factors=_random_factors if with_map else None, spread=name != "one-node")
+    plan = bands_plan("random", dict(BOXES[name], period=1), EDGES, random_sections(K, S, 10 * K + S), tail=TAIL_W3, lag=lag,
+                      map_factors=_random_factors if with_map else None)
+    want = check("arrival_bands", "random", "f64", "triple", plan, 32, **(dict(condition=None) if name == "one-node" else {}))[1]
     if name != "one-node":
         assert (want["bins"][:, -1].reshape(K, -1).max(axis=1) > 0).any()       # the open-ended bin took something
 
 
 @pytest.mark.parametrize("tail", [None, (3, 20, 7), (20, 18, 1)], ids=["no-tail", "tail-inside-a-fold", "a-bin-per-capture"])
 def test_tails(tail):
-    check("random", "f32", "pair", dict(BOXES["sub-box-567-odd"], period=1), EDGES, random_sections(2, 3, 9), 32, tail=tail, lag=(0, 2))
+    check("arrival_bands", "random", "f32", "pair", bands_plan("random", dict(BOXES["sub-box-567-odd"], period=1), EDGES, random_sections(2, 3, 9), tail=tail, lag=(0, 2)), 32)
 
 
 def test_a_node_without_an_onset_keeps_everything_in_pre():
     """A threshold above every |p|: no onset, no bin, no moment; pre holds every band's whole energy and the peak is still found."""
-    got, want, snaps = check("random", "f64", "single", dict(BOXES["sub-box-630"], period=1), EDGES, random_sections(2, 1, 4), 20, tail=TAIL_W3,
-                             threshold=1e30, spread=False)
+    plan = bands_plan("random", dict(BOXES["sub-box-630"], period=1), EDGES, random_sections(2, 1, 4), tail=TAIL_W3, threshold=float(np.float32(1e30)))
+    got, _, _, snaps, _ = check("arrival_bands", "random", "f64", "single", plan, 20, condition=None)
     assert (got["onset"] == A.NONE).all() and not got["bins"].any() and not got["moment"].any() and (got["pre"] > 0).all()
     assert got["peak"].tobytes() == np.abs(snaps).max(axis=0).tobytes()
 
@@ -143,7 +109,7 @@ def test_identity_sections_reproduce_the_arrival_plan_on_the_device():
     plan = dict(BOXES["sub-box-567-odd"], period=1)
     snaps, _ = reference_snapshots("random", "f64", "pair", plan, 32)
     thr = threshold_of(snaps)
-    got, want, _ = check("random", "f64", "pair", plan, EDGES, IDENTITY, 32)
+    got = check("arrival_bands", "random", "f64", "pair", bands_plan("random", plan, EDGES, IDENTITY), 32)[0]
     set_tuning(**FORMS["pair"])
     eng = make_engine(cases.CASES["random"](), "f64")
     try:
@@ -165,7 +131,7 @@ def test_threshold_zero_reproduces_the_banded_decay_plan_on_the_device(w, n_bins
     n_bins = n, bytewise -- the merged fold and the new one on the same captures, with the reference's Butterworth octave bands."""
     plan = dict(BOXES["sub-box-567-odd"], period=1)
     sections = np.array([D.butterworth_bandpass(lo, hi, 8000.0) for lo, hi in D.octave_band_edges([250.0, 500.0, 1000.0])])
-    got, want, _ = check("random", "f64", "pair", plan, (0,), sections, 32, tail=(n_bins - 1, w, w), threshold=0.0, spread=False)
+    got = check("arrival_bands", "random", "f64", "pair", bands_plan("random", plan, (0,), sections, tail=(n_bins - 1, w, w), threshold=0.0), 32, condition=None)[0]
     set_tuning(**FORMS["pair"])
     eng = make_engine(cases.CASES["random"](), "f64")
     try:
@@ -176,151 +142,6 @@ def test_threshold_zero_reproduces_the_banded_decay_plan_on_the_device(w, n_bins
         eng.close()
     assert captures == 33 and got["bins"].tobytes() == bins.tobytes() and bins.max() > 0
     assert (got["onset"] == 0).all() and not got["pre"].any()
-
-
-def test_fetching_mid_run_and_at_the_end():
-    """A fetch after 14 captures folds t = 14 < 16; the states it leaves carry the next 17 captures."""
-    plan = dict(BOXES["sub-box-630"], period=1)
-    sections = random_sections(3, 4, 2)
-    args = dict(tail=TAIL_W3, lag=(0, 2, 20))
-    snaps, steps = reference_snapshots("random", "f64", "pair", plan, 30)
-    thr = threshold_of(snaps)
-    eng, _ = bands_engine("random", "f64", "pair", plan, EDGES, sections, thr, **args)
-    try:
-        assert eng.run_steps(13) == (13, 0)
-        mid, mid_count = eng.fetch_arrival_bands()
-        again, again_count = eng.fetch_arrival_bands()
-        assert eng.run_steps(17) == (17, 0)
-        end, end_count = eng.fetch_arrival_bands()
-    finally:
-        eng.close()
-    assert (mid_count, again_count, end_count) == (14, 14, 31)
-    same(mid, A.banded_arrival_fold(snaps[:14], thr, EDGES, sections, **args))
-    same(again, mid)
-    want = A.banded_arrival_fold(snaps, thr, EDGES, sections, **args)
-    same(end, want)
-    assert ((want["onset"] >= 14) & (want["onset"] != A.NONE)).any() and (want["onset"] < 14).any()      # onsets on both sides of the fetch
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-def test_checkpoint_run_rollback_rerun_gives_the_same_state_twice(form):
-    """The impulse room's plane: the wavefront is crossing it at the checkpoint, so some onsets lie before it and some behind.  The
-    checkpoint holds sums AND filter states: the re-run's captures are filtered from the state capture 10 left."""
-    plan = dict(PLANE, period=1)
-    edges, sections, args = (0, 2, 6), random_sections(2, 3, 8), dict(tail=(3, 8, 2), lag=(0, 2))
-    snaps, steps = reference_snapshots("impulse_flat", "f64", form, plan, 27)
-    thr = threshold_of(snaps)
-    want = A.banded_arrival_fold(snaps, thr, edges, sections, **args)
-    heard = want["onset"] != A.NONE
-    assert (want["onset"][heard] <= 10).any() and (want["onset"][heard] > 10).any()
-    golden = json.load(open(GOLDEN))
-    eng, _ = bands_engine("impulse_flat", "f64", form, plan, edges, sections, thr, **args)
-    try:
-        assert eng.run_steps(10) == (10, 0)            # captures of 0 .. 10
-        eng.checkpoint()
-        assert eng.run_steps(17) == (17, 0)
-        first, first_count = eng.fetch_arrival_bands()
-        eng.rollback()
-        assert eng.step_count() == 10 and eng.arrival_bands_count() == (11, 10)
-        kept, kept_count = eng.fetch_arrival_bands()
-        assert eng.run_steps(17) == (17, 0)
-        second, second_count = eng.fetch_arrival_bands()
-        assert eng.arrival_bands_count() == (28, 27)
-        eng.set_arrival_bands(edges, sections, thr, **dict(args, **plan))      # a plan set after the checkpoint has no state to go back to
-        assert refusal(lambda e: e.rollback(), eng) == golden["rollback"]
-    finally:
-        eng.close()
-    assert (first_count, kept_count, second_count) == (28, 11, 28)
-    same(kept, A.banded_arrival_fold(snaps[:11], thr, edges, sections, **args))
-    same(first, want)
-    same(second, want)
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-@pytest.mark.parametrize("bad_step", [12, 13, 14])
-def test_a_run_that_stops_on_a_flag_holds_nothing_of_a_later_step(form, bad_step):
-    """inf in the source signal at step f, a capture every 4 steps: sums and onsets hold the captures of 0, 4, 8, 12 and nothing of 16,
-    whose field (inf / nan) the batch had already produced when the flag was read.  Neither do the filter states: both engines get
-    clean fields and run on, and the continued run's outputs are the twin's continued from the state capture 12 left -- finite."""
-    set_tuning(**FORMS[form])
-    mesh = M.box_mesh(12, 12, 12)
-    sig = np.zeros(40)
-    sig[0] = 1.0
-    sig[bad_step] = np.inf
-    case = dict(mesh=mesh, init=None, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig,
-                recv=[mesh.compute_index(7, 6, 6)])
-    plan = dict(box=((0, 0, 6), (None, None, 1)), period=4)
-    sections, args = random_sections(2, 3, 12), dict(tail=(2, 2, 2), lag=(0, 1))
-    engines = [make_engine(case, "f64", plan), make_engine(case, "f64")]
-    try:
-        engines[1].set_arrival_bands((0, 1), sections, 1e-3, **dict(args, **plan))
-        memories = [engines[0].read_boundary_data(d) for d in (1, 2, 3)]
-        for eng in engines:
-            done, flag = eng.run_steps(40)
-            assert done == bad_step and flag & M.ERR_INF
-        snaps, steps = engines[0].fetch_snapshots()
-        assert list(steps) == [0, 4, 8, 12] and engines[1].arrival_bands_count() == (4, 12)
-        got, count = engines[1].fetch_arrival_bands()
-        want, state = A.banded_arrival_fold(snaps, np.float32(1e-3), (0, 1), sections, return_state=True, **args)
-        assert count == 4 and np.isfinite(got["bins"]).all() and np.isfinite(got["peak"]).all() and (want["onset"] != A.NONE).any()
-        same(got, want)
-        rng = np.random.default_rng(7)
-        fields = [rng.uniform(-1, 1, mesh.num_nodes) * (mesh.nodes["boundary_type"] & M.ID_INSIDE != 0) for _ in range(2)]
-        sig = np.zeros(16)
-        sig[1] = 0.5
-        for eng in engines:
-            eng.write_field(fields[0], E.BUF_PREVIOUS)
-            eng.write_field(fields[1], E.BUF_CURRENT)
-            for d, clean in zip((1, 2, 3), memories):
-                eng.write_boundary_data(d, clean)
-            eng.set_source(E.SOURCE_HARD, mesh.compute_index(6, 6, 6), sig)
-            assert eng.run_steps(8) == (8, 0)
-        snaps, steps = engines[0].fetch_snapshots()
-        assert list(steps) == [0, 4, 8, 12, 16, 20] and engines[1].arrival_bands_count() == (6, 20)
-        got, count = engines[1].fetch_arrival_bands()
-    finally:
-        for eng in engines:
-            eng.close()
-    continued = A.banded_arrival_fold(snaps[4:], np.float32(1e-3), (0, 1), sections, state=state, first_capture=4, **args)
-    assert np.isfinite(got["bins"]).all() and np.isfinite(got["moment"]).all() and (continued["bins"][:, -1] > 0).any()
-    same(got, continued)
-
-
-def test_generic_steps_in_between_capture_nothing():
-    set_tuning(**FORMS["pair"])
-    case = cases.CASES["random"]()
-    plan = dict(box=((0, 0, 0), (None, None, 2)), period=3)
-    sections, args = random_sections(2, 2, 5), dict(tail=(2, 2, 1), lag=(0, 1))
-    engines = [make_engine(case, "f32"), make_engine(case, "f32")]
-    golden = json.load(open(GOLDEN))
-    try:
-        for e in engines:
-            assert e.run_steps(9) == (9, 0)
-        engines[0].set_arrival_bands((0, 1), sections, 0.2, **dict(args, **plan))       # steps 0, 3, 6 lie before the plan
-        engines[1].set_snapshots(**plan)
-        assert engines[0].arrival_bands_count() == (0, 0)
-        for e in engines:
-            assert e.run_steps(4) == (4, 0)               # 9 (at the start of this run), 12
-            for _ in range(3):                            # 13 -> 16 by generic steps: 15 is passed
-                assert e.step() == 0
-                e.swap()
-        assert engines[0].arrival_bands_count() == (2, 12)
-        for e in engines:
-            assert e.run_steps(2) == (2, 0)               # 18
-        got, count = engines[0].fetch_arrival_bands()
-        snaps, steps = engines[1].fetch_snapshots()
-        assert list(steps) == [9, 12, 18] and count == 3
-        want = A.banded_arrival_fold(snaps, np.float32(0.2), (0, 1), sections, **args)
-        same(got, want)
-        assert (want["onset"] != A.NONE).any() and (want["onset"] == A.NONE).any()
-        engines[0].set_arrival_bands(None, None)          # stops, forgets and frees ...
-        assert refusal(lambda e: e.arrival_bands_count(), engines[0]) == golden["no_plan"]["arrival_bands_count"]
-        assert refusal(lambda e: e.fetch_arrival_bands(), engines[0]) == golden["no_plan"]["fetch_arrival_bands"]
-        engines[0].set_decay(2, 2, **plan)                # ... and a decay plan takes its place
-        assert engines[0].run_steps(3) == (3, 0) and engines[0].decay_count() == (2, 21)
-    finally:
-        for e in engines:
-            e.close()
 
 
 # ---- refusals: code and text against tests/golden/arrival_bands_refusals.json, written by hand from the contract ----------------
@@ -442,48 +263,20 @@ def test_the_plans_exclude_each_other_both_ways():
         group.close()
 
 
-@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("form", FILE_FORMS["arrival_bands"])
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_a_plan_changes_nothing_the_run_computes(form, tag):
-    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise."""
-    set_tuning(**FORMS[form])
-    case = cases.CASES["random"]()
-    out = []
-    for plan in (None, dict(box="mesh", stride=(1, 2, 1), period=7, first_step=3)):
-        eng = make_engine(case, tag)
-        try:
-            if plan:
-                eng.set_arrival_bands((0, 2, 4), random_sections(3, 4, 1), 0.3, tail=(2, 5, 1), lag=(0, 1, 2), **plan)
-            assert eng.run_steps(case["steps"]) == (case["steps"], 0)
-            out.append([eng.fetch_receivers(0, case["steps"]), eng.read_field(E.BUF_CURRENT), eng.read_field(E.BUF_PREVIOUS)] +
-                       [eng.read_boundary_data(d) for d in (1, 2, 3)])
-            if plan:
-                assert eng.arrival_bands_count() == (9, 59)   # steps 3, 10, ..., 59
-        finally:
-            eng.close()
-    for a, b in zip(*out):
-        assert a.tobytes() == b.tobytes()
-    assert np.abs(out[0][0]).max() > 0
-
-
-def test_kernel_timing_accounts_for_the_fold_kernels():
-    eng, _ = bands_engine("impulse_flat", "f64", "single", dict(box="mesh", period=1), (0, 4, 8), random_sections(2, 4, 1), 1e-6, tail=(4, 12, 4))
-    try:
-        eng.enable_kernel_timing(True)
-        assert eng.run_steps(40) == (40, 0)
-        eng.fetch_arrival_bands()
-        assert eng.query(E.Engine.QUERY_ARRIVAL_BANDS_FOLDS) == 3 and eng.query(E.Engine.QUERY_ARRIVAL_BANDS_NS) > 0
-    finally:
-        eng.close()
+    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise:
+    plan_cases.changes_nothing, in the forms this file always named."""
+    changes_nothing("arrival_bands", tag, form)
 
 
 def test_canonical_returns_the_band_maps_beside_the_receiver_output():
     """simulation.canonical(..., arrival=dict(bands=...)): the records are those of a run without a plan, the state is the
     engine-level one, folded from canonical's own snapshots of the same plane and cadence with the sections, edges, tail and lags
     arrival_bands_plan_arguments names."""
-    from test_gpu_decay import _box_scene
     set_tuning()
-    W, vm, source, receiver = _box_scene()
+    W, vm, source, receiver = box_scene()
     env = W.Environment()
     rate = W.compute_sample_rate(vm.mesh.spacing, env.speed_of_sound)
     seconds = 39.5 / rate      # 40 steps

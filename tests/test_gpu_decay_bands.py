@@ -12,9 +12,10 @@ import numpy as np
 import pytest
 
 import cases
-from helpers import set_tuning
-from test_gpu_decay import BOXES, LAYOUTS, numpy_bins, reference_snapshots
-from test_gpu_snapshots import FORMS, make_engine
+from helpers import numpy_bins, set_tuning
+from plan_cases import (BOXES, FILE_COUNTS, FILE_FORMS, FORMS, LAYOUTS, STATE_FORM_CASES, box_scene, capture_counts, changes_nothing,
+                        check, default_tuning_afterwards, make_engine, plan_on, reference_snapshots, sections)
+from plan_cases import every_band as not_zeros
 from wayverb_amd import decay as D
 from wayverb_amd import engine as E
 from wayverb_amd import mesh as M
@@ -29,74 +30,22 @@ IDENTITY = np.array([[[1.0, 0.0, 0.0, 0.0, 0.0]]])
 @pytest.fixture(autouse=True)
 def _default_tuning_afterwards(built_library):
     yield
-    set_tuning()
+    default_tuning_afterwards()
 
 
-_sections = {}
+def banded_plan(case, cadence, bands, n_bins, bin_captures):
+    return plan_on(case, "banded", bands=bands, n_bins=n_bins, bin_captures=bin_captures, **cadence)
 
 
-def sections(k_bands, n_sections):
-    """K octave bands from 0.2 cycles per capture downwards, the first S sections of the 4th-order Butterworth band-pass (S = 1: the
-    reference's single band-pass biquad).  Designed once, read only."""
-    key = (k_bands, n_sections)
-    if key not in _sections:
-        edges = D.octave_band_edges([0.2 / 2 ** k for k in range(k_bands)])
-        if n_sections == 1:
-            s = np.stack([D.bandpass_biquad(lo, hi, 1.0) for lo, hi in edges])
-        else:
-            s = np.stack([D.butterworth_bandpass(lo, hi, 1.0)[4 - n_sections:] for lo, hi in edges])
-        s.setflags(write=False)
-        _sections[key] = s
-    return _sections[key]
-
-
-def not_zeros(bins):
-    """every band of [K, n_bins, ...] holds something"""
-    return bool((bins.reshape(bins.shape[0], -1).max(axis=1) > 0).all())
-
-
-def bands_engine(case_name, tag, form, plan, bands, n_bins, bin_captures):
-    set_tuning(**FORMS[form])
-    eng = make_engine(cases.CASES[case_name](), tag)
-    shape = eng.set_decay(n_bins, bin_captures, bands=bands, **plan)
-    return eng, shape
-
-
-def check(case_name, tag, form, plan, bands, n_bins, bin_captures, n_steps, query=None):
-    snaps, steps = reference_snapshots(case_name, tag, form, plan, n_steps)
-    want = D.banded_bins(snaps, bands, n_bins, bin_captures)
-    eng, shape = bands_engine(case_name, tag, form, plan, bands, n_bins, bin_captures)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.decay_count() == (len(steps), int(steps[-1]))
-        got, captures = eng.fetch_decay()
-        if query is not None:
-            assert eng.query(query) > 0
-        assert eng.query(E.Engine.QUERY_DECAY_CAPTURES) == len(steps)
-        folds = eng.query(E.Engine.QUERY_DECAY_FOLDS)
-    finally:
-        eng.close()
-    assert captures == len(steps) and len(steps) > 1
-    assert got.shape == shape == want.shape == (bands.shape[0], n_bins) + snaps.shape[1:] and got.dtype == np.float64
-    assert folds <= -(-len(steps) // 16) + 1
-    assert got.tobytes() == want.tobytes(), "largest difference %g" % np.abs(got - want).max()
-    assert not_zeros(want) and np.abs(snaps[-1]).max() > 0
-    return got, snaps
-
-
-FORM_CASES = [("single", 1, None), ("single", 7, None), ("graph", 1, None), ("graph", 3, None),
-              ("pair", 1, None), ("pair", 3, E.Engine.QUERY_PASSES), ("pair", 7, E.Engine.QUERY_PASSES),
-              ("triple", 1, None), ("triple", 3, E.Engine.QUERY_TRIPLE_PASSES), ("triple", 7, E.Engine.QUERY_TRIPLE_PASSES)]
-
-
-@pytest.mark.parametrize("form,period,query", FORM_CASES, ids=["%s-every%d" % c[:2] for c in FORM_CASES])
+@pytest.mark.parametrize("form,period,query", STATE_FORM_CASES, ids=["%s-every%d" % c[:2] for c in STATE_FORM_CASES])
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_every_stepping_form_gives_the_banded_bins_of_the_snapshots(form, period, query, tag):
     """Single steps, graph replay, two- and three-step passes; period 1 (every step ends a pass), 3 (three-step passes stay whole) and 7;
     one plane of the 32^3 impulse room, three bands of four sections, four captures per bin."""
     n_steps = 64 if form == "graph" else 30
     captures = n_steps // period + 1
-    check("impulse_flat", tag, form, dict(box=((0, 0, 15), (None, None, 1)), period=period), sections(3, 4), -(-captures // 4), 4, n_steps, query)
+    plan = banded_plan("impulse_flat", dict(box=((0, 0, 15), (None, None, 1)), period=period), sections(3, 4), -(-captures // 4), 4)
+    check("banded", "impulse_flat", tag, form, plan, n_steps, query)
 
 
 BAND_BOXES = ["sub-box-630", "sub-box-567-odd", "one-node", "strides-1-2-3"]
@@ -108,33 +57,13 @@ def test_boxes_and_strides_with_the_state_carried_across_two_folds(name, tag):
     """tests/golden/cases.py "random": 24 x 20 x 28, six different wall filters; B = 630 (more than one workgroup), 567 (odd, a tail),
     one node, strides (1, 2, 3); every step captured, 21 captures: 16 in the first fold, 5 in the second, which starts from the state
     the first one stored."""
-    check("random", tag, "triple", dict(BOXES[name], period=1), sections(3, 4), 7, 3, 20)
-
-
-@pytest.mark.parametrize("captures", [1, 16, 17, 33])
-def test_capture_counts_around_the_stage(captures):
-    n_steps = captures - 1
-    plan = dict(box=((3, 2, 4), (10, 9, 7)), period=1)
-    bands = sections(2, 3)
-    eng, _ = bands_engine("random", "f64", "single", plan, bands, 5, 5)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.decay_count() == (captures, n_steps)
-        assert eng.query(E.Engine.QUERY_DECAY_FOLDS) <= (captures - 1) // 16   # (nothing is folded merely because a run ended)
-        got, count = eng.fetch_decay()
-        assert count == captures == eng.query(E.Engine.QUERY_DECAY_CAPTURES)
-        assert eng.query(E.Engine.QUERY_DECAY_FOLDS) <= -(-captures // 16) + 1
-    finally:
-        eng.close()
-    snaps, steps = reference_snapshots("random", "f64", "single", plan, 32)
-    want = D.banded_bins(snaps[:captures], bands, 5, 5)
-    assert got.tobytes() == want.tobytes() and not_zeros(want)
+    check("banded", "random", tag, "triple", banded_plan("random", dict(BOXES[name], period=1), sections(3, 4), 7, 3), 20)
 
 
 @pytest.mark.parametrize("k_bands,n_sections", [(1, 1), (8, 4), (2, 3)])
 @pytest.mark.parametrize("name", ["sub-box-630", "sub-box-567-odd"])
 def test_band_and_section_counts(name, k_bands, n_sections):
-    check("random", "f64", "pair", dict(BOXES[name], period=1), sections(k_bands, n_sections), 7, 5, 32)
+    check("banded", "random", "f64", "pair", banded_plan("random", dict(BOXES[name], period=1), sections(k_bands, n_sections), 7, 5), 32)
 
 
 BAND_LAYOUTS = ["W1-every-capture-a-new-bin", "W5-edges-inside-and-across-folds", "W40-whole-folds-in-one-bin", "one-bin", "open-ended-last-bin"]
@@ -144,7 +73,7 @@ BAND_LAYOUTS = ["W1-every-capture-a-new-bin", "W5-edges-inside-and-across-folds"
 @pytest.mark.parametrize("name", ["sub-box-630", "sub-box-567-odd"])
 def test_bin_layouts_against_the_stage(name, layout):
     n_bins, bin_captures = LAYOUTS[layout]
-    check("random", "f64", "pair", dict(BOXES[name], period=1), sections(2, 3), n_bins, bin_captures, 32)
+    check("banded", "random", "f64", "pair", banded_plan("random", dict(BOXES[name], period=1), sections(2, 3), n_bins, bin_captures), 32)
 
 
 @pytest.mark.parametrize("name", ["sub-box-630", "sub-box-567-odd"])
@@ -152,7 +81,8 @@ def test_the_identity_section_gives_the_plain_plans_bins(name):
     """{1, 0, 0, 0, 0}: out = x * 1 + 0 = x exactly, the states stay +0.0 or -0.0 and add nothing: one band of a banded plan equals a
     plain set_decay engine's bins bytewise (and both the NumPy bins of the snapshots)."""
     plan = dict(BOXES[name], period=1)
-    got, snaps = check("random", "f64", "pair", plan, IDENTITY, 7, 5, 32)
+    got, _, _, snaps, _ = check("banded", "random", "f64", "pair", banded_plan("random", plan, IDENTITY, 7, 5), 32)
+    got = got["bins"]
     set_tuning(**FORMS["pair"])
     eng = make_engine(cases.CASES["random"](), "f64")
     eng.set_decay(7, 5, **plan)
@@ -160,101 +90,6 @@ def test_the_identity_section_gives_the_plain_plans_bins(name):
     plain, _ = eng.fetch_decay()
     eng.close()
     assert got[0].tobytes() == plain.tobytes() == numpy_bins(snaps, 7, 5).tobytes() and plain.max() > 0
-
-
-def test_fetching_mid_run_and_at_the_end():
-    plan = dict(box=((3, 2, 4), (10, 9, 7)), period=1)
-    bands = sections(3, 4)
-    eng, _ = bands_engine("random", "f64", "pair", plan, bands, 6, 5)
-    assert eng.run_steps(13) == (13, 0)
-    mid, mid_count = eng.fetch_decay()
-    again, again_count = eng.fetch_decay()
-    assert eng.run_steps(17) == (17, 0)
-    end, end_count = eng.fetch_decay()
-    eng.close()
-    snaps, steps = reference_snapshots("random", "f64", "pair", plan, 30)
-    assert (mid_count, again_count, end_count) == (14, 14, 31)
-    want_mid, want_end = D.banded_bins(snaps[:14], bands, 6, 5), D.banded_bins(snaps, bands, 6, 5)
-    assert mid.tobytes() == again.tobytes() == want_mid.tobytes() and not_zeros(want_mid)
-    assert end.tobytes() == want_end.tobytes() and not_zeros(want_end)      # (the fetch in between cut a fold in two: same bytes)
-    assert (end[:, :2] == mid[:, :2]).all() and (end[:, 2] >= mid[:, 2]).all()
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-@pytest.mark.parametrize("bad_step", [12, 13, 14])
-def test_a_run_that_stops_on_a_flag_filters_no_capture_of_a_later_step(form, bad_step):
-    """inf in the source signal at step f, a capture every 4 steps: the bins hold the captures of 0, 4, 8, 12; the capture of 16, whose
-    field (inf / nan) the batch had already produced when the flag was read, reached neither a bin nor a filter state -- the continued
-    run's bins are those of the six snapshots in one go, finite."""
-    set_tuning(**FORMS[form])
-    mesh = M.box_mesh(12, 12, 12)
-    sig = np.zeros(40)
-    sig[0] = 1.0
-    sig[bad_step] = np.inf
-    case = dict(mesh=mesh, init=None, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig,
-                recv=[mesh.compute_index(7, 6, 6)])
-    plan = dict(box=((0, 0, 6), (None, None, 1)), period=4)
-    bands = sections(2, 3)
-    engines = [make_engine(case, "f64", plan), make_engine(case, "f64")]
-    engines[1].set_decay(3, 2, bands=bands, **plan)
-    memories = [engines[0].read_boundary_data(d) for d in (1, 2, 3)]
-    for eng in engines:
-        done, flag = eng.run_steps(40)
-        assert done == bad_step and flag & M.ERR_INF
-    snaps, steps = engines[0].fetch_snapshots()
-    assert list(steps) == [0, 4, 8, 12]
-    assert engines[1].decay_count() == (4, 12)
-    got, count = engines[1].fetch_decay()
-    want = D.banded_bins(snaps, bands, 3, 2)
-    assert count == 4 and np.isfinite(got).all() and got.tobytes() == want.tobytes() and not_zeros(want)
-    rng = np.random.default_rng(7)
-    fields = [rng.uniform(-1, 1, mesh.num_nodes) * (mesh.nodes["boundary_type"] & M.ID_INSIDE != 0) for _ in range(2)]
-    sig = np.zeros(16)
-    sig[1] = 0.5
-    for eng in engines:
-        eng.write_field(fields[0], E.BUF_PREVIOUS)
-        eng.write_field(fields[1], E.BUF_CURRENT)
-        for d, clean in zip((1, 2, 3), memories):
-            eng.write_boundary_data(d, clean)
-        eng.set_source(E.SOURCE_HARD, mesh.compute_index(6, 6, 6), sig)
-        assert eng.run_steps(8) == (8, 0)
-    snaps, steps = engines[0].fetch_snapshots()
-    assert list(steps) == [0, 4, 8, 12, 16, 20] and engines[1].decay_count() == (6, 20)
-    got, count = engines[1].fetch_decay()
-    for eng in engines:
-        eng.close()
-    want = D.banded_bins(snaps, bands, 3, 2)
-    assert count == 6 and np.isfinite(got).all() and got[:, 2].max() > 0
-    assert got.tobytes() == want.tobytes() and not_zeros(want)
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-def test_checkpoint_run_rollback_rerun_gives_the_same_bins_twice(form):
-    """The checkpoint holds bins AND filter states: after the rollback the three captures that follow are filtered from the state
-    capture 2 left, not from the one capture 5 left -- the re-run's bins are the first run's, and those of the six snapshots."""
-    plan = dict(box=((2, 3, 4), (12, 11, 9)), stride=(1, 2, 2), period=5)
-    bands = sections(3, 4)
-    eng, _ = bands_engine("random", "f64", form, plan, bands, 3, 2)
-    assert eng.run_steps(10) == (10, 0)            # captures of 0, 5, 10
-    eng.checkpoint()
-    assert eng.run_steps(17) == (17, 0)            # 15, 20, 25
-    first, first_count = eng.fetch_decay()
-    eng.rollback()
-    assert eng.step_count() == 10 and eng.decay_count() == (3, 10)
-    kept, kept_count = eng.fetch_decay()
-    assert eng.run_steps(17) == (17, 0)
-    second, second_count = eng.fetch_decay()
-    assert eng.decay_count() == (6, 25)
-    # a plan set after the checkpoint has neither bins nor states to go back to
-    eng.set_decay(3, 2, bands=bands, **plan)
-    with pytest.raises(E.WaveguideError, match="error -6: .*after the checkpoint"):
-        eng.rollback()
-    eng.close()
-    snaps, steps = reference_snapshots("random", "f64", form, plan, 27)
-    assert (first_count, kept_count, second_count) == (6, 3, 6)
-    want = D.banded_bins(snaps, bands, 3, 2)
-    assert kept.tobytes() == D.banded_bins(snaps[:3], bands, 3, 2).tobytes()
-    assert first.tobytes() == second.tobytes() == want.tobytes() and not_zeros(want)
 
 
 def test_subnormal_floats_and_subnormal_states():
@@ -394,71 +229,26 @@ def test_refusals_leave_an_earlier_plan_intact():
     group.close()
 
 
-@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("captures", FILE_COUNTS["banded"])
+def test_capture_counts_around_the_stage(captures):
+    """One fold per 16 captures and one for the fetch at the most: plan_cases.capture_counts, at the counts this file always named
+    (tests/test_gpu_plan_life_cycle.py has the others)."""
+    capture_counts("banded", captures)
+
+
+@pytest.mark.parametrize("form", FILE_FORMS["banded"])
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_a_banded_plan_changes_nothing_the_run_computes(form, tag):
-    """Receiver traces, final current / previous and the filter memories with a banded plan equal those without one, bytewise."""
-    set_tuning(**FORMS[form])
-    case = cases.CASES["random"]()
-    out = []
-    for plan in (None, dict(box="mesh", stride=(1, 2, 1), period=7, first_step=3)):
-        eng = make_engine(case, tag)
-        if plan:
-            eng.set_decay(4, 2, bands=sections(3, 4), **plan)
-        done, flag = eng.run_steps(case["steps"])
-        assert (done, flag) == (case["steps"], 0)
-        out.append([eng.fetch_receivers(0, case["steps"]), eng.read_field(E.BUF_CURRENT), eng.read_field(E.BUF_PREVIOUS)] +
-                   [eng.read_boundary_data(d) for d in (1, 2, 3)])
-        if plan:
-            assert eng.decay_count() == (9, 59)   # steps 3, 10, ..., 59
-            assert not_zeros(eng.fetch_decay()[0])
-        eng.close()
-    for a, b in zip(*out):
-        assert a.tobytes() == b.tobytes()
-    assert np.abs(out[0][0]).max() > 0
-
-
-def test_generic_steps_in_between_are_gaps_in_the_series():
-    """wv_step / wv_swap capture nothing: the filters see the captures that were taken, back to back."""
-    set_tuning(**FORMS["pair"])
-    case = cases.CASES["random"]()
-    plan = dict(box=((0, 0, 0), (None, None, 2)), period=3)
-    bands = sections(2, 3)
-    engines = [make_engine(case, "f32"), make_engine(case, "f32")]
-    for e in engines:
-        assert e.run_steps(9) == (9, 0)
-    engines[0].set_decay(2, 2, bands=bands, **plan)
-    engines[1].set_snapshots(**plan)
-    for e in engines:
-        assert e.run_steps(4) == (4, 0)               # 9 (at the start of this run), 12
-        for _ in range(3):                            # 13 -> 16 by generic steps: 15 is passed
-            assert e.step() == 0
-            e.swap()
-        assert e.run_steps(2) == (2, 0)               # 18
-    got, count = engines[0].fetch_decay()
-    snaps, steps = engines[1].fetch_snapshots()
-    for e in engines:
-        e.close()
-    want = D.banded_bins(snaps, bands, 2, 2)
-    assert list(steps) == [9, 12, 18] and count == 3
-    assert got.tobytes() == want.tobytes() and not_zeros(want)
-
-
-def test_kernel_timing_accounts_for_the_banded_fold_kernels():
-    eng, _ = bands_engine("impulse_flat", "f64", "single", dict(box="mesh", period=1), sections(3, 4), 3, 8)
-    eng.enable_kernel_timing(True)
-    assert eng.run_steps(20) == (20, 0)
-    eng.fetch_decay()
-    assert eng.query(E.Engine.QUERY_DECAY_FOLDS) == 2 and eng.query(E.Engine.QUERY_DECAY_NS) > 0
-    eng.close()
+    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise:
+    plan_cases.changes_nothing, in the forms this file always named."""
+    changes_nothing("banded", tag, form)
 
 
 def test_canonical_designs_the_bands_at_the_rate_of_the_captured_series():
     """simulation.canonical(..., decay=dict(..., bands=[(lo_hz, hi_hz), ...])): the bins are the engine-level ones -- banded_bins over
     canonical's own snapshots of the same box and cadence with butterworth_bandpass(lo, hi, sample_rate / period)."""
     set_tuning()
-    from test_gpu_decay import _box_scene
-    W, vm, source, receiver = _box_scene()
+    W, vm, source, receiver = box_scene()
     env = W.Environment()
     rate = W.compute_sample_rate(vm.mesh.spacing, env.speed_of_sound)
     seconds = 39.5 / rate      # 40 steps

@@ -17,9 +17,9 @@ import interaural_twin as T
 import plan_argument_faults as F
 import plan_twin as P
 from helpers import set_tuning
-from test_gpu_decay import _box_scene, reference_snapshots
+from plan_cases import (ALL_FORMS, FILE_COUNTS, FILE_FORMS, box_scene, capture_counts, changes_nothing, check, default_tuning_afterwards, ear_level,
+                        ear_map, ears_on_the_mesh, levels, make_engine, plan_on, reference_snapshots)
 from test_gpu_plan_refusals import BANDS, SET, STOP, refusal
-from test_gpu_snapshots import FORMS, make_engine
 from wayverb_amd import decay as D
 from wayverb_amd import engine as E
 from wayverb_amd import interaural as IA
@@ -30,7 +30,6 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-ALL_FORMS = dict(FORMS, whole=dict(pair=0, triple=0, whole_step=1))     # (one launch per step)
 SECTIONS = D.butterworth_bandpass(500.0, 2000.0, 8000.0)                # four sections; [:1] is a cascade of one
 EDGES = {1: [0], 4: [0, 3, 8, 20]}
 SEAT = dict(box=((3, 2, 4), (10, 9, 7)), ear_a=(0, -2, 0), ear_b=(0, 2, 0))      # B = 630 on the 24 x 20 x 28 room
@@ -39,7 +38,7 @@ SEAT = dict(box=((3, 2, 4), (10, 9, 7)), ear_a=(0, -2, 0), ear_b=(0, 2, 0))     
 @pytest.fixture(autouse=True)
 def _default_tuning_afterwards(built_library):
     yield
-    set_tuning()
+    default_tuning_afterwards()
 
 
 def ear_planes(snaps, dims, box, stride, ear):
@@ -62,49 +61,26 @@ def reference(case_name, tag, form, n_steps, period, box, ear_a, ear_b, stride=1
     return ear_planes(snaps, dims, box, stride, ear_a), ear_planes(snaps, dims, box, stride, ear_b), steps
 
 
-def levels(a, b):
-    """Thresholds made of the INPUT: a scalar half the nodes reach early, and a map that puts every node's onset at a capture of its
-    own -- and every seventh node's nowhere."""
-    mag = np.fmax(np.abs(a), np.abs(b))
-    rng = np.random.default_rng(a.shape[0])
-    order = np.sort(mag.reshape(mag.shape[0], -1), axis=0)
-    pick = rng.integers(0, mag.shape[0], order.shape[1])
-    tmap = order[pick, np.arange(order.shape[1])].astype(np.float32)
-    tmap[3::7] = np.float32(3e38)
-    return float(np.median(mag.max(axis=0))) * 0.5, tmap.reshape(mag.shape[1:])
+THRESHOLDS = dict(zero=dict(threshold=0.0), scalar=dict(threshold=ear_level), map=dict(threshold=0.0, threshold_map=ear_map))
+
+
+def check_seats(case_name, tag, form, n_steps, period, box, ear_a, ear_b, L, edges, sections, threshold="scalar", stride=1, query=None):
+    """The shared check of an interaural plan whose threshold is made of the input (plan_cases.levels), and what this kind adds: both
+    ears hear something at the end, and a map leaves a node that never reaches its threshold."""
+    plan = plan_on(case_name, "interaural", box=box, stride=stride, period=period, edges=list(edges), ear_a=tuple(ear_a), ear_b=tuple(ear_b), max_lag=L,
+                   sections=sections, **THRESHOLDS[threshold])
+    got, want, plan, snaps, _ = check("interaural", case_name, tag, form, plan, n_steps, query)
+    a, b = ears_on_the_mesh(plan, snaps)
+    assert np.abs(a[-1]).max() > 0 and np.abs(b[-1]).max() > 0
+    if threshold == "map" and a[0].size > 8:
+        assert (got["onset"] == IA.NONE).any() and (got["onset"] != IA.NONE).any()       # a node that never reaches its threshold
+    return got, want
 
 
 def same(got, want, what=""):
     for key in ("onset", "pre", "bins"):
         assert got[key].shape == want[key].shape and got[key].dtype == want[key].dtype, (what, key)
         assert got[key].tobytes() == np.ascontiguousarray(want[key]).tobytes(), (what, key)
-
-
-def check(case_name, tag, form, n_steps, period, box, ear_a, ear_b, L, edges, sections, threshold="scalar", stride=1, query=None):
-    a, b, steps = reference(case_name, tag, form, n_steps, period, box, ear_a, ear_b, stride)
-    scalar, tmap = levels(a, b)
-    thr = dict(zero=0.0, scalar=scalar, map=tmap)[threshold]
-    want = IA.interaural_fold(a, b, thr, edges, L, sections)
-    set_tuning(**ALL_FORMS[form])
-    eng = make_engine(cases.CASES[case_name](), tag)
-    try:
-        shape = eng.set_interaural(edges, ear_a, ear_b, L, 0.0 if threshold == "map" else thr, sections, box=box, stride=stride, period=period,
-                                   threshold_map=tmap if threshold == "map" else None)
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.interaural_count() == (len(steps), int(steps[-1]))
-        got, captures = eng.fetch_interaural()
-        if query is not None:
-            assert eng.query(query) > 0
-        assert eng.query(E.Engine.QUERY_INTERAURAL_CAPTURES) == len(steps)
-        assert eng.query(E.Engine.QUERY_INTERAURAL_FOLDS) <= -(-len(steps) // 16) + 1
-    finally:
-        eng.close()
-    assert captures == len(steps) and shape == (len(edges), 2 * L + 3) + a.shape[1:] == got["bins"].shape
-    same(got, want, (tag, form, L, len(edges), threshold))
-    assert np.abs(got["bins"]).max() > 0 and np.abs(a[-1]).max() > 0 and np.abs(b[-1]).max() > 0
-    if threshold == "map" and a[0].size > 8:
-        assert (got["onset"] == IA.NONE).any() and (got["onset"] != IA.NONE).any()       # a node that never reaches its threshold
-    return got, want
 
 
 GRID = [(L, n_bins, S) for L in (0, 1, 5, 16) for n_bins in (1, 4) for S in (0, 1, 4)]
@@ -115,14 +91,14 @@ def test_lags_bins_and_sections_against_the_definition(L, n_bins, S):
     """Every lag class, one and four bins, no filter, one section and four; 33 captures (two full stages and one for the fetch: the
     history carried across folds, bin edges inside and between folds); fp32 and fp64 and the three kinds of threshold in turn."""
     k = GRID.index((L, n_bins, S))
-    check("random", ("f32", "f64")[k % 2], "pair", 32, 1, SEAT["box"], SEAT["ear_a"], SEAT["ear_b"], L, EDGES[n_bins], SECTIONS[:S] if S else None,
+    check_seats("random", ("f32", "f64")[k % 2], "pair", 32, 1, SEAT["box"], SEAT["ear_a"], SEAT["ear_b"], L, EDGES[n_bins], SECTIONS[:S] if S else None,
           ("zero", "scalar", "map")[k % 3])
 
 
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 @pytest.mark.parametrize("threshold", ["zero", "scalar", "map"])
 def test_thresholds_in_both_precisions(tag, threshold):
-    check("random", tag, "triple", 32, 1, SEAT["box"], SEAT["ear_a"], SEAT["ear_b"], 5, EDGES[4], SECTIONS[:2], threshold)
+    check_seats("random", tag, "triple", 32, 1, SEAT["box"], SEAT["ear_a"], SEAT["ear_b"], 5, EDGES[4], SECTIONS[:2], threshold)
 
 
 PLACES = {
@@ -140,59 +116,12 @@ PLACES = {
 def test_boxes_strides_and_ear_offsets_on_a_room_with_walls(name, tag):
     """tests/golden/cases.py "random": 24 x 20 x 28, six different wall filters, a soft source; 21 captures."""
     place = PLACES[name]
-    got, _ = check("random", tag, "triple", 20, 1, place["box"], place["ear_a"], place["ear_b"], 5, EDGES[4], SECTIONS[:1], "map", place.get("stride", 1))
+    got, _ = check_seats("random", tag, "triple", 20, 1, place["box"], place["ear_a"], place["ear_b"], 5, EDGES[4], SECTIONS[:1], "map", place.get("stride", 1))
     if name == "equal-ears":                 # the autocorrelation form: symmetric in the lag, and the energies are C[0]
         bins = got["bins"]
         assert bins[:, 0].tobytes() == bins[:, 1].tobytes() == bins[:, 2 + 5].tobytes()
         for l in range(1, 6):
             assert bins[:, 2 + 5 + l].tobytes() == bins[:, 2 + 5 - l].tobytes()
-
-
-@pytest.mark.parametrize("captures", [1, 15, 16, 17, 33])
-def test_capture_counts_around_the_stage(captures):
-    """Runs that take exactly 1, 15, 16, 17 and 33 captures: a fold of one capture, a full stage, a history carried across folds."""
-    n_steps = captures - 1
-    a, b, steps = reference("random", "f64", "single", 32, 1, SEAT["box"], SEAT["ear_a"], SEAT["ear_b"])
-    scalar, _ = levels(a, b)
-    set_tuning(**ALL_FORMS["single"])
-    eng = make_engine(cases.CASES["random"](), "f64")
-    try:
-        eng.set_interaural(EDGES[4], SEAT["ear_a"], SEAT["ear_b"], 7, scalar, SECTIONS[:2], box=SEAT["box"])
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.interaural_count() == (captures, n_steps)
-        assert eng.query(E.Engine.QUERY_INTERAURAL_FOLDS) <= (captures - 1) // 16   # (nothing is folded merely because a run ended)
-        got, count = eng.fetch_interaural()
-        assert count == captures == eng.query(E.Engine.QUERY_INTERAURAL_CAPTURES)
-    finally:
-        eng.close()
-    same(got, IA.interaural_fold(a[:captures], b[:captures], scalar, EDGES[4], 7, SECTIONS[:2]), captures)
-    assert np.abs(got["pre"]).max() > 0 or np.abs(got["bins"]).max() > 0
-
-
-def test_calls_of_one_seven_and_thirty_steps_and_a_fetch_mid_run_give_the_same_bytes():
-    a, b, steps = reference("random", "f32", "pair", 30, 1, SEAT["box"], SEAT["ear_a"], SEAT["ear_b"])
-    scalar, tmap = levels(a, b)
-    want = IA.interaural_fold(a, b, tmap, EDGES[4], 16, SECTIONS)
-    for call in (1, 7, 30):
-        set_tuning(**ALL_FORMS["pair"])
-        eng = make_engine(cases.CASES["random"](), "f32")
-        try:
-            eng.set_interaural(EDGES[4], SEAT["ear_a"], SEAT["ear_b"], 16, 0.0, SECTIONS, box=SEAT["box"], threshold_map=tmap)
-            done = 0
-            while done < 30:
-                n = min(call, 30 - done)
-                assert eng.run_steps(n) == (n, 0)
-                done += n
-                if call == 7 and done == 14:      # (a fold of 15 captures, then 15 more: the ring of 16 slots wraps inside the second)
-                    mid, mid_count = eng.fetch_interaural()
-                    assert mid_count == 15
-                    same(mid, IA.interaural_fold(a[:15], b[:15], tmap, EDGES[4], 16, SECTIONS), "mid")
-            got, count = eng.fetch_interaural()
-        finally:
-            eng.close()
-        assert count == 31
-        same(got, want, call)
-    assert np.abs(want["bins"]).max() > 0
 
 
 @pytest.mark.parametrize("tag", ["f32", "f64"])
@@ -251,7 +180,7 @@ def test_the_early_iacf_peaks_at_the_travel_time_between_the_ears():
     assert (lags["across"] == 0).all()
 
 
-# ---- the life cycle ---------------------------------------------------------------------------------------------------------------------
+# ---- the stepping forms --------------------------------------------------------------------------------------------------------------------
 
 FORM_CASES = [("single", 1), ("single", 5), ("whole", 1), ("whole", 3), ("graph", 16), ("graph", 1), ("pair", 2), ("pair", 3), ("triple", 3), ("triple", 4), ("triple", 7)]
 
@@ -260,152 +189,13 @@ FORM_CASES = [("single", 1), ("single", 5), ("whole", 1), ("whole", 3), ("graph"
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_every_stepping_form_gives_the_same_bytes(form, period, tag):
     """Single steps, one launch per step, graph replay, two- and three-step passes, periods that do and do not divide 2 and 3: the
-    bytes are those of the definition fed from a snapshot run in the SAME form -- and those of single steps."""
+    bytes are those of the definition fed from a snapshot run in the SAME form (one launch per step: in single steps, the form it is a
+    variant of) -- and those of single steps."""
     n_steps = 64 if form == "graph" and period == 16 else 30
     query = {"pair": E.Engine.QUERY_PASSES, "triple": E.Engine.QUERY_TRIPLE_PASSES}.get(form)
-    got, _ = check("random", tag, form, n_steps, period, SEAT["box"], SEAT["ear_a"], SEAT["ear_b"], 5, EDGES[4], SECTIONS[:1], "zero", query=query)
+    got, _ = check_seats("random", tag, form, n_steps, period, SEAT["box"], SEAT["ear_a"], SEAT["ear_b"], 5, EDGES[4], SECTIONS[:1], "zero", query=query)
     a, b, steps = reference("random", tag, "single", n_steps, period, SEAT["box"], SEAT["ear_a"], SEAT["ear_b"])
     same(got, IA.interaural_fold(a, b, 0.0, EDGES[4], 5, SECTIONS[:1]), (form, period, tag))
-
-
-@pytest.mark.parametrize("form", sorted(ALL_FORMS))
-@pytest.mark.parametrize("tag", ["f32", "f64"])
-def test_a_plan_changes_nothing_the_run_computes(form, tag):
-    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise."""
-    set_tuning(**ALL_FORMS[form])
-    case = cases.CASES["random"]()
-    out = []
-    for plan in (None, dict(box=((0, 2, 0), (None, 16, None)), stride=(1, 2, 1), period=7, first_step=3)):
-        eng = make_engine(case, tag)
-        if plan:
-            eng.set_interaural(EDGES[4], (0, -2, 0), (0, 2, 0), 8, 0.0, SECTIONS[:2], **plan)
-        assert eng.run_steps(case["steps"]) == (case["steps"], 0)
-        out.append([eng.fetch_receivers(0, case["steps"]), eng.read_field(E.BUF_CURRENT), eng.read_field(E.BUF_PREVIOUS)] +
-                   [eng.read_boundary_data(d) for d in (1, 2, 3)])
-        if plan:
-            assert eng.interaural_count() == (9, 59)   # steps 3, 10, ..., 59
-        eng.close()
-    for x, y in zip(*out):
-        assert x.tobytes() == y.tobytes()
-    assert np.abs(out[0][0]).max() > 0
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-@pytest.mark.parametrize("bad_step", [12, 13, 14])
-def test_a_run_that_stops_on_a_flag_folds_no_capture_of_a_later_step(form, bad_step):
-    """inf in the source signal at step f: the run completes f steps; with a capture every 4 steps the state holds those of 0, 4, 8, 12
-    and nothing of 16 (whose field the batch had already produced when the flag was read)."""
-    set_tuning(**ALL_FORMS[form])
-    mesh = M.box_mesh(12, 12, 12)
-    sig = np.zeros(40)
-    sig[0] = 1.0
-    sig[bad_step] = np.inf
-    case = dict(mesh=mesh, init=None, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig, recv=[mesh.compute_index(7, 6, 6)])
-    box = ((0, 2, 6), (None, 8, 1))
-    engines = [make_engine(case, "f64", dict(box="mesh", period=4)), make_engine(case, "f64")]
-    engines[1].set_interaural([0, 2], (0, -2, 0), (0, 2, 0), 3, 1e-6, SECTIONS[:1], box=box, period=4)
-    try:
-        for eng in engines:
-            done, flag = eng.run_steps(40)
-            assert done == bad_step and flag & M.ERR_INF
-        snaps, steps = engines[0].fetch_snapshots()
-        assert list(steps) == [0, 4, 8, 12]
-        assert engines[1].interaural_count() == (4, 12)
-        got, count = engines[1].fetch_interaural()
-    finally:
-        for eng in engines:
-            eng.close()
-    a, b = ear_planes(snaps, mesh.dims, box, 1, (0, -2, 0)), ear_planes(snaps, mesh.dims, box, 1, (0, 2, 0))
-    assert count == 4 and np.isfinite(got["bins"]).all() and np.abs(got["bins"]).max() > 0
-    same(got, IA.interaural_fold(a, b, 1e-6, [0, 2], 3, SECTIONS[:1]), bad_step)
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-def test_checkpoint_run_rollback_rerun_gives_the_same_state_twice(form):
-    plan = dict(box=((2, 3, 4), (12, 11, 9)), stride=(1, 2, 2), period=2)
-    ears = ((-2, 0, 1), (2, 0, -1))
-    set_tuning(**ALL_FORMS[form])
-    eng = make_engine(cases.CASES["random"](), "f64")
-    a, b, steps = reference("random", "f64", form, 44, 2, plan["box"], ears[0], ears[1], plan["stride"])
-    scalar, _ = levels(a, b)
-    args = (EDGES[4], ears[0], ears[1], 6, scalar, SECTIONS[:2])
-    try:
-        eng.set_interaural(*args, **plan)
-        assert eng.run_steps(10) == (10, 0)            # captures of 0 .. 10: 6
-        eng.checkpoint()
-        assert eng.run_steps(34) == (34, 0)            # 12 .. 44: 17 more, a full stage among them
-        first, first_count = eng.fetch_interaural()
-        eng.rollback()
-        assert eng.step_count() == 10 and eng.interaural_count() == (6, 10)
-        kept, kept_count = eng.fetch_interaural()
-        assert eng.run_steps(34) == (34, 0)
-        second, second_count = eng.fetch_interaural()
-        assert eng.interaural_count() == (23, 44)
-        # a plan set after the checkpoint has no state to go back to: a new plan REPLACES the old one and forgets
-        eng.set_interaural(*args, **plan)
-        assert eng.interaural_count() == (0, 0)
-        with pytest.raises(E.WaveguideError, match=r"error -6: wv_rollback: the interaural plan was set after the checkpoint \(its state has no copy to go back to\)"):
-            eng.rollback()
-        empty, empty_count = eng.fetch_interaural()
-        assert empty_count == 0 and not empty["bins"].any() and not empty["pre"].any() and (empty["onset"] == IA.NONE).all()
-        eng.set_interaural(None)                       # stops and forgets
-        with pytest.raises(E.WaveguideError, match="error -6: wv_interaural_count: no interaural plan is set"):
-            eng.interaural_count()
-        with pytest.raises(E.WaveguideError, match="error -6: wv_fetch_interaural: no interaural plan is set"):
-            eng.fetch_interaural()
-        assert eng.run_steps(3) == (3, 0)
-    finally:
-        eng.close()
-    assert (first_count, kept_count, second_count) == (23, 6, 23)
-    same(kept, IA.interaural_fold(a[:6], b[:6], scalar, EDGES[4], 6, SECTIONS[:2]), "kept")
-    same(first, IA.interaural_fold(a, b, scalar, EDGES[4], 6, SECTIONS[:2]), "first")
-    same(second, first, "second")
-    assert np.abs(first["bins"]).max() > 0
-
-
-def test_generic_steps_in_between_capture_nothing():
-    """wv_step / wv_swap capture nothing and the plan steps they pass are passed; a plan set at a non-zero step count captures that
-    very step at the next run."""
-    set_tuning(**ALL_FORMS["pair"])
-    case = cases.CASES["random"]()
-    engines = [make_engine(case, "f32"), make_engine(case, "f32")]
-    try:
-        for e in engines:
-            assert e.run_steps(9) == (9, 0)
-        engines[0].set_interaural([0, 1], SEAT["ear_a"], SEAT["ear_b"], 2, 0.0, None, box=SEAT["box"], period=3)
-        engines[1].set_snapshots(box="mesh", period=3)
-        assert engines[0].interaural_count() == (0, 0)
-        for e in engines:
-            assert e.run_steps(4) == (4, 0)               # 9 (at the start of this run), 12
-            for _ in range(3):                            # 13 -> 16 by generic steps: 15 is passed
-                assert e.step() == 0
-                e.swap()
-        assert engines[0].interaural_count() == (2, 12)
-        for e in engines:
-            assert e.run_steps(2) == (2, 0)               # 18
-        got, count = engines[0].fetch_interaural()
-        snaps, steps = engines[1].fetch_snapshots()
-    finally:
-        for e in engines:
-            e.close()
-    assert list(steps) == [9, 12, 18] and count == 3
-    dims = case["mesh"].dims
-    a, b = ear_planes(snaps, dims, SEAT["box"], 1, SEAT["ear_a"]), ear_planes(snaps, dims, SEAT["box"], 1, SEAT["ear_b"])
-    same(got, IA.interaural_fold(a, b, 0.0, [0, 1], 2), "generic")
-    assert np.abs(got["bins"][1]).max() > 0
-
-
-def test_kernel_timing_accounts_for_the_fold_kernels():
-    set_tuning(**ALL_FORMS["single"])
-    eng = make_engine(cases.CASES["impulse_flat"](), "f64")
-    try:
-        eng.set_interaural([0, 8], (0, -1, 0), (0, 1, 0), 8, 0.0, SECTIONS[:2], box=((0, 1, 15), (None, 30, 1)))
-        eng.enable_kernel_timing(True)
-        assert eng.run_steps(20) == (20, 0)
-        eng.fetch_interaural()
-        assert eng.query(E.Engine.QUERY_INTERAURAL_FOLDS) == 2 and eng.query(E.Engine.QUERY_INTERAURAL_NS) > 0
-    finally:
-        eng.close()
 
 
 # ---- refusals: the 12 x 10 x 9 fp32 box mesh of tests/plan_argument_faults.py, no stepping ------------------------------------------
@@ -594,7 +384,7 @@ MODES = {"default": {}, "three-step-passes": dict(pair=1, triple=1), "single-ste
 _script = {}
 
 
-@pytest.fixture(scope="module")
+@pytest.fixture(scope="module", autouse=True)
 def interaural_family():
     with T.registered():
         yield
@@ -618,11 +408,26 @@ def test_random_plan_sequence(oracle, interaural_family, seed, mode):
 
 # ---- the Python front and the tools -----------------------------------------------------------------------------------------------------
 
+@pytest.mark.parametrize("captures", FILE_COUNTS["interaural"])
+def test_capture_counts_around_the_stage(captures):
+    """One fold per 16 captures and one for the fetch at the most: plan_cases.capture_counts, at the counts this file always named
+    (tests/test_gpu_plan_life_cycle.py has the others)."""
+    capture_counts("interaural", captures)
+
+
+@pytest.mark.parametrize("form", FILE_FORMS["interaural"])
+@pytest.mark.parametrize("tag", ["f32", "f64"])
+def test_a_plan_changes_nothing_the_run_computes(form, tag):
+    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise:
+    plan_cases.changes_nothing, in the forms this file always named."""
+    changes_nothing("interaural", tag, form)
+
+
 def test_canonical_returns_the_maps_beside_the_receiver_output():
     """simulation.canonical(..., interaural=...): the records are those of a run without a plan, the maps are the definition's over
     canonical's own snapshots of the same plane and cadence; a second plan beside it is refused with the engine's message."""
     set_tuning()
-    W, vm, source, receiver = _box_scene()
+    W, vm, source, receiver = box_scene()
     env = W.Environment()
     rate = W.compute_sample_rate(vm.mesh.spacing, env.speed_of_sound)
     seconds = 39.5 / rate      # 40 steps

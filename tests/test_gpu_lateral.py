@@ -13,9 +13,9 @@ import pytest
 
 import cases
 from helpers import set_tuning
-from test_gpu_decay import reference_snapshots
-from test_gpu_intensity import BOXES, constants, hull_of
-from test_gpu_snapshots import FORMS, make_engine
+from plan_cases import HULL_BOXES as BOXES
+from plan_cases import (FILE_COUNTS, FILE_FORMS, FORMS, FORM_QUERIES, box_of, box_scene, capture_counts, changes_nothing, check, constants, default_tuning_afterwards, filled_bins,
+                        hull_of, make_engine, plan_engine, plan_on, quantile_threshold, quarters, reference_snapshots, scaled_map)
 from wayverb_amd import arrival as A
 from wayverb_amd import engine as E
 from wayverb_amd import lateral as L
@@ -30,31 +30,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.fixture(autouse=True)
 def _default_tuning_afterwards(built_library):
     yield
-    set_tuning()
+    default_tuning_afterwards()
+
+
+def quantile(q):
+    return lambda snaps, plan: quantile_threshold(snaps, plan, q)
+
+
+def lateral_plan(case, cadence, edges, threshold, map_factors=None):
+    """`threshold`: a number, or a callable(snaps, plan) of the reference's hull snapshots; `map_factors`: a per-node map of that many times it."""
+    if map_factors is not None:
+        return plan_on(case, "lateral", edges=list(edges), threshold=0.0, threshold_map=scaled_map(threshold, map_factors), **cadence)
+    return plan_on(case, "lateral", edges=list(edges), threshold=threshold, **cadence)
 
 
 def fold(snaps, plan, threshold, edges, **more):
     """The definition over hull snapshots of `plan`'s box, with the constants the engine is given."""
     c = constants(plan)
     return L.lateral_fold(snaps, hull_of(plan)[1], threshold, edges, c["spacing"], c["sample_rate"], c["ambient_density"], **more)
-
-
-def box_of(snaps, plan):
-    """The taken nodes' own snapshots [T][nz][ny][nx] out of the hull's."""
-    return np.ascontiguousarray(snaps[(slice(None),) + hull_of(plan)[1]])
-
-
-def quantile_threshold(snaps, plan, q):
-    """The q-quantile, over the box's nodes that ever hold anything, of the per-node max |p| (float32, as the plan holds it)."""
-    highest = np.abs(box_of(snaps, plan)).max(axis=0)
-    return np.float32(np.quantile(highest[highest > 0], q))
-
-
-def lateral_engine(case, tag, form, plan, edges, threshold, threshold_map=None):
-    set_tuning(**FORMS[form])
-    eng = make_engine(cases.CASES[case]() if isinstance(case, str) else case, tag)
-    shape = eng.set_lateral(edges, threshold, threshold_map=threshold_map, **plan, **constants(plan))
-    return eng, shape
 
 
 def same(got, want):
@@ -65,49 +58,7 @@ def same(got, want):
             raise AssertionError("%s differs at %d entries %s" % (key, (got[key] != want[key]).sum(), planes))
 
 
-def filled_bins(plane):
-    return (np.abs(plane).reshape(plane.shape[0], -1).max(axis=1) > 0).sum()
-
-
-def not_trivial(want, tensor=True):
-    """What the reference alone must show before a comparison means anything: at least a quarter of the nodes with an onset, at
-    least a quarter without, three distinct onsets, two bins that hold something in E and (tensor) in at least one Q plane."""
-    heard = want["onset"] != L.NONE
-    nodes = heard.size
-    assert heard.sum() >= nodes / 4 and (~heard).sum() >= nodes / 4, (heard.sum(), nodes)
-    assert len(set(want["onset"][heard].tolist())) >= 3, sorted(set(want["onset"][heard].tolist()))
-    assert filled_bins(want["bins"][0]) >= 2
-    if tensor:
-        assert max(filled_bins(want["bins"][a]) for a in range(4, 10)) >= 2
-
-
-def check(case_name, tag, form, plan, edges, n_steps, threshold, map_factors=None, query=None, trivial=not_trivial):
-    snaps, steps = reference_snapshots(case_name, tag, form, hull_of(plan)[0], n_steps)
-    thr = np.float32(threshold(snaps) if callable(threshold) else threshold)
-    threshold_map = None if map_factors is None else (thr * map_factors(box_of(snaps, plan).shape[1:])).astype(np.float32)
-    want = fold(snaps, plan, thr if threshold_map is None else threshold_map, edges)
-    if trivial:
-        trivial(want)
-    eng, shape = lateral_engine(case_name, tag, form, plan, edges, 0.0 if threshold_map is not None else thr, threshold_map)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.lateral_count() == (len(steps), int(steps[-1]))
-        got, captures = eng.fetch_lateral()
-        if query is not None:
-            assert eng.query(query) > 0
-        assert eng.query(E.Engine.QUERY_LATERAL_CAPTURES) == len(steps)
-        folds = eng.query(E.Engine.QUERY_LATERAL_FOLDS)
-    finally:
-        eng.close()
-    assert captures == len(steps) and len(steps) > 1
-    assert shape == want["bins"].shape
-    assert folds <= -(-len(steps) // 16) + 1
-    same(got, want)
-    return got, want, snaps
-
-
 PLANE = dict(box=((1, 1, 15), (30, 30, 1)))
-FORM_QUERIES = {"single": None, "graph": None, "pair": E.Engine.QUERY_PASSES, "triple": E.Engine.QUERY_TRIPLE_PASSES}
 
 
 @pytest.mark.parametrize("period", range(1, 8))
@@ -133,15 +84,15 @@ def test_every_stepping_form_gives_the_fold_of_the_hull_snapshots(form, period, 
     query = FORM_QUERIES[form] if (form == "pair" and period >= 2) or (form == "triple" and period >= 3) else None
     plan = dict(PLANE, period=period)
     if period % 2 == 1:
-        check("impulse_flat", tag, form, plan, (0, 1, 3), n_steps, lambda snaps: quantile_threshold(snaps, plan, 0.5), query=query)
+        check("lateral", "impulse_flat", tag, form, lateral_plan("impulse_flat", plan, (0, 1, 3), quantile(0.5)), n_steps, query)
         return
-    got, want, snaps = check("impulse_flat", tag, form, plan, (0, 1, 3), n_steps, lambda snaps: quantile_threshold(snaps, plan, 0.25), query=query,
-                             trivial=lambda want: not_trivial(want, tensor=False))
-    highest = np.abs(box_of(snaps, plan)).max(axis=0)
+    got, want, full, snaps, _ = check("lateral", "impulse_flat", tag, form, lateral_plan("impulse_flat", plan, (0, 1, 3), quantile(0.25)), n_steps, query,
+                                      condition=quarters)
+    highest = np.abs(box_of(snaps, full)).max(axis=0)
     assert (highest == 0).sum() >= highest.size / 2          # the silent colour: the plain median would be 0, or next to it
     heard = want["onset"] != L.NONE
     assert (want["bins"][1:, :, heard] == 0).all() and (want["velocity"][:, heard] == 0).all() and np.abs(want["velocity"][:, ~heard]).max() > 0
-    got, want, _ = check("impulse_flat", tag, form, plan, (0, 1, 3), n_steps, 0.0, trivial=None)
+    want = check("lateral", "impulse_flat", tag, form, lateral_plan("impulse_flat", plan, (0, 1, 3), 0.0), n_steps, condition=None)[1]
     assert (want["onset"] == 0).all() and filled_bins(want["bins"][0]) >= 2 and max(filled_bins(want["bins"][a]) for a in range(4, 10)) >= 2
 
 
@@ -157,8 +108,8 @@ def test_boxes_and_strides_on_a_room_with_walls(name, with_map):
     one behind it.  Once with the scalar median of the per-node maxima as the threshold, once with a per-node map of 0.1 .. 10 times
     that median.  (One node has no quarter of nodes to show: the box of one node is compared as it is.)"""
     plan = dict(BOXES[name], period=1)
-    check("random", "f64", "triple", plan, (0, 1, 5, 16, 17), 32, lambda snaps: quantile_threshold(snaps, plan, 0.5),
-          map_factors=_random_factors if with_map else None, trivial=not_trivial if name != "one-node" else None)
+    check("lateral", "random", "f64", "triple", lateral_plan("random", plan, (0, 1, 5, 16, 17), quantile(0.5), _random_factors if with_map else None), 32,
+          **(dict(condition=None) if name == "one-node" else {}))
 
 
 @pytest.mark.parametrize("w,n_bins", [(1, 8), (5, 7), (16, 3), (40, 2)])
@@ -166,7 +117,7 @@ def test_threshold_zero_and_even_edges_equal_the_intensity_plan(w, n_bins):
     """Every onset is capture 0: E and I are an intensity plan's bins of the same box, cadence and bin_captures, and the velocities
     its velocities, bytewise -- the merged fold and the new one on the same captures."""
     plan = dict(BOXES["sub-box-567-odd"], period=1)
-    got, want, snaps = check("random", "f64", "pair", plan, [k * w for k in range(n_bins)], 32, 0.0, trivial=None)
+    got = check("lateral", "random", "f64", "pair", lateral_plan("random", plan, [k * w for k in range(n_bins)], 0.0), 32, condition=None)[0]
     set_tuning(**FORMS["pair"])
     eng = make_engine(cases.CASES["random"](), "f64")
     eng.set_intensity(n_bins, w, **plan, **constants(plan))
@@ -188,10 +139,10 @@ def test_onset_pre_and_energy_equal_the_arrival_plan(name):
     onset, pre and bins, bytewise."""
     plan = dict(BOXES[name], period=1)
     edges = (0, 1, 5, 16, 17)
-    got, want, snaps = check("random", "f64", "pair", plan, edges, 32, lambda snaps: quantile_threshold(snaps, plan, 0.5))
+    got, _, full, _, _ = check("lateral", "random", "f64", "pair", lateral_plan("random", plan, edges, quantile(0.5)), 32)
     set_tuning(**FORMS["pair"])
     eng = make_engine(cases.CASES["random"](), "f64")
-    eng.set_arrival(edges, quantile_threshold(snaps, plan, 0.5), **plan)
+    eng.set_arrival(edges, full["threshold"], **plan)
     try:
         assert eng.run_steps(32) == (32, 0)
         arrival, captures = eng.fetch_arrival()
@@ -224,7 +175,7 @@ def test_the_receiver_path_carries_the_same_velocities(tag):
     finally:
         recv.close()
     for threshold in (1e30, 0.0):
-        eng, _ = lateral_engine(case, tag, "pair", plan, (0, 4), threshold)
+        eng = plan_engine(case, tag, "pair", lateral_plan(case, plan, (0, 4), threshold))
         try:
             assert eng.run_steps(n - 1) == (n - 1, 0)           # captures of steps 0 .. n - 1
             assert eng.lateral_count() == (n, n - 1)
@@ -235,151 +186,6 @@ def test_the_receiver_path_carries_the_same_velocities(tag):
         for r, (x, y, z) in enumerate(picks):
             assert recv_v[r].tobytes() == got["velocity"][:, z - 4, y - 2, x - 3].tobytes()
     assert np.abs(recv_v).min() > 0
-
-
-def test_fetching_mid_run_and_at_the_end():
-    plan = dict(BOXES["sub-box-630"], period=1)
-    edges = (0, 1, 5, 16, 17)
-    snaps, steps = reference_snapshots("random", "f64", "pair", hull_of(plan)[0], 30)
-    thr = quantile_threshold(snaps, plan, 0.5)
-    eng, _ = lateral_engine("random", "f64", "pair", plan, edges, thr)
-    try:
-        assert eng.run_steps(13) == (13, 0)
-        mid, mid_count = eng.fetch_lateral()
-        again, again_count = eng.fetch_lateral()
-        assert eng.run_steps(17) == (17, 0)
-        end, end_count = eng.fetch_lateral()
-    finally:
-        eng.close()
-    assert (mid_count, again_count, end_count) == (14, 14, 31)
-    same(mid, fold(snaps[:14], plan, thr, edges))
-    same(again, mid)
-    want = fold(snaps, plan, thr, edges)
-    same(end, want)
-    assert ((want["onset"] >= 14) & (want["onset"] != L.NONE)).any() and (want["onset"] < 14).any()   # onsets on both sides of the fetch
-
-
-@pytest.mark.parametrize("captures", [15, 16, 17, 32, 33])
-def test_capture_counts_around_the_stage(captures):
-    """Runs that take exactly 15, 16, 17, 32 and 33 captures: one fold per 16 captures and one for the fetch at the most."""
-    plan = dict(BOXES["sub-box-567-odd"], period=1)
-    edges = (0, 1, 5, 16, 17)
-    snaps, _ = reference_snapshots("random", "f64", "triple", hull_of(plan)[0], 32)
-    thr = quantile_threshold(snaps, plan, 0.5)
-    eng, _ = lateral_engine("random", "f64", "triple", plan, edges, thr)
-    try:
-        assert eng.run_steps(captures - 1) == (captures - 1, 0)
-        assert eng.lateral_count() == (captures, captures - 1)
-        assert eng.query(E.Engine.QUERY_LATERAL_FOLDS) <= (captures - 1) // 16   # (nothing is folded merely because a run ended)
-        got, count = eng.fetch_lateral()
-        assert count == captures == eng.query(E.Engine.QUERY_LATERAL_CAPTURES)
-        assert eng.query(E.Engine.QUERY_LATERAL_FOLDS) <= -(-captures // 16) + 1
-    finally:
-        eng.close()
-    want = fold(snaps[:captures], plan, thr, edges)
-    same(got, want)
-    assert (want["onset"] != L.NONE).any() and (want["onset"] == L.NONE).any()
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-def test_checkpoint_run_rollback_rerun_gives_the_same_state_twice(form):
-    """The impulse room's plane: the wavefront is crossing it at the checkpoint, so some onsets lie before it and some behind."""
-    plan = dict(PLANE, period=1)
-    edges = (0, 2, 6)
-    snaps, steps = reference_snapshots("impulse_flat", "f64", form, hull_of(plan)[0], 27)
-    thr = quantile_threshold(snaps, plan, 0.5)
-    want = fold(snaps, plan, thr, edges)
-    heard = want["onset"] != L.NONE
-    assert (want["onset"][heard] <= 10).any() and (want["onset"][heard] > 10).any()
-    eng, _ = lateral_engine("impulse_flat", "f64", form, plan, edges, thr)
-    try:
-        assert eng.run_steps(10) == (10, 0)            # captures of 0 .. 10
-        eng.checkpoint()
-        assert eng.run_steps(17) == (17, 0)
-        first, first_count = eng.fetch_lateral()
-        eng.rollback()
-        assert eng.step_count() == 10 and eng.lateral_count() == (11, 10)
-        kept, kept_count = eng.fetch_lateral()
-        assert eng.run_steps(17) == (17, 0)
-        second, second_count = eng.fetch_lateral()
-        assert eng.lateral_count() == (28, 27)
-        # a plan set after the checkpoint has no state to go back to
-        eng.set_lateral(edges, thr, **plan, **constants(plan))
-        with pytest.raises(E.WaveguideError, match="error -6: .*lateral plan was set after the checkpoint"):
-            eng.rollback()
-    finally:
-        eng.close()
-    assert (first_count, kept_count, second_count) == (28, 11, 28)
-    same(kept, fold(snaps[:11], plan, thr, edges))
-    same(first, want)
-    same(second, want)
-
-
-@pytest.mark.parametrize("bad_step", [12, 13])
-def test_a_run_that_stops_on_a_flag_holds_nothing_of_a_later_step(bad_step):
-    """inf in the source signal at step f: the run completes f steps; with a capture every 4 steps the state holds the captures of
-    0, 4, 8, 12 and nothing of 16, whose field the batch had already produced when the flag was read."""
-    set_tuning(**FORMS["triple"])
-    mesh = M.box_mesh(12, 12, 12)
-    sig = np.zeros(40)
-    sig[0] = 1.0
-    sig[bad_step] = np.inf
-    case = dict(mesh=mesh, init=None, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig,
-                recv=[mesh.compute_index(7, 6, 6)])
-    plan = dict(box=((1, 1, 5), (10, 10, 1)), period=4)
-    engines = [make_engine(case, "f64", hull_of(plan)[0]), make_engine(case, "f64")]
-    try:
-        engines[1].set_lateral((0, 1), 1e-3, **plan, **constants(plan))
-        for eng in engines:
-            done, flag = eng.run_steps(40)
-            assert done == bad_step and flag & M.ERR_INF
-        snaps, steps = engines[0].fetch_snapshots()
-        assert list(steps) == [0, 4, 8, 12] and engines[1].lateral_count() == (4, 12)
-        got, count = engines[1].fetch_lateral()
-    finally:
-        for eng in engines:
-            eng.close()
-    want = fold(snaps, plan, np.float32(1e-3), (0, 1))
-    assert count == 4 and np.isfinite(got["bins"]).all() and np.isfinite(got["velocity"]).all() and (want["onset"] != L.NONE).any()
-    same(got, want)
-
-
-def test_generic_steps_in_between_capture_nothing():
-    set_tuning(**FORMS["pair"])
-    case = cases.CASES["random"]()
-    plan = dict(box=((1, 1, 1), (22, 18, 2)), period=3)
-    engines = [make_engine(case, "f32"), make_engine(case, "f32")]
-    try:
-        for e in engines:
-            assert e.run_steps(9) == (9, 0)
-        engines[0].set_lateral((0, 1), 0.2, **plan, **constants(plan))   # steps 0, 3, 6 lie before the plan; 9 is the count it is set at
-        engines[1].set_snapshots(**hull_of(plan)[0])
-        assert engines[0].lateral_count() == (0, 0)
-        for e in engines:
-            assert e.run_steps(4) == (4, 0)               # 9 (at the start of this run), 12
-            for _ in range(3):                            # 13 -> 16 by generic steps: 15 is passed
-                assert e.step() == 0
-                e.swap()
-        assert engines[0].lateral_count() == (2, 12)
-        for e in engines:
-            assert e.run_steps(2) == (2, 0)               # 18
-        got, count = engines[0].fetch_lateral()
-        snaps, steps = engines[1].fetch_snapshots()
-        assert list(steps) == [9, 12, 18] and count == 3
-        want = fold(snaps, plan, np.float32(0.2), (0, 1))
-        same(got, want)
-        assert (want["onset"] != L.NONE).any() and (want["onset"] == L.NONE).any()
-        engines[0].set_lateral(None)                      # stops, forgets and frees ...
-        with pytest.raises(E.WaveguideError, match="error -6: .*no lateral plan"):
-            engines[0].lateral_count()
-        with pytest.raises(E.WaveguideError, match="error -6: .*no lateral plan"):
-            engines[0].fetch_lateral()
-        engines[0].set_decay(2, 2, **plan)                # ... and a decay plan takes its place
-        assert engines[0].run_steps(3) == (3, 0) and engines[0].decay_count() == (2, 21)
-        assert engines[0].fetch_decay()[0].max() > 0
-    finally:
-        for e in engines:
-            e.close()
 
 
 def test_refusals_leave_an_earlier_plan_intact_and_all_six_plans_exclude_each_other():
@@ -393,7 +199,7 @@ def test_refusals_leave_an_earlier_plan_intact_and_all_six_plans_exclude_each_ot
     c = constants(plan)
     edges = (0, 1, 5)
     snaps, _ = reference_snapshots("random", "f64", "single", hull_of(plan)[0], 32)
-    thr = quantile_threshold(snaps, plan, 0.5)
+    thr = quantile_threshold(snaps, plan_on("random", "lateral", **plan), 0.5)
     snapshot_plan = dict(box=plan["box"], period=1)
     intensity = dict(box=((1, 1, 1), (4, 4, 4)), **c)
     bands = np.array([[[1.0, 0, 0, 0, 0]]])
@@ -482,49 +288,27 @@ def test_refusals_leave_an_earlier_plan_intact_and_all_six_plans_exclude_each_ot
         group.close()
 
 
-@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("captures", FILE_COUNTS["lateral"])
+def test_capture_counts_around_the_stage(captures):
+    """One fold per 16 captures and one for the fetch at the most: plan_cases.capture_counts, at the counts this file always named
+    (tests/test_gpu_plan_life_cycle.py has the others)."""
+    capture_counts("lateral", captures)
+
+
+@pytest.mark.parametrize("form", FILE_FORMS["lateral"])
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_a_plan_changes_nothing_the_run_computes(form, tag):
-    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise."""
-    set_tuning(**FORMS[form])
-    case = cases.CASES["random"]()
-    out = []
-    for plan in (None, dict(box=((1, 1, 1), (22, 18, 26)), stride=(1, 2, 1), period=7, first_step=3)):
-        eng = make_engine(case, tag)
-        try:
-            if plan:
-                eng.set_lateral((0, 2, 4), 0.3, **plan, **constants(plan))
-            assert eng.run_steps(case["steps"]) == (case["steps"], 0)
-            out.append([eng.fetch_receivers(0, case["steps"]), eng.read_field(E.BUF_CURRENT), eng.read_field(E.BUF_PREVIOUS)] +
-                       [eng.read_boundary_data(d) for d in (1, 2, 3)])
-            if plan:
-                assert eng.lateral_count() == (9, 59)   # steps 3, 10, ..., 59
-        finally:
-            eng.close()
-    for a, b in zip(*out):
-        assert a.tobytes() == b.tobytes()
-    assert np.abs(out[0][0]).max() > 0
-
-
-def test_kernel_timing_accounts_for_both_kernels():
-    eng, _ = lateral_engine("impulse_flat", "f64", "single", dict(box=((1, 1, 1), (30, 30, 30)), period=1), (0, 4, 8), 1e-6)
-    try:
-        eng.enable_kernel_timing(True)
-        assert eng.run_steps(40) == (40, 0)
-        eng.fetch_lateral()
-        assert eng.query(E.Engine.QUERY_LATERAL_FOLDS) == 3 and eng.query(E.Engine.QUERY_LATERAL_NS) > 0
-        assert eng.query(E.Engine.QUERY_LATERAL_GATHERS) == 41 and eng.query(E.Engine.QUERY_LATERAL_GATHER_NS) > 0
-    finally:
-        eng.close()
+    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise:
+    plan_cases.changes_nothing, in the forms this file always named."""
+    changes_nothing("lateral", tag, form)
 
 
 def test_canonical_returns_the_maps_beside_the_receiver_output():
     """simulation.canonical(..., lateral=dict(plane=, every=, threshold=, edges_ms=)): the records are those of a run without a plan,
     the state is the definition's over canonical's own snapshots of the plane's hull at the same cadence, with the mesh's spacing,
     sample_rate / every and the environment's density filled in; a second plan beside it is refused with the engine's message."""
-    from test_gpu_decay import _box_scene
     set_tuning()
-    W, vm, source, receiver = _box_scene()
+    W, vm, source, receiver = box_scene()
     env = W.Environment()
     rate = W.compute_sample_rate(vm.mesh.spacing, env.speed_of_sound)
     seconds = 39.5 / rate      # 40 steps

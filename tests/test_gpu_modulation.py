@@ -14,10 +14,10 @@ import pytest
 
 import cases
 from helpers import set_tuning
-from test_gpu_decay import BOXES, reference_snapshots
-from test_gpu_decay_bands import sections
+from plan_cases import (BOXES, FILE_COUNTS, FILE_FORMS, FORMS, box_scene, capture_counts, changes_nothing, check, default_tuning_afterwards,
+                        make_engine, plan_engine, plan_on, reference_snapshots, sections)
+from plan_cases import every_band_and_frequency as not_zeros
 from test_gpu_plan_refusals import KINDS, SET, STOP, refusal
-from test_gpu_snapshots import FORMS, make_engine
 from wayverb_amd import decay as D
 from wayverb_amd import engine as E
 from wayverb_amd import mesh as M
@@ -34,7 +34,7 @@ SENTENCE = "a modulation plan is active (wv_set_modulation(e, NULL, NULL, NULL, 
 @pytest.fixture(autouse=True)
 def _default_tuning_afterwards(built_library):
     yield
-    set_tuning()
+    default_tuning_afterwards()
 
 
 def freqs(m):
@@ -42,44 +42,12 @@ def freqs(m):
     return np.array([0.013]) if m == 1 else np.linspace(0.0, 0.5, m)
 
 
-def not_zeros(energy, sums):
-    """every band holds energy, and every frequency of every band a sum"""
-    k, m = sums.shape[:2]
-    return bool((energy.reshape(k, -1).max(axis=1) > 0).all() and (np.abs(sums).reshape(k, m, -1).max(axis=2) > 0).all())
+def modulation_plan(case, cadence, bands, f):
+    return plan_on(case, "modulation", freqs=f, bands=bands, **cadence)
 
 
 def same(got, want):
     return got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
-
-
-def modulation_engine(case_name, tag, form, plan, bands, f):
-    set_tuning(**FORMS[form])
-    eng = make_engine(cases.CASES[case_name](), tag)
-    shape = eng.set_modulation(f, bands, **plan)
-    return eng, shape
-
-
-def check(case_name, tag, form, plan, bands, f, n_steps, query=None):
-    snaps, steps = reference_snapshots(case_name, tag, form, plan, n_steps)
-    want = MOD.modulation_fold(snaps, steps, f, bands)
-    eng, shape = modulation_engine(case_name, tag, form, plan, bands, f)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.modulation_count() == (len(steps), int(steps[-1]))
-        got = eng.fetch_modulation()
-        if query is not None:
-            assert eng.query(query) > 0
-        assert eng.query(E.Engine.QUERY_MODULATION_CAPTURES) == len(steps)
-        folds = eng.query(E.Engine.QUERY_MODULATION_FOLDS)
-    finally:
-        eng.close()
-    assert len(steps) > 1
-    assert got[1].shape == shape == want[1].shape == (bands.shape[0], len(f)) + snaps.shape[1:] and got[1].dtype == np.complex128
-    assert got[0].shape == want[0].shape == (bands.shape[0],) + snaps.shape[1:] and got[0].dtype == np.float64
-    assert folds <= -(-len(steps) // 16) + 1
-    assert same(got, want), "largest difference %g / %g" % (np.abs(got[0] - want[0]).max(), np.abs(got[1] - want[1]).max())
-    assert not_zeros(*want) and np.abs(snaps[-1]).max() > 0
-    return got, snaps, steps
 
 
 FORM_CASES = [(form, period, {("pair", 3): E.Engine.QUERY_PASSES, ("pair", 7): E.Engine.QUERY_PASSES, ("triple", 3): E.Engine.QUERY_TRIPLE_PASSES,
@@ -93,7 +61,7 @@ def test_every_stepping_form_gives_the_sums_of_the_snapshots(form, period, query
     """Single steps, graph replay, two- and three-step passes; period 1 (every step ends a pass), 3 (three-step passes stay whole) and 7;
     one plane of the 32^3 impulse room, three bands of four sections, five modulation frequencies."""
     n_steps = 64 if form == "graph" else 30
-    check("impulse_flat", tag, form, dict(box=((0, 0, 15), (None, None, 1)), period=period), sections(3, 4), freqs(5), n_steps, query)
+    check("modulation", "impulse_flat", tag, form, modulation_plan("impulse_flat", dict(box=((0, 0, 15), (None, None, 1)), period=period), sections(3, 4), freqs(5)), n_steps, query)
 
 
 MODULATION_BOXES = ["sub-box-630", "sub-box-567-odd", "one-node", "strides-1-2-3"]
@@ -105,46 +73,27 @@ def test_boxes_and_strides_with_the_state_carried_across_two_folds(name, tag):
     """tests/golden/cases.py "random": 24 x 20 x 28, six different wall filters; B = 630 (more than one workgroup), 567 (odd, a tail),
     one node, strides (1, 2, 3); every step captured, 21 captures: 16 in the first fold, 5 in the second, which starts from the state
     and the sums the first one stored; the standard's 14 frequencies' worth of planes."""
-    check("random", tag, "triple", dict(BOXES[name], period=1), sections(3, 4), freqs(14), 20)
+    check("modulation", "random", tag, "triple", modulation_plan("random", dict(BOXES[name], period=1), sections(3, 4), freqs(14)), 20)
 
 
 @pytest.mark.parametrize("k_bands,n_sections", [(1, 1), (2, 3), (8, 4)])
 @pytest.mark.parametrize("name", ["sub-box-630", "sub-box-567-odd"])
 def test_band_and_section_counts(name, k_bands, n_sections):
-    check("random", "f64", "pair", dict(BOXES[name], period=1), sections(k_bands, n_sections), freqs(5), 32)
+    check("modulation", "random", "f64", "pair", modulation_plan("random", dict(BOXES[name], period=1), sections(k_bands, n_sections), freqs(5)), 32)
 
 
 @pytest.mark.parametrize("m", [1, 5, 14, 16])
 @pytest.mark.parametrize("name", ["sub-box-630", "sub-box-567-odd"])
 def test_frequency_counts_on_either_side_of_the_chunk(name, m):
-    check("random", "f64", "pair", dict(BOXES[name], period=1), sections(2, 3), freqs(m), 32)
-
-
-@pytest.mark.parametrize("captures", [1, 16, 17, 33])
-def test_capture_counts_around_the_stage(captures):
-    n_steps = captures - 1
-    plan = dict(box=((3, 2, 4), (10, 9, 7)), period=1)
-    bands, f = sections(2, 3), freqs(5)
-    eng, _ = modulation_engine("random", "f64", "single", plan, bands, f)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.modulation_count() == (captures, n_steps)
-        assert eng.query(E.Engine.QUERY_MODULATION_FOLDS) <= (captures - 1) // 16   # (nothing is folded merely because a run ended)
-        got = eng.fetch_modulation()
-        assert captures == eng.query(E.Engine.QUERY_MODULATION_CAPTURES)
-        assert eng.query(E.Engine.QUERY_MODULATION_FOLDS) <= -(-captures // 16) + 1
-    finally:
-        eng.close()
-    snaps, steps = reference_snapshots("random", "f64", "single", plan, 32)
-    want = MOD.modulation_fold(snaps[:captures], steps[:captures], f, bands)
-    assert same(got, want) and not_zeros(*want)
+    check("modulation", "random", "f64", "pair", modulation_plan("random", dict(BOXES[name], period=1), sections(2, 3), freqs(m)), 32)
 
 
 @pytest.mark.parametrize("name", ["sub-box-630", "sub-box-567-odd"])
 def test_the_identity_section_at_zero_frequency_gives_the_plain_plans_sum(name):
     """{1, 0, 0, 0, 0} and f = 0: Re equals E bytewise, Im is zero, and both equal a plain decay plan's single bin."""
     plan = dict(BOXES[name], period=1)
-    got, snaps, _ = check("random", "f64", "pair", plan, IDENTITY, np.array([0.0]), 32)
+    got = check("modulation", "random", "f64", "pair", modulation_plan("random", plan, IDENTITY, np.array([0.0])), 32)[0]
+    got = (got["energy"], got["sums"])
     set_tuning(**FORMS["pair"])
     eng = make_engine(cases.CASES["random"](), "f64")
     eng.set_decay(1, 1, **plan)
@@ -155,132 +104,23 @@ def test_the_identity_section_at_zero_frequency_gives_the_plain_plans_sum(name):
     assert not got[1].imag.any()
 
 
-def test_fetching_mid_run_and_at_the_end():
-    plan = dict(box=((3, 2, 4), (10, 9, 7)), period=1)
-    bands, f = sections(3, 4), freqs(14)
-    eng, _ = modulation_engine("random", "f64", "pair", plan, bands, f)
-    assert eng.run_steps(13) == (13, 0)
-    mid, mid_count = eng.fetch_modulation(), eng.modulation_count()
-    again = eng.fetch_modulation()
-    assert eng.run_steps(17) == (17, 0)
-    end, end_count = eng.fetch_modulation(), eng.modulation_count()
-    # either destination may be NULL, and the captures come back with either
-    captures = E.C.c_uint64()
-    only_energy = np.zeros_like(end[0])
-    E._check(eng.lib.wv_fetch_modulation(eng.h, only_energy.ctypes.data_as(E.C.c_void_p), None, E.C.byref(captures)))
-    only_sums = np.zeros_like(end[1])
-    E._check(eng.lib.wv_fetch_modulation(eng.h, None, only_sums.ctypes.data_as(E.C.c_void_p), None))
-    E._check(eng.lib.wv_fetch_modulation(eng.h, None, None, None))
-    eng.close()
-    snaps, steps = reference_snapshots("random", "f64", "pair", plan, 30)
-    assert (mid_count, end_count, captures.value) == ((14, 13), (31, 30), 31)
-    want_mid, want_end = MOD.modulation_fold(snaps[:14], steps[:14], f, bands), MOD.modulation_fold(snaps, steps, f, bands)
-    assert same(mid, want_mid) and same(again, want_mid) and not_zeros(*want_mid)
-    assert same(end, want_end) and not_zeros(*want_end)      # (the fetch in between cut a fold in two: same bytes)
-    assert only_energy.tobytes() == end[0].tobytes() and only_sums.tobytes() == end[1].tobytes()
-    assert (end[0] >= mid[0]).all()
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-@pytest.mark.parametrize("bad_step", [12, 13, 14])
-def test_a_run_that_stops_on_a_flag_filters_no_capture_of_a_later_step(form, bad_step):
-    """inf in the source signal at step f, a capture every 4 steps: the sums hold the captures of 0, 4, 8, 12; the capture of 16, whose
-    field (inf / nan) the batch had already produced when the flag was read, reached neither a sum nor a filter state -- the continued
-    run's sums are those of the six snapshots in one go, finite."""
-    set_tuning(**FORMS[form])
-    mesh = M.box_mesh(12, 12, 12)
-    sig = np.zeros(40)
-    sig[0] = 1.0
-    sig[bad_step] = np.inf
-    case = dict(mesh=mesh, init=None, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig,
-                recv=[mesh.compute_index(7, 6, 6)])
-    plan = dict(box=((0, 0, 6), (None, None, 1)), period=4)
-    bands, f = sections(2, 3), freqs(5)
-    engines = [make_engine(case, "f64", plan), make_engine(case, "f64")]
-    engines[1].set_modulation(f, bands, **plan)
-    memories = [engines[0].read_boundary_data(d) for d in (1, 2, 3)]
-    for eng in engines:
-        done, flag = eng.run_steps(40)
-        assert done == bad_step and flag & M.ERR_INF
-    snaps, steps = engines[0].fetch_snapshots()
-    assert list(steps) == [0, 4, 8, 12]
-    assert engines[1].modulation_count() == (4, 12)
-    got = engines[1].fetch_modulation()
-    want = MOD.modulation_fold(snaps, steps, f, bands)
-    assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all() and same(got, want) and not_zeros(*want)
-    rng = np.random.default_rng(7)
-    fields = [rng.uniform(-1, 1, mesh.num_nodes) * (mesh.nodes["boundary_type"] & M.ID_INSIDE != 0) for _ in range(2)]
-    sig = np.zeros(16)
-    sig[1] = 0.5
-    for eng in engines:
-        eng.write_field(fields[0], E.BUF_PREVIOUS)
-        eng.write_field(fields[1], E.BUF_CURRENT)
-        for d, clean in zip((1, 2, 3), memories):
-            eng.write_boundary_data(d, clean)
-        eng.set_source(E.SOURCE_HARD, mesh.compute_index(6, 6, 6), sig)
-        assert eng.run_steps(8) == (8, 0)
-    snaps, steps = engines[0].fetch_snapshots()
-    assert list(steps) == [0, 4, 8, 12, 16, 20] and engines[1].modulation_count() == (6, 20)
-    got = engines[1].fetch_modulation()
-    for eng in engines:
+def test_either_destination_of_the_fetch_may_be_null():
+    """wv_fetch_modulation with a NULL for the energies, for the sums, for both: the other comes back, and the captures with either."""
+    plan = modulation_plan("random", dict(box=((3, 2, 4), (10, 9, 7)), period=1), sections(3, 4), freqs(14))
+    eng = plan_engine("random", "f64", "pair", plan)
+    try:
+        assert eng.run_steps(30) == (30, 0)
+        end = eng.fetch_modulation()
+        captures = E.C.c_uint64()
+        only_energy = np.zeros_like(end[0])
+        E._check(eng.lib.wv_fetch_modulation(eng.h, only_energy.ctypes.data_as(E.C.c_void_p), None, E.C.byref(captures)))
+        only_sums = np.zeros_like(end[1])
+        E._check(eng.lib.wv_fetch_modulation(eng.h, None, only_sums.ctypes.data_as(E.C.c_void_p), None))
+        E._check(eng.lib.wv_fetch_modulation(eng.h, None, None, None))
+    finally:
         eng.close()
-    want = MOD.modulation_fold(snaps, steps, f, bands)
-    assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all()
-    assert same(got, want) and not_zeros(*want)
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-def test_checkpoint_run_rollback_rerun_gives_the_same_sums_twice(form):
-    """The checkpoint holds sums AND filter states: after the rollback the three captures that follow are filtered from the state
-    capture 2 left, not from the one capture 5 left -- the re-run's sums are the first run's, and those of the six snapshots."""
-    plan = dict(box=((2, 3, 4), (12, 11, 9)), stride=(1, 2, 2), period=5)
-    bands, f = sections(3, 4), freqs(5)
-    eng, _ = modulation_engine("random", "f64", form, plan, bands, f)
-    assert eng.run_steps(10) == (10, 0)            # captures of 0, 5, 10
-    eng.checkpoint()
-    assert eng.run_steps(17) == (17, 0)            # 15, 20, 25
-    first, first_count = eng.fetch_modulation(), eng.modulation_count()
-    eng.rollback()
-    assert eng.step_count() == 10 and eng.modulation_count() == (3, 10)
-    kept = eng.fetch_modulation()
-    assert eng.run_steps(17) == (17, 0)
-    second = eng.fetch_modulation()
-    assert eng.modulation_count() == (6, 25) == first_count
-    # a plan set after the checkpoint has neither sums nor states to go back to
-    eng.set_modulation(f, bands, **plan)
-    assert refusal(lambda e: e.rollback(), eng) == [-6, "wv_rollback: the modulation plan was set after the checkpoint (its sums have no copy to go back to)"]
-    eng.close()
-    snaps, steps = reference_snapshots("random", "f64", form, plan, 27)
-    want = MOD.modulation_fold(snaps, steps, f, bands)
-    assert same(kept, MOD.modulation_fold(snaps[:3], steps[:3], f, bands))
-    assert same(first, want) and same(second, want) and not_zeros(*want)
-
-
-def test_generic_steps_in_between_are_gaps_in_the_series():
-    """wv_step / wv_swap capture nothing: the filters see the captures that were taken, back to back, and the twiddles are those of the
-    steps at which they were taken."""
-    set_tuning(**FORMS["pair"])
-    case = cases.CASES["random"]()
-    plan = dict(box=((0, 0, 0), (None, None, 2)), period=3)
-    bands, f = sections(2, 3), freqs(5)
-    engines = [make_engine(case, "f32"), make_engine(case, "f32")]
-    for e in engines:
-        assert e.run_steps(9) == (9, 0)
-    engines[0].set_modulation(f, bands, **plan)
-    engines[1].set_snapshots(**plan)
-    for e in engines:
-        assert e.run_steps(4) == (4, 0)               # 9 (at the start of this run), 12
-        for _ in range(3):                            # 13 -> 16 by generic steps: 15 is passed
-            assert e.step() == 0
-            e.swap()
-        assert e.run_steps(2) == (2, 0)               # 18
-    got, count = engines[0].fetch_modulation(), engines[0].modulation_count()
-    snaps, steps = engines[1].fetch_snapshots()
-    for e in engines:
-        e.close()
-    want = MOD.modulation_fold(snaps, steps, f, bands)
-    assert list(steps) == [9, 12, 18] and count == (3, 18)
-    assert same(got, want) and not_zeros(*want)
+    assert captures.value == 31 and not_zeros(*end)
+    assert only_energy.tobytes() == end[0].tobytes() and only_sums.tobytes() == end[1].tobytes()
 
 
 def test_bad_arguments_and_a_null_plan_leave_an_earlier_plan_intact():
@@ -381,40 +221,19 @@ def test_slabs_and_groups_refuse_the_plan():
     group.close()
 
 
-@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("captures", FILE_COUNTS["modulation"])
+def test_capture_counts_around_the_stage(captures):
+    """One fold per 16 captures and one for the fetch at the most: plan_cases.capture_counts, at the counts this file always named
+    (tests/test_gpu_plan_life_cycle.py has the others)."""
+    capture_counts("modulation", captures)
+
+
+@pytest.mark.parametrize("form", FILE_FORMS["modulation"])
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_a_modulation_plan_changes_nothing_the_run_computes(form, tag):
-    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise."""
-    set_tuning(**FORMS[form])
-    case = cases.CASES["random"]()
-    out = []
-    for plan in (None, dict(box="mesh", stride=(1, 2, 1), period=7, first_step=3)):
-        eng = make_engine(case, tag)
-        if plan:
-            eng.set_modulation(freqs(14), sections(3, 4), **plan)
-        done, flag = eng.run_steps(case["steps"])
-        assert (done, flag) == (case["steps"], 0)
-        out.append([eng.fetch_receivers(0, case["steps"]), eng.read_field(E.BUF_CURRENT), eng.read_field(E.BUF_PREVIOUS)] +
-                   [eng.read_boundary_data(d) for d in (1, 2, 3)])
-        if plan:
-            assert eng.modulation_count() == (9, 59)   # steps 3, 10, ..., 59
-            assert not_zeros(*eng.fetch_modulation())
-        eng.close()
-    for a, b in zip(*out):
-        assert a.tobytes() == b.tobytes()
-    assert np.abs(out[0][0]).max() > 0
-
-
-def test_queries_count_folds_and_captures_and_kernel_timing_accounts_for_the_fold_kernel():
-    eng, _ = modulation_engine("impulse_flat", "f64", "single", dict(box="mesh", period=1), sections(3, 4), freqs(14))
-    assert [eng.query(q) for q in (E.Engine.QUERY_MODULATION_CAPTURES, E.Engine.QUERY_MODULATION_FOLDS, E.Engine.QUERY_MODULATION_NS)] == [0, 0, 0]
-    eng.enable_kernel_timing(True)
-    assert eng.run_steps(20) == (20, 0)
-    assert eng.query(E.Engine.QUERY_MODULATION_CAPTURES) == 21 and eng.query(E.Engine.QUERY_MODULATION_FOLDS) == 1
-    eng.fetch_modulation()
-    assert eng.query(E.Engine.QUERY_MODULATION_FOLDS) == 2 and eng.query(E.Engine.QUERY_MODULATION_NS) > 0
-    assert eng.query(E.Engine.QUERY_DECAY_FOLDS) == 0 and eng.query(E.Engine.QUERY_SPECTRUM_FOLDS) == 0
-    eng.close()
+    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise:
+    plan_cases.changes_nothing, in the forms this file always named."""
+    changes_nothing("modulation", tag, form)
 
 
 def test_canonical_designs_the_bands_at_the_rate_of_the_captured_series():
@@ -422,8 +241,7 @@ def test_canonical_designs_the_bands_at_the_rate_of_the_captured_series():
     modulation_fold over canonical's own snapshots of the same box and cadence with butterworth_bandpass(lo, hi, sample_rate / 2) over
     the octaves around bands_hz and freqs_hz / sample_rate cycles per step."""
     set_tuning()
-    from test_gpu_decay import _box_scene
-    W, vm, source, receiver = _box_scene()
+    W, vm, source, receiver = box_scene()
     env = W.Environment()
     rate = W.compute_sample_rate(vm.mesh.spacing, env.speed_of_sound)
     seconds = 39.5 / rate      # 40 steps

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 import cases
-from helpers import initial_fields, set_tuning, subsample
+from helpers import set_tuning, subsample
+from plan_cases import FORMS, make_engine      # (their home; the files that import them from here go on doing so)
 from test_gpu_parity import _random_case
 from wayverb_amd import engine as E
 from wayverb_amd import mesh as M
@@ -13,13 +14,6 @@ from wayverb_amd.slab import SlabLayout, slab_mesh
 
 pytestmark = pytest.mark.gpu
 
-# how tests/test_gpu_pair.py and tests/test_gpu_triple.py force theirs (tile_lists=0: a small box would otherwise count as a sparse room)
-FORMS = {
-    "single": dict(pair=0, triple=0),
-    "graph": dict(pair=0, triple=0, graph=1),
-    "pair": dict(pair=1, triple=0, tile_lists=0),
-    "triple": dict(pair=1, triple=1, tile_lists=0),
-}
 
 
 @pytest.fixture(autouse=True)
@@ -28,23 +22,9 @@ def _default_tuning_afterwards(built_library):
     set_tuning()
 
 
-def make_engine(case, tag, plan=None):
-    eng = E.Engine(case["mesh"], precision=tag)
-    if case["init"] is not None:
-        prev, cur = initial_fields(case, eng.dtype)
-        eng.write_field(prev, E.BUF_PREVIOUS)
-        eng.write_field(cur, E.BUF_CURRENT)
-    eng.set_source(case["source_kind"], case["source_node"], case["signal"])
-    eng.set_receivers(case["recv"])
-    if plan is not None:
-        eng.set_snapshots(**plan)
-    return eng
-
-
 def plan_steps(plan, set_at, upto):
     first, period = plan.get("first_step", 0), plan.get("period", 1)
     return [s for s in range(first, upto + 1, period) if s >= set_at]
-
 
 
 def reference_snapshots(case, tag, plan, steps):

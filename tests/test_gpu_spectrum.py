@@ -11,7 +11,8 @@ import pytest
 
 import cases
 from helpers import numpy_fold, set_tuning
-from test_gpu_snapshots import FORMS, make_engine
+from plan_cases import (BOXES, FILE_COUNTS, FILE_FORMS, FORMS, FORM_CASES, box_scene, capture_counts, changes_nothing,
+                        check, default_tuning_afterwards, make_engine, plan_on)
 from wayverb_amd import engine as E
 from wayverb_amd import mesh as M
 from wayverb_amd.slab import SlabLayout, slab_mesh
@@ -25,61 +26,7 @@ FREQS5 = [0.0, 0.5, 0.125, 0.0371, 1.0 / 3.0]
 @pytest.fixture(autouse=True)
 def _default_tuning_afterwards(built_library):
     yield
-    set_tuning()
-
-
-
-_reference = {}
-
-
-def reference_snapshots(case_name, tag, form, plan, n_steps):
-    """(snapshots, steps) of an identical engine with a snapshot plan of the same box and cadence; computed once per key, read only."""
-    key = (case_name, tag, form, repr(sorted(plan.items())), n_steps)
-    if key not in _reference:
-        set_tuning(**FORMS[form])
-        eng = make_engine(cases.CASES[case_name](), tag, plan)
-        try:
-            assert eng.run_steps(n_steps) == (n_steps, 0)
-            snaps, steps = eng.fetch_snapshots()
-        finally:
-            eng.close()
-        snaps.setflags(write=False)
-        _reference[key] = (snaps, steps)
-    return _reference[key]
-
-
-def spectrum_engine(case_name, tag, form, plan, freqs):
-    set_tuning(**FORMS[form])
-    eng = make_engine(cases.CASES[case_name](), tag)
-    shape = eng.set_spectrum(freqs, **plan)
-    return eng, shape
-
-
-def check(case_name, tag, form, plan, freqs, n_steps, query=None):
-    snaps, steps = reference_snapshots(case_name, tag, form, plan, n_steps)
-    want = numpy_fold(snaps, steps, freqs)
-    eng, shape = spectrum_engine(case_name, tag, form, plan, freqs)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.spectrum_count() == (len(steps), int(steps[-1]))
-        got, captures = eng.fetch_spectrum()
-        if query is not None:
-            assert eng.query(query) > 0
-        assert eng.query(E.Engine.QUERY_SPECTRUM_CAPTURES) == len(steps)
-        folds = eng.query(E.Engine.QUERY_SPECTRUM_FOLDS)
-    finally:
-        eng.close()
-    assert captures == len(steps) and len(steps) > 1
-    assert got.shape == shape == want.shape and got.dtype == np.complex128
-    assert folds <= -(-len(steps) // 16) + 1
-    assert got.tobytes() == want.tobytes(), "largest difference %g" % np.abs(got - want).max()
-    assert np.abs(got).max() > 0 and np.abs(snaps[-1]).max() > 0   # (the comparison is not of zeros)
-    return got, snaps
-
-
-FORM_CASES = [("single", 1, None), ("single", 5, None), ("graph", 16, None),
-              ("pair", 2, E.Engine.QUERY_PASSES), ("pair", 3, E.Engine.QUERY_PASSES), ("pair", 7, E.Engine.QUERY_PASSES),
-              ("triple", 3, E.Engine.QUERY_TRIPLE_PASSES), ("triple", 4, E.Engine.QUERY_TRIPLE_PASSES), ("triple", 7, E.Engine.QUERY_TRIPLE_PASSES)]
+    default_tuning_afterwards()
 
 
 @pytest.mark.parametrize("form,period,query", FORM_CASES, ids=["%s-every%d" % c[:2] for c in FORM_CASES])
@@ -88,7 +35,9 @@ def test_every_stepping_form_gives_the_fold_of_the_snapshots(form, period, query
     """Single steps, graph replay, two- and three-step passes, periods that do and do not divide 2 and 3: one plane of the 32^3 impulse
     room, K = 5 with f = 0 and f = 0.5 among them.  At f = 0 the real part is the plain ordered sum and the imaginary part is zero."""
     n_steps = 64 if form == "graph" else 30
-    got, snaps = check("impulse_flat", tag, form, dict(box=((0, 0, 15), (None, None, 1)), period=period), FREQS5, n_steps, query)
+    plan = plan_on("impulse_flat", "spectrum", box=((0, 0, 15), (None, None, 1)), period=period, freqs=FREQS5)
+    got, _, _, snaps, _ = check("spectrum", "impulse_flat", tag, form, plan, n_steps, query)
+    got = got["spectrum"]
     plain = np.zeros(snaps.shape[1:])
     for p in snaps:
         plain = plain + p.astype(np.float64)
@@ -96,22 +45,12 @@ def test_every_stepping_form_gives_the_fold_of_the_snapshots(form, period, query
     assert got[0].imag.tobytes() == np.zeros_like(plain).tobytes()
 
 
-BOXES = {
-    "sub-box-630": dict(box=((3, 2, 4), (10, 9, 7))),             # not a multiple of 64, an odd number of rows; two nodes per lane
-    "sub-box-567-odd": dict(box=((3, 2, 4), (9, 9, 7))),          # an odd B: one node per lane, three workgroups, a tail
-    "sub-box-16-byte-rows": dict(box=((4, 1, 2), (16, 5, 3))),
-    "every-face-stride-3": dict(box="mesh", stride=3),            # 24 / 3, 20 / 3 and 28 / 3: the last two do not divide
-    "strides-1-2-3": dict(box=((1, 0, 2), (21, 20, 25)), stride=(1, 2, 3)),
-    "one-node": dict(box=((5, 6, 7), (1, 1, 1))),
-}
-
-
 @pytest.mark.parametrize("name", sorted(BOXES))
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_boxes_and_strides_on_a_room_with_walls(name, tag):
     """tests/golden/cases.py "random": 24 x 20 x 28, six different wall filters, a soft source; every step captured, 21 captures
     (more than the stage holds), three-step passes forced (which then run as single steps: every step ends a pass)."""
-    check("random", tag, "triple", dict(BOXES[name], period=1), FREQS5, 20)
+    check("spectrum", "random", tag, "triple", plan_on("random", "spectrum", freqs=FREQS5, period=1, **BOXES[name]), 20)
 
 
 @pytest.mark.parametrize("n_freqs", [1, 3, 4, 5, 9, 64])
@@ -120,147 +59,7 @@ def test_numbers_of_frequencies_around_the_chunk(name, n_freqs):
     """The fold kernel walks the frequencies in chunks of 4: one frequency, 3 / 4 / 5 around a chunk, 9 (two chunks and one), the
     maximum; with two nodes per lane and with one."""
     freqs = [0.25] if n_freqs == 1 else list(np.linspace(0.0, 0.5, n_freqs))
-    check("random", "f64", "pair", dict(BOXES[name], period=1), freqs, 20)
-
-
-@pytest.mark.parametrize("captures", [1, 16, 17, 33])
-def test_capture_counts_around_the_stage(captures):
-    """Runs that take exactly 1, 16, 17 and 33 captures: one fold per 16 captures and one for the fetch at the most."""
-    n_steps = captures - 1
-    plan = dict(box=((3, 2, 4), (10, 9, 7)), period=1)
-    eng, _ = spectrum_engine("random", "f64", "single", plan, FREQS5)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.spectrum_count() == (captures, n_steps)
-        assert eng.query(E.Engine.QUERY_SPECTRUM_FOLDS) <= (captures - 1) // 16   # (nothing is folded merely because a run ended)
-        got, count = eng.fetch_spectrum()
-        assert count == captures == eng.query(E.Engine.QUERY_SPECTRUM_CAPTURES)
-        assert eng.query(E.Engine.QUERY_SPECTRUM_FOLDS) <= -(-captures // 16) + 1
-    finally:
-        eng.close()
-    snaps, steps = reference_snapshots("random", "f64", "single", plan, 32)
-    assert got.tobytes() == numpy_fold(snaps[:captures], steps[:captures], FREQS5).tobytes()
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-def test_calls_of_1_7_and_30_steps_give_the_same_bytes(form):
-    plan = dict(box=((3, 2, 4), (10, 9, 7)), period=2)
-    out = []
-    for call in (1, 7, 30):
-        eng, _ = spectrum_engine("random", "f32", form, plan, FREQS5)
-        left = 30
-        while left:
-            n = min(call, left)
-            assert eng.run_steps(n) == (n, 0)
-            left -= n
-        out.append(eng.fetch_spectrum())
-        eng.close()
-    snaps, steps = reference_snapshots("random", "f32", form, plan, 30)
-    want = numpy_fold(snaps, steps, FREQS5)
-    for got, count in out:
-        assert count == 16 and got.tobytes() == want.tobytes()
-
-
-def test_fetching_mid_run_and_at_the_end():
-    plan = dict(box=((3, 2, 4), (10, 9, 7)), period=1)
-    eng, _ = spectrum_engine("random", "f64", "pair", plan, FREQS5)
-    assert eng.run_steps(13) == (13, 0)
-    mid, mid_count = eng.fetch_spectrum()
-    again, again_count = eng.fetch_spectrum()
-    assert eng.run_steps(17) == (17, 0)
-    end, end_count = eng.fetch_spectrum()
-    eng.close()
-    snaps, steps = reference_snapshots("random", "f64", "pair", plan, 30)
-    assert (mid_count, again_count, end_count) == (14, 14, 31)
-    assert mid.tobytes() == again.tobytes() == numpy_fold(snaps[:14], steps[:14], FREQS5).tobytes()
-    assert end.tobytes() == numpy_fold(snaps, steps, FREQS5).tobytes()
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-@pytest.mark.parametrize("bad_step", [12, 13, 14])
-def test_a_run_that_stops_on_a_flag_folds_no_capture_of_a_later_step(form, bad_step):
-    """inf in the source signal at step f: the run completes f steps; with a capture every 4 steps the sums hold those of 0, 4, 8, 12
-    and nothing of 16 (whose field the batch had already produced when the flag was read)."""
-    set_tuning(**FORMS[form])
-    mesh = M.box_mesh(12, 12, 12)
-    sig = np.zeros(40)
-    sig[0] = 1.0
-    sig[bad_step] = np.inf
-    case = dict(mesh=mesh, init=None, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig,
-                recv=[mesh.compute_index(7, 6, 6)])
-    plan = dict(box=((0, 0, 6), (None, None, 1)), period=4)
-    ref = make_engine(case, "f64", plan)
-    done, flag = ref.run_steps(40)
-    assert done == bad_step and flag & M.ERR_INF
-    snaps, steps = ref.fetch_snapshots()
-    ref.close()
-    assert list(steps) == [0, 4, 8, 12]
-    eng = make_engine(case, "f64")
-    eng.set_spectrum(FREQS5, **plan)
-    done, flag = eng.run_steps(40)
-    assert done == bad_step and flag & M.ERR_INF
-    assert eng.spectrum_count() == (4, 12)
-    got, count = eng.fetch_spectrum()
-    eng.close()
-    assert count == 4 and np.isfinite(got.view(np.float64)).all() and np.abs(got).max() > 0
-    assert got.tobytes() == numpy_fold(snaps, steps, FREQS5).tobytes()
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-def test_checkpoint_run_rollback_rerun_gives_the_same_sums_twice(form):
-    plan = dict(box=((2, 3, 4), (12, 11, 9)), stride=(1, 2, 2), period=5)
-    eng, _ = spectrum_engine("random", "f64", form, plan, FREQS5)
-    assert eng.run_steps(10) == (10, 0)            # captures of 0, 5, 10
-    eng.checkpoint()
-    assert eng.run_steps(17) == (17, 0)            # 15, 20, 25
-    first, first_count = eng.fetch_spectrum()
-    eng.rollback()
-    assert eng.step_count() == 10 and eng.spectrum_count() == (3, 10)
-    kept, kept_count = eng.fetch_spectrum()
-    assert eng.run_steps(17) == (17, 0)
-    second, second_count = eng.fetch_spectrum()
-    assert eng.spectrum_count() == (6, 25)
-    # a plan set after the checkpoint has no sums to go back to
-    eng.set_spectrum(FREQS5, **plan)
-    with pytest.raises(E.WaveguideError, match="error -6: .*after the checkpoint"):
-        eng.rollback()
-    eng.close()
-    snaps, steps = reference_snapshots("random", "f64", form, plan, 27)
-    assert (first_count, kept_count, second_count) == (6, 3, 6)
-    assert kept.tobytes() == numpy_fold(snaps[:3], steps[:3], FREQS5).tobytes()
-    assert first.tobytes() == second.tobytes() == numpy_fold(snaps, steps, FREQS5).tobytes()
-
-
-def test_generic_steps_in_between_capture_nothing():
-    """wv_step / wv_swap capture nothing and the plan steps they pass are passed; a plan set at a non-zero step count captures that
-    very step at the next run."""
-    set_tuning(**FORMS["pair"])
-    case = cases.CASES["random"]()
-    plan = dict(box=((0, 0, 0), (None, None, 2)), period=3)
-    engines = [make_engine(case, "f32"), make_engine(case, "f32")]
-    for e in engines:
-        assert e.run_steps(9) == (9, 0)
-    engines[0].set_spectrum(FREQS5, **plan)           # steps 0, 3, 6 lie before the plan; 9 is the count it is set at
-    engines[1].set_snapshots(**plan)
-    assert engines[0].spectrum_count() == (0, 0)
-    for e in engines:
-        assert e.run_steps(4) == (4, 0)               # 9 (at the start of this run), 12
-        for _ in range(3):                            # 13 -> 16 by generic steps: 15 is passed
-            assert e.step() == 0
-            e.swap()
-    assert engines[0].spectrum_count() == (2, 12)
-    for e in engines:
-        assert e.run_steps(2) == (2, 0)               # 18
-    got, count = engines[0].fetch_spectrum()
-    snaps, steps = engines[1].fetch_snapshots()
-    assert list(steps) == [9, 12, 18] and count == 3
-    assert got.tobytes() == numpy_fold(snaps, steps, FREQS5).tobytes() and np.abs(got).max() > 0
-    engines[0].set_spectrum(None)                     # stops and forgets
-    with pytest.raises(E.WaveguideError, match="error -6: .*no spectrum plan"):
-        engines[0].spectrum_count()
-    assert engines[0].run_steps(3) == (3, 0)
-    for e in engines:
-        e.close()
+    check("spectrum", "random", "f64", "pair", plan_on("random", "spectrum", freqs=freqs, period=1, **BOXES[name]), 20)
 
 
 def test_refusals_leave_an_earlier_plan_intact():
@@ -316,49 +115,26 @@ def test_refusals_leave_an_earlier_plan_intact():
     group.close()
 
 
-@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("captures", FILE_COUNTS["spectrum"])
+def test_capture_counts_around_the_stage(captures):
+    """One fold per 16 captures and one for the fetch at the most: plan_cases.capture_counts, at the counts this file always named
+    (tests/test_gpu_plan_life_cycle.py has the others)."""
+    capture_counts("spectrum", captures)
+
+
+@pytest.mark.parametrize("form", FILE_FORMS["spectrum"])
 @pytest.mark.parametrize("tag", ["f32", "f64"])
 def test_a_plan_changes_nothing_the_run_computes(form, tag):
-    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise."""
-    set_tuning(**FORMS[form])
-    case = cases.CASES["random"]()
-    out = []
-    for plan in (None, dict(box="mesh", stride=(1, 2, 1), period=7, first_step=3)):
-        eng = make_engine(case, tag)
-        if plan:
-            eng.set_spectrum(FREQS5, **plan)
-        assert eng.run_steps(case["steps"]) == (case["steps"], 0)
-        out.append([eng.fetch_receivers(0, case["steps"]), eng.read_field(E.BUF_CURRENT), eng.read_field(E.BUF_PREVIOUS)] +
-                   [eng.read_boundary_data(d) for d in (1, 2, 3)])
-        if plan:
-            assert eng.spectrum_count() == (9, 59)   # steps 3, 10, ..., 59
-        eng.close()
-    for a, b in zip(*out):
-        assert a.tobytes() == b.tobytes()
-
-
-def test_kernel_timing_accounts_for_the_fold_kernels():
-    eng, _ = spectrum_engine("impulse_flat", "f64", "single", dict(box="mesh", period=1), FREQS5)
-    eng.enable_kernel_timing(True)
-    assert eng.run_steps(20) == (20, 0)
-    eng.fetch_spectrum()
-    assert eng.query(E.Engine.QUERY_SPECTRUM_FOLDS) == 2 and eng.query(E.Engine.QUERY_SPECTRUM_NS) > 0
-    eng.close()
-
-
-def _box_scene():
-    from wayverb_amd import simulation as W
-    mesh = M.box_mesh(24, 24, 24, coefficients=np.array([M.flat_coefficients(0.1)], dtype=M.coefficients_dtype))
-    vm = W.VoxelsAndMesh(None, None, 0, None, None, mesh, (0.0, 0.0, 0.0))
-    sp = mesh.spacing
-    return W, vm, (12 * sp, 12 * sp, 12 * sp), (15 * sp, 12 * sp, 12 * sp)
+    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise:
+    plan_cases.changes_nothing, in the forms this file always named."""
+    changes_nothing("spectrum", tag, form)
 
 
 def test_canonical_returns_the_spectrum_beside_the_receiver_output():
     """simulation.canonical(..., spectrum=...): Hz become cycles per step with the run's sample rate, the records are those of a run
     without a plan, and the spectrum is the engine-level one (the fold of canonical's own snapshots of the same box and cadence)."""
     set_tuning()
-    W, vm, source, receiver = _box_scene()
+    W, vm, source, receiver = box_scene()
     env = W.Environment()
     rate = W.compute_sample_rate(vm.mesh.spacing, env.speed_of_sound)
     seconds = 39.5 / rate      # 40 steps

@@ -17,9 +17,9 @@ import plan_argument_faults as F
 import plan_twin as P
 import waterfall_twin as T
 from helpers import numpy_fold, set_tuning
-from test_gpu_decay import BOXES, FORM_CASES, LAYOUTS, _box_scene, reference_snapshots
+from plan_cases import (BOXES, FILE_COUNTS, FILE_FORMS, FORM_CASES, LAYOUTS, box_scene, capture_counts, changes_nothing, check,
+                        default_tuning_afterwards, make_engine, plan_engine, plan_on, reference_snapshots)
 from test_gpu_plan_refusals import BANDS, SET, STOP, refusal
-from test_gpu_snapshots import FORMS, make_engine
 from wayverb_amd import engine as E
 from wayverb_amd import mesh as M
 from wayverb_amd import waterfall as WF
@@ -34,7 +34,7 @@ SUB_BOX = dict(box=((3, 2, 4), (10, 9, 7)), period=1)      # BOXES["sub-box-630"
 @pytest.fixture(autouse=True)
 def _default_tuning_afterwards(built_library):
     yield
-    set_tuning()
+    default_tuning_afterwards()
 
 
 def freqs_of(k):
@@ -42,37 +42,13 @@ def freqs_of(k):
     return ([0.0, 0.5] + [float(f) for f in np.random.default_rng(k).uniform(0.0, 0.5, max(k - 2, 0))])[:k]
 
 
-def waterfall_engine(case_name, tag, form, plan, freqs, n_bins, bin_captures):
-    set_tuning(**FORMS[form])
-    eng = make_engine(cases.CASES[case_name](), tag)
-    return eng, eng.set_waterfall(freqs, n_bins, bin_captures, **plan)
+def waterfall_plan(case, cadence, freqs, n_bins, bin_captures):
+    return plan_on(case, "waterfall", freqs=freqs, n_bins=n_bins, bin_captures=bin_captures, **cadence)
 
 
 def nonzero(bins):
     """Not a comparison of zeros: something in the real parts, and in the imaginary ones wherever a frequency has any."""
     return bool(np.abs(bins.real).max() > 0)
-
-
-def check(case_name, tag, form, plan, freqs, n_bins, bin_captures, n_steps, query=None):
-    snaps, steps = reference_snapshots(case_name, tag, form, plan, n_steps)
-    want = WF.waterfall_fold(snaps, steps, freqs, n_bins, bin_captures)
-    eng, shape = waterfall_engine(case_name, tag, form, plan, freqs, n_bins, bin_captures)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.waterfall_count() == (len(steps), int(steps[-1]))
-        got, captures = eng.fetch_waterfall()
-        if query is not None:
-            assert eng.query(query) > 0
-        assert eng.query(E.Engine.QUERY_WATERFALL_CAPTURES) == len(steps)
-        folds = eng.query(E.Engine.QUERY_WATERFALL_FOLDS)
-    finally:
-        eng.close()
-    assert captures == len(steps) and len(steps) > 1
-    assert got.shape == shape == want.shape == (n_bins, len(freqs)) + snaps.shape[1:] and got.dtype == np.complex128
-    assert folds <= -(-len(steps) // 16) + 1
-    assert got.tobytes() == want.tobytes(), "largest difference %g" % np.abs(got - want).max()
-    assert nonzero(got) and np.abs(snaps[-1]).max() > 0
-    return got, snaps, steps
 
 
 @pytest.mark.parametrize("form,period,query", FORM_CASES, ids=["%s-every%d" % c[:2] for c in FORM_CASES])
@@ -82,7 +58,7 @@ def test_every_stepping_form_gives_the_sums_of_the_snapshots(form, period, query
     room, K = 3, four captures per bin."""
     n_steps = 64 if form == "graph" else 30
     captures = n_steps // period + 1
-    check("impulse_flat", tag, form, dict(box=((0, 0, 15), (None, None, 1)), period=period), freqs_of(3), -(-captures // 4), 4, n_steps, query)
+    check("waterfall", "impulse_flat", tag, form, waterfall_plan("impulse_flat", dict(box=((0, 0, 15), (None, None, 1)), period=period), freqs_of(3), -(-captures // 4), 4), n_steps, query)
 
 
 @pytest.mark.parametrize("name", sorted(BOXES))
@@ -90,7 +66,7 @@ def test_every_stepping_form_gives_the_sums_of_the_snapshots(form, period, query
 def test_boxes_and_strides_on_a_room_with_walls(name, tag):
     """tests/golden/cases.py "random": 24 x 20 x 28, six different wall filters, a soft source; every step captured, 21 captures (more
     than the stage holds), K = 5, 7 bins of 3."""
-    check("random", tag, "triple", dict(BOXES[name], period=1), freqs_of(5), 7, 3, 20)
+    check("waterfall", "random", tag, "triple", waterfall_plan("random", dict(BOXES[name], period=1), freqs_of(5), 7, 3), 20)
 
 
 @pytest.mark.parametrize("k", [1, 3, 4, 5, 9, 64])
@@ -98,7 +74,7 @@ def test_boxes_and_strides_on_a_room_with_walls(name, tag):
 def test_numbers_of_frequencies_around_the_chunk_in_both_lane_widths(name, k):
     """K below, at and above the fold's chunk of four, a chunk with a tail, and the most there is; B even (two nodes per lane) and odd
     (one): 33 captures into 4 bins of 5, the last open-ended."""
-    check("random", "f64", "pair", dict(BOXES[name], period=1), freqs_of(k), 4, 5, 32)
+    check("waterfall", "random", "f64", "pair", waterfall_plan("random", dict(BOXES[name], period=1), freqs_of(k), 4, 5), 32)
 
 
 LAYOUT_CASES = [(layout, k) for layout in sorted(LAYOUTS) for k in (1, 5) if LAYOUTS[layout][0] * k <= 4096]
@@ -111,72 +87,18 @@ def test_bin_layouts_against_the_stage(name, layout, k):
     bin, edges inside and across folds, whole folds inside one bin, one bin, the open-ended last bin.  4096 bins are more than the cap
     on sums allows at K = 5: that layout runs at K = 1, where the bins no capture reached must be +0.0 with the sign bit clear."""
     n_bins, bin_captures = LAYOUTS[layout]
-    got, _, _ = check("random", "f64", "pair", dict(BOXES[name], period=1), freqs_of(k), n_bins, bin_captures, 32)
+    got = check("waterfall", "random", "f64", "pair", waterfall_plan("random", dict(BOXES[name], period=1), freqs_of(k), n_bins, bin_captures), 32)[0]["waterfall"]
     if layout == "more-bins-than-captures":
         untouched = np.stack([got[33:].real, got[33:].imag])
         assert k == 1 and (untouched == 0).all() and not np.signbit(untouched).any()
     assert ("more-bins-than-captures", 1) in LAYOUT_CASES and len(LAYOUT_CASES) == 15
 
 
-@pytest.mark.parametrize("captures", [1, 16, 17, 33])
-def test_capture_counts_around_the_stage(captures):
-    """Runs that take exactly 1, 16, 17 and 33 captures: one fold per 16 captures and one for the fetch at the most."""
-    n_steps = captures - 1
-    freqs = freqs_of(5)
-    eng, _ = waterfall_engine("random", "f64", "single", SUB_BOX, freqs, 5, 5)
-    try:
-        assert eng.run_steps(n_steps) == (n_steps, 0)
-        assert eng.waterfall_count() == (captures, n_steps)
-        assert eng.query(E.Engine.QUERY_WATERFALL_FOLDS) <= (captures - 1) // 16   # (nothing is folded merely because a run ended)
-        got, count = eng.fetch_waterfall()
-        assert count == captures == eng.query(E.Engine.QUERY_WATERFALL_CAPTURES)
-        assert eng.query(E.Engine.QUERY_WATERFALL_FOLDS) <= -(-captures // 16) + 1
-    finally:
-        eng.close()
-    snaps, steps = reference_snapshots("random", "f64", "single", SUB_BOX, 32)
-    assert got.tobytes() == WF.waterfall_fold(snaps[:captures], steps[:captures], freqs, 5, 5).tobytes() and nonzero(got)
-
-
-def test_calls_of_one_seven_and_thirty_steps_give_the_same_bytes():
-    freqs = freqs_of(4)
-    snaps, steps = reference_snapshots("random", "f64", "pair", SUB_BOX, 30)
-    want = WF.waterfall_fold(snaps, steps, freqs, 6, 5)
-    for call in (1, 7, 30):
-        eng, _ = waterfall_engine("random", "f64", "pair", SUB_BOX, freqs, 6, 5)
-        try:
-            done = 0
-            while done < 30:
-                n = min(call, 30 - done)
-                assert eng.run_steps(n) == (n, 0)
-                done += n
-            got, count = eng.fetch_waterfall()
-        finally:
-            eng.close()
-        assert count == 31 and got.tobytes() == want.tobytes(), call
-    assert nonzero(want)
-
-
-def test_fetching_mid_run_and_at_the_end():
-    freqs = freqs_of(5)
-    eng, _ = waterfall_engine("random", "f64", "pair", SUB_BOX, freqs, 6, 5)
-    assert eng.run_steps(13) == (13, 0)
-    mid, mid_count = eng.fetch_waterfall()
-    again, again_count = eng.fetch_waterfall()
-    assert eng.run_steps(17) == (17, 0)
-    end, end_count = eng.fetch_waterfall()
-    eng.close()
-    snaps, steps = reference_snapshots("random", "f64", "pair", SUB_BOX, 30)
-    assert (mid_count, again_count, end_count) == (14, 14, 31)
-    assert mid.tobytes() == again.tobytes() == WF.waterfall_fold(snaps[:14], steps[:14], freqs, 6, 5).tobytes()
-    assert end.tobytes() == WF.waterfall_fold(snaps, steps, freqs, 6, 5).tobytes() and nonzero(end) and nonzero(mid)
-    assert end[:2].tobytes() == mid[:2].tobytes() and end[2].tobytes() != mid[2].tobytes()       # full bins stay, the bin in progress grows
-
-
 @pytest.mark.parametrize("k", [1, 5])
 def test_one_bin_is_the_spectrum_plan_bytewise(k):
     """n_bins = 1: the bytes of fetch_spectrum of an identical engine (and of the spectrum's definition, helpers.numpy_fold)."""
     freqs = freqs_of(k)
-    eng, _ = waterfall_engine("random", "f64", "triple", SUB_BOX, freqs, 1, 3)
+    eng = plan_engine("random", "f64", "triple", waterfall_plan("random", SUB_BOX, freqs, 1, 3))
     other = make_engine(cases.CASES["random"](), "f64")
     other.set_spectrum(freqs, **SUB_BOX)
     try:
@@ -190,147 +112,6 @@ def test_one_bin_is_the_spectrum_plan_bytewise(k):
     snaps, steps = reference_snapshots("random", "f64", "triple", SUB_BOX, 20)
     assert count == spectrum_count == 21 and got.shape == (1,) + spectrum.shape
     assert got[0].tobytes() == spectrum.tobytes() == numpy_fold(snaps, steps, freqs).tobytes() and nonzero(got)
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-@pytest.mark.parametrize("bad_step", [12, 13, 14])
-def test_a_run_that_stops_on_a_flag_folds_no_capture_of_a_later_step(form, bad_step):
-    """inf in the source signal at step f: the run completes f steps; with a capture every 4 steps the sums hold those of 0, 4, 8, 12
-    and nothing of 16 (whose field the batch had already produced when the flag was read).  A following run goes on from there."""
-    set_tuning(**FORMS[form])
-    mesh = M.box_mesh(12, 12, 12)
-    sig = np.zeros(40)
-    sig[0] = 1.0
-    sig[bad_step] = np.inf
-    case = dict(mesh=mesh, init=None, source_kind=E.SOURCE_HARD, source_node=mesh.compute_index(6, 6, 6), signal=sig,
-                recv=[mesh.compute_index(7, 6, 6)])
-    plan = dict(box=((0, 0, 6), (None, None, 1)), period=4)
-    freqs = freqs_of(3)
-    engines = [make_engine(case, "f64", plan), make_engine(case, "f64")]
-    engines[1].set_waterfall(freqs, 3, 2, **plan)
-    memories = [engines[0].read_boundary_data(d) for d in (1, 2, 3)]
-    for eng in engines:
-        done, flag = eng.run_steps(40)
-        assert done == bad_step and flag & M.ERR_INF
-    snaps, steps = engines[0].fetch_snapshots()
-    assert list(steps) == [0, 4, 8, 12]
-    assert engines[1].waterfall_count() == (4, 12)
-    got, count = engines[1].fetch_waterfall()
-    assert count == 4 and np.isfinite(got.real).all() and np.isfinite(got.imag).all() and nonzero(got)
-    assert got.tobytes() == WF.waterfall_fold(snaps, steps, freqs, 3, 2).tobytes()
-    # the next run continues: the failed steps left inf / nan behind, so both engines get the same finite fields, clean filter memories
-    # and a finite source; the capture of step 16, dropped above, is due again and the plan goes on counting from capture 4
-    rng = np.random.default_rng(7)
-    fields = [rng.uniform(-1, 1, mesh.num_nodes) * (mesh.nodes["boundary_type"] & M.ID_INSIDE != 0) for _ in range(2)]
-    sig = np.zeros(16)
-    sig[1] = 0.5
-    for eng in engines:
-        eng.write_field(fields[0], E.BUF_PREVIOUS)
-        eng.write_field(fields[1], E.BUF_CURRENT)
-        for d, clean in zip((1, 2, 3), memories):
-            eng.write_boundary_data(d, clean)
-        eng.set_source(E.SOURCE_HARD, mesh.compute_index(6, 6, 6), sig)
-        assert eng.run_steps(8) == (8, 0)
-    snaps, steps = engines[0].fetch_snapshots()
-    assert list(steps) == [0, 4, 8, 12, 16, 20] and engines[1].waterfall_count() == (6, 20)
-    got, count = engines[1].fetch_waterfall()
-    for eng in engines:
-        eng.close()
-    assert count == 6 and np.isfinite(got.real).all() and np.abs(got[2]).max() > 0
-    assert got.tobytes() == WF.waterfall_fold(snaps, steps, freqs, 3, 2).tobytes()
-
-
-@pytest.mark.parametrize("form", ["single", "triple"])
-def test_checkpoint_run_rollback_rerun_gives_the_same_sums_twice(form):
-    plan = dict(box=((2, 3, 4), (12, 11, 9)), stride=(1, 2, 2), period=5)
-    freqs = freqs_of(5)
-    eng, _ = waterfall_engine("random", "f64", form, plan, freqs, 3, 2)
-    assert eng.run_steps(10) == (10, 0)            # captures of 0, 5, 10
-    eng.checkpoint()
-    assert eng.run_steps(17) == (17, 0)            # 15, 20, 25
-    first, first_count = eng.fetch_waterfall()
-    eng.rollback()
-    assert eng.step_count() == 10 and eng.waterfall_count() == (3, 10)
-    kept, kept_count = eng.fetch_waterfall()
-    assert eng.run_steps(17) == (17, 0)
-    second, second_count = eng.fetch_waterfall()
-    assert eng.waterfall_count() == (6, 25)
-    # a plan set after the checkpoint has no sums to go back to
-    eng.set_waterfall(freqs, 3, 2, **plan)
-    with pytest.raises(E.WaveguideError, match=r"error -6: wv_rollback: the waterfall plan was set after the checkpoint \(its sums have no copy to go back to\)"):
-        eng.rollback()
-    eng.close()
-    snaps, steps = reference_snapshots("random", "f64", form, plan, 27)
-    assert (first_count, kept_count, second_count) == (6, 3, 6)
-    assert kept.tobytes() == WF.waterfall_fold(snaps[:3], steps[:3], freqs, 3, 2).tobytes() and nonzero(kept)
-    assert first.tobytes() == second.tobytes() == WF.waterfall_fold(snaps, steps, freqs, 3, 2).tobytes() and nonzero(first)
-
-
-def test_generic_steps_in_between_capture_nothing():
-    """wv_step / wv_swap capture nothing and the plan steps they pass are passed; a plan set at a non-zero step count captures that
-    very step at the next run: the pinned example of period 3 at step 9."""
-    set_tuning(**FORMS["pair"])
-    case = cases.CASES["random"]()
-    plan = dict(box=((0, 0, 0), (None, None, 2)), period=3)
-    freqs = freqs_of(3)
-    engines = [make_engine(case, "f32"), make_engine(case, "f32")]
-    for e in engines:
-        assert e.run_steps(9) == (9, 0)
-    engines[0].set_waterfall(freqs, 2, 2, **plan)       # steps 0, 3, 6 lie before the plan; 9 is the count it is set at
-    engines[1].set_snapshots(**plan)
-    assert engines[0].waterfall_count() == (0, 0)
-    for e in engines:
-        assert e.run_steps(4) == (4, 0)               # 9 (at the start of this run), 12
-        for _ in range(3):                            # 13 -> 16 by generic steps: 15 is passed
-            assert e.step() == 0
-            e.swap()
-    assert engines[0].waterfall_count() == (2, 12)
-    for e in engines:
-        assert e.run_steps(2) == (2, 0)               # 18
-    got, count = engines[0].fetch_waterfall()
-    snaps, steps = engines[1].fetch_snapshots()
-    assert list(steps) == [9, 12, 18] and count == 3
-    assert got.tobytes() == WF.waterfall_fold(snaps, steps, freqs, 2, 2).tobytes() and nonzero(got) and np.abs(got[1]).max() > 0
-    engines[0].set_waterfall(None, None, None)        # stops and forgets
-    with pytest.raises(E.WaveguideError, match="error -6: wv_waterfall_count: no waterfall plan is set"):
-        engines[0].waterfall_count()
-    with pytest.raises(E.WaveguideError, match="error -6: wv_fetch_waterfall: no waterfall plan is set"):
-        engines[0].fetch_waterfall()
-    assert engines[0].run_steps(3) == (3, 0)
-    for e in engines:
-        e.close()
-
-
-@pytest.mark.parametrize("form", sorted(FORMS))
-@pytest.mark.parametrize("tag", ["f32", "f64"])
-def test_a_plan_changes_nothing_the_run_computes(form, tag):
-    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise."""
-    set_tuning(**FORMS[form])
-    case = cases.CASES["random"]()
-    out = []
-    for plan in (None, dict(box="mesh", stride=(1, 2, 1), period=7, first_step=3)):
-        eng = make_engine(case, tag)
-        if plan:
-            eng.set_waterfall(freqs_of(5), 4, 2, **plan)
-        assert eng.run_steps(case["steps"]) == (case["steps"], 0)
-        out.append([eng.fetch_receivers(0, case["steps"]), eng.read_field(E.BUF_CURRENT), eng.read_field(E.BUF_PREVIOUS)] +
-                   [eng.read_boundary_data(d) for d in (1, 2, 3)])
-        if plan:
-            assert eng.waterfall_count() == (9, 59)   # steps 3, 10, ..., 59
-        eng.close()
-    for a, b in zip(*out):
-        assert a.tobytes() == b.tobytes()
-    assert np.abs(out[0][0]).max() > 0
-
-
-def test_kernel_timing_accounts_for_the_fold_kernels():
-    eng, _ = waterfall_engine("impulse_flat", "f64", "single", dict(box="mesh", period=1), freqs_of(3), 3, 8)
-    eng.enable_kernel_timing(True)
-    assert eng.run_steps(20) == (20, 0)
-    eng.fetch_waterfall()
-    folds = eng.query(E.Engine.QUERY_WATERFALL_FOLDS)
-    assert folds == 2 <= -(-21 // 16) + 1 and eng.query(E.Engine.QUERY_WATERFALL_NS) > 0
-    eng.close()
 
 
 # ---- refusals: the 12 x 10 x 9 fp32 box mesh of tests/plan_argument_faults.py, no stepping ------------------------------------------
@@ -485,8 +266,9 @@ MODES = {"default": {}, "three-step-passes": dict(pair=1, triple=1), "single-ste
 _script = {}
 
 
-@pytest.fixture(scope="module")
+@pytest.fixture(scope="module", autouse=True)
 def waterfall_family():
+    """(for the whole module: the shared check reads the kind's entry too)"""
     with T.registered():
         yield
 
@@ -509,11 +291,26 @@ def test_random_plan_sequence(oracle, waterfall_family, seed, mode):
 
 # ---- the Python front and the tools -----------------------------------------------------------------------------------------------------
 
+@pytest.mark.parametrize("captures", FILE_COUNTS["waterfall"])
+def test_capture_counts_around_the_stage(captures):
+    """One fold per 16 captures and one for the fetch at the most: plan_cases.capture_counts, at the counts this file always named
+    (tests/test_gpu_plan_life_cycle.py has the others)."""
+    capture_counts("waterfall", captures)
+
+
+@pytest.mark.parametrize("form", FILE_FORMS["waterfall"])
+@pytest.mark.parametrize("tag", ["f32", "f64"])
+def test_a_plan_changes_nothing_the_run_computes(form, tag):
+    """Receiver traces, final current / previous and the filter memories with a plan equal those without one, bytewise:
+    plan_cases.changes_nothing, in the forms this file always named."""
+    changes_nothing("waterfall", tag, form)
+
+
 def test_canonical_returns_the_bins_beside_the_receiver_output():
     """simulation.canonical(..., waterfall=...): the records are those of a run without a plan, the bins are the engine-level ones
     (folded from canonical's own snapshots of the same box and cadence); a second plan beside it is refused with the engine's message."""
     set_tuning()
-    W, vm, source, receiver = _box_scene()
+    W, vm, source, receiver = box_scene()
     env = W.Environment()
     rate = W.compute_sample_rate(vm.mesh.spacing, env.speed_of_sound)
     seconds = 39.5 / rate      # 40 steps
